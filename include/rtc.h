@@ -87,6 +87,12 @@ typedef struct RtcRenderDesc {
                                       their places of the host frame (rtc_copy_rows_d2h_dma, its own PCIe link);
                                       without it the parts are gathered to device 0 over RCCL, re-interleaved there
                                       and copied once.  Same frame bit for bit. */
+#define RTC_F_SPLIT_SPHERES 0x2000 /* a launch that renders spheres takes the split launch (tile cull with sphere coverage,
+                                      sky pass, rtc_render_chain with spheres) even where the scene's gate keeps it on
+                                      the one-lane-per-pixel kernel (rtc_scene_sphere_split == 0); A/B timing and tests,
+                                      like RTC_F_NO_COOP.  Never more than 32 spheres, and not with RTC_F_NO_COOP,
+                                      RTC_F_NO_REORDER, RTC_F_NO_TILE_CULL or RTC_F_DEBUG_BOUNCES.  Same frame bit for
+                                      bit. */
 #define RTC_F_OVERLAP       0x800 /* frame pipelining (device-resident split only): the launch does not make
                                      `stream` wait for its sky pass, so the next launches on the same scene render
                                      (scratch in 8 slots) while this one's sky pass still runs.  A later overlapped
@@ -219,6 +225,21 @@ int rtc_scene_kernel_times(const RtcDeviceScene *s, float out[2]);
  * scene got from it (4 above 0.15, else 3; small row shares run 3). */
 int rtc_bounce_hit_share(const Triangle *tris, int triCount, float *share);
 int rtc_scene_chain_wgs(const RtcDeviceScene *s);
+/* Sphere scenes (calculateRayCollision's sphere loop, raytracing.c:219-228).  A launch that renders spheres takes the split
+ * launch -- the pixels whose primary ray hits nothing go to the sky pass, the others to rtc_render_chain, which tests the
+ * spheres first and lets a triangle win only when strictly closer -- when all of these hold: at most 32 spheres; the
+ * scene's gate allows it or the launch carries RTC_F_SPLIT_SPHERES; none of RTC_F_NO_COOP, RTC_F_NO_REORDER,
+ * RTC_F_NO_TILE_CULL, RTC_F_DEBUG_BOUNCES.  Every other sphere launch runs the one-lane-per-pixel kernel.  The gate is
+ * decided at upload: rtc_bounce_hit_share_all is rtc_bounce_hit_share's probe with ray origins on triangles and spheres
+ * (area-weighted, a sphere's area 4 pi r^2) tested against both, and the gate allows the split launch when that share is
+ * at most 0.5 (open scenes: most bounce rays escape; a closed box traces ~10 segments per sample, which the chain kernel's
+ * windows of one lane per RNG state index would mostly discard) and the scene has at least one triangle (spheres alone
+ * render faster one lane per pixel).  Measured at 1920x1080x64: an open scene 12.9 -> 6.5 ms per frame through the split
+ * launch, the reference's default box 40.8 -> 451 ms (gated off).  rtc_scene_sphere_split returns the upload's decision,
+ * 1 or 0 (0 for a scene without spheres, without triangles or with more than 32 spheres).  The frame is the same bit for
+ * bit on either route. */
+int rtc_bounce_hit_share_all(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, float *share);
+int rtc_scene_sphere_split(const RtcDeviceScene *s);
 int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
                           const RtcRenderDesc *d, void *dColors, float *dAccum,
                           unsigned long long *dSegments, void *stream);
@@ -270,6 +291,9 @@ int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out);
 int rtc_plan_sim_launch(RtcPlanSim *sim, const RtcRenderDesc *d, unsigned long long stream, unsigned long long colors,
                         unsigned long long accum, int segments, const float cam[13], const float env[14], int *ops,
                         int maxOps, unsigned long long *footprint, int maxFootprint);
+/* The simulated scene's spheres (0 by default) and whether its upload gate would allow the split launch for them; a
+ * launch with d->trianglesOnly renders none. */
+int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
 int rtc_plan_sim_release(RtcPlanSim *sim);
 
 /* Pipelined frames on one device, driven from native code (the per-frame host cost is the launch enqueue alone).

@@ -31,6 +31,7 @@ from ._abi import (  # noqa: F401
     RTC_F_CHAIN_INLINE,
     RTC_F_OVERLAP,
     RTC_F_HOST_ROWS,
+    RTC_F_SPLIT_SPHERES,
     RTC_F_NO_REORDER,
     RTC_F_NO_TILE_CULL,
     RTC_SEGMENT_COUNTERS,
@@ -151,13 +152,16 @@ class RenderConfig:
     # frame pipelining (DeviceScene.render_rows_async): the launch does not join its sky pass into the stream;
     # the frame is complete at the scene's frame event (DeviceScene.set_frame_event); same frame
     overlap: bool = False
+    # a launch that renders spheres takes the split launch (tile cull with sphere coverage, sky pass, rtc_render_chain with
+    # spheres) whatever the scene's gate decided (DeviceScene.sphere_split; RTC_F_SPLIT_SPHERES; same frame)
+    split_spheres: bool = False
 
     def flags(self) -> int:
         return ((RTC_F_HOIST_PRIMARY if self.hoist else 0) | (RTC_F_DEBUG_BOUNCES if self.debug_bounces else 0)
                 | (0 if self.tile_cull else RTC_F_NO_TILE_CULL) | (0 if self.reorder else RTC_F_NO_REORDER)
                 | (0 if self.coop else RTC_F_NO_COOP) | (0 if self.cluster_cull else RTC_F_NO_CLUSTER_CULL)
                 | (RTC_F_CHAIN_INLINE if self.chain_inline else 0) | (RTC_F_OVERLAP if self.overlap else 0)
-                | (RTC_F_HOST_ROWS if self.host_rows else 0))
+                | (RTC_F_HOST_ROWS if self.host_rows else 0) | (RTC_F_SPLIT_SPHERES if self.split_spheres else 0))
 
     def desc(self) -> RtcRenderDesc:
         return RtcRenderDesc(self.width, self.height, self.spp, self.max_bounce, int(self.triangles_only),
@@ -246,6 +250,13 @@ class DeviceScene:
     def chain_wgs(self) -> int:
         """rtc_render_chain's workgroups per CU for whole frames, chosen at upload (rtc_scene_chain_wgs)."""
         return lib().rtc_scene_chain_wgs(self._h)
+
+    @property
+    def sphere_split(self) -> bool:
+        """Whether launches that render this scene's spheres take the split launch by default, decided at upload
+        (rtc_scene_sphere_split: at most 32 spheres, at least one triangle and a bounce-hit share, spheres included, of
+        at most 0.5)."""
+        return bool(lib().rtc_scene_sphere_split(self._h))
 
     def set_timing(self, enable: bool):
         """Record HIP events around the split launch's kernels from now on (rtc_scene_set_timing)."""
@@ -360,12 +371,17 @@ def deinterleave_async(compact_ptr: int, parts: int, rows_per_part: int, width: 
           "rtc_deinterleave_async")
 
 
-def bounce_hit_share(tris) -> float:
+def bounce_hit_share(tris, spheres=None) -> float:
     """rtc_bounce_hit_share: the share of diffuse bounce rays from the triangles that hit the scene again (host probe,
-    a scheduling hint)."""
+    a scheduling hint).  With `spheres` (rtc_bounce_hit_share_all): the rays start on the triangles and the spheres,
+    area-weighted, and are tested against both -- the value the sphere split's gate compares."""
     t, nt = _arr(tris, TRIANGLE_DT)
     out = C.c_float()
-    check(lib().rtc_bounce_hit_share(_ptr(t), nt, C.byref(out)), "rtc_bounce_hit_share")
+    if spheres is None:
+        check(lib().rtc_bounce_hit_share(_ptr(t), nt, C.byref(out)), "rtc_bounce_hit_share")
+        return out.value
+    s, ns = _arr(spheres, SPHERE_DT)
+    check(lib().rtc_bounce_hit_share_all(_ptr(t), nt, _ptr(s), ns, C.byref(out)), "rtc_bounce_hit_share_all")
     return out.value
 
 

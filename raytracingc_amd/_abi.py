@@ -101,6 +101,7 @@ RTC_F_PIPE = 0x200
 RTC_F_CHAIN_INLINE = 0x400
 RTC_F_OVERLAP = 0x800
 RTC_F_HOST_ROWS = 0x1000
+RTC_F_SPLIT_SPHERES = 0x2000  # sphere launches take the split launch whatever the scene's gate says (A/B, tests)
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007
@@ -136,7 +137,8 @@ EXPORTS = [
     "rtc_scene_set_sun", "rtc_camera_basis", "rtc_write_bmp", "rtc_quantize",
     "rtc_render", "rtc_render_multi", "rtc_last_multi_info",
     "rtc_scene_upload", "rtc_scene_release", "rtc_rows_selected", "rtc_render_rows_async", "rtc_scene_set_timing", "rtc_scene_kernel_times",
-    "rtc_bounce_hit_share", "rtc_scene_chain_wgs",
+    "rtc_bounce_hit_share", "rtc_scene_chain_wgs", "rtc_bounce_hit_share_all", "rtc_scene_sphere_split",
+    "rtc_plan_sim_set_spheres",
     "rtc_scene_set_geometry_event", "rtc_scene_set_frame_event",
     "rtc_deinterleave_async", "rtc_deinterleave_bands_async", "rtc_copy_async", "rtc_copy_d2h_dma", "rtc_copy_rows_d2h_dma", "rtc_host_register",
     "rtc_host_unregister", "rtc_plan_sim_create", "rtc_plan_sim_launch", "rtc_plan_sim_release", "rtc_frame_loop", "rtc_frame_loop_cameras", "rtc_dma_pending", "rtc_dma_debug_inflight",
@@ -192,6 +194,10 @@ def lib() -> C.CDLL:
     L.rtc_scene_kernel_times.argtypes = [vp, vp]
     L.rtc_bounce_hit_share.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.rtc_scene_chain_wgs.argtypes = [vp]
+    if hasattr(L, "rtc_scene_sphere_split"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_bounce_hit_share_all.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_float)]
+        L.rtc_scene_sphere_split.argtypes = [vp]
+        L.rtc_plan_sim_set_spheres.argtypes = [vp, ip, ip]
     L.rtc_scene_set_timing.argtypes = [vp, C.c_int]
     L.rtc_scene_set_geometry_event.argtypes = [vp, vp]
     L.rtc_scene_set_frame_event.argtypes = [vp, vp]

@@ -286,7 +286,7 @@ __host__ __device__ __forceinline__ bool env_sun_skippable(float focus, float in
  * (env_vanish_limit, on the host in double) proves sv < H.  Required: focus > 0 and finite (sunSkip), intensity > 0 and
  * finite, x a normal float in (0, 1), every colour component in [2^-60, 2^60] (no product underflows or overflows; else
  * the limit is -inf).  Skipping the powf then is the sunKnown skip of a value known to vanish (tests/test_gpu_parity.py
- * whole frames, tests/test_oracle_env.py the bound against the oracle's environment on every tested direction). */
+ * whole frames, tests/test_sun_vanish.py the bound against the oracle's environment on every tested direction). */
 __host__ __device__ inline double env_vanish_limit(float focus, float intensity, const float col[9])
 {
     if (!(focus > 0.f) || !(intensity > 0.f) || !(focus < 3.0e38f) || !(intensity < 3.0e38f))

@@ -325,7 +325,8 @@ extern "C" int rtc_render_multi(const Triangle *tris, int triCount, const Sphere
         int rows = 0;
     };
     std::vector<Part> parts(G);
-    const float share = rtc_upload_hit_share(tris, triCount); /* the scheduling hint, estimated once for every device */
+    const float share = rtc_upload_hit_share(tris, triCount); /* the scheduling hints, estimated once for every device */
+    const float shareAll = rtc_upload_hit_share_all(tris, triCount, spheres, sphereCount, share);
     Events evs;
     struct PartsGuard {
         std::vector<Part> &p;
@@ -345,7 +346,7 @@ extern "C" int rtc_render_multi(const Triangle *tris, int triCount, const Sphere
         RtcDeviceGuard dg(g);
         const RtcRenderDesc dg_desc = part_desc(d, g, G);
         p.rows = rtc_rows_selected(&dg_desc);
-        if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, &p.s))
+        if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, shareAll, &p.s))
             return rc;
         HIP_TRY(hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking));
         HIP_TRY(p.col.alloc(partPx * 3, g));
@@ -477,7 +478,8 @@ int rtc_render_multi_host_rows(const Triangle *tris, int triCount, const Sphere 
         std::string err;
     };
     std::vector<Part> parts(G);
-    const float share = rtc_upload_hit_share(tris, triCount); /* the scheduling hint, estimated once for every device */
+    const float share = rtc_upload_hit_share(tris, triCount); /* the scheduling hints, estimated once for every device */
+    const float shareAll = rtc_upload_hit_share_all(tris, triCount, spheres, sphereCount, share);
     Events evs;
     struct PartsGuard {
         std::vector<Part> &p;
@@ -496,7 +498,7 @@ int rtc_render_multi_host_rows(const Triangle *tris, int triCount, const Sphere 
         RtcDeviceGuard dg(g);
         const RtcRenderDesc dg_desc = part_desc(d, g, G);
         p.rows = rtc_rows_selected(&dg_desc);
-        if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, &p.s))
+        if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, shareAll, &p.s))
             return rc;
         HIP_TRY(hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking));
         HIP_TRY(p.col.alloc(partPx * 3 + 16, g));

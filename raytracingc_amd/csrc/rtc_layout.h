@@ -130,6 +130,8 @@ struct RtcDeviceScene {
     int *geoCounts;
     double hitShare;  /* bounce_hit_share at upload */
     int chainWgsFull; /* rtc_render_chain workgroups per CU for whole frames */
+    double hitShareAll;   /* the same probe with the spheres as origins and targets too (== hitShare without spheres) */
+    bool sphereSplitGate; /* launches with spheres may take the split launch (rtcplan::sphere_split's gate) */
     /* every ordering decision's state: slots, pending sky passes, counter sets, prep records (rtc_plan.h) */
     rtcplan::State plan;
     /* streams: overlapped launches prepare, cull and run their geometry kernel on `cst` or `cst2` (high priority, by

@@ -37,6 +37,12 @@ uint64_t stream_id(int st, uint64_t caller)
 }
 } // namespace
 
+bool sphere_split(int sphereCount, bool gateAllows, int flags)
+{
+    return sphereCount > 0 && sphereCount <= kSplitSpheresMax && (gateAllows || (flags & RTC_F_SPLIT_SPHERES)) &&
+           !(flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER | RTC_F_NO_TILE_CULL | RTC_F_DEBUG_BOUNCES));
+}
+
 void plan_launch(const State &s, const Request &r, Plan &p)
 {
     memset(&p, 0, sizeof p);
@@ -53,8 +59,10 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     p.debug = (r.flags & RTC_F_DEBUG_BOUNCES) != 0;
     /* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB) */
     p.cull = !(r.flags & RTC_F_NO_TILE_CULL) && r.maskWords <= 6144;
-    /* the split launch (rtc_render_chain + the sky pass): every triangle-only scene */
-    p.fused = p.cull && !p.debug && r.sphereCount == 0 && !(r.flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER));
+    /* the split launch (rtc_render_chain + the sky pass): every triangle-only scene, and the sphere scenes sphere_split
+     * admits */
+    p.fused = p.cull && !p.debug && (r.sphereCount == 0 || r.sphereSplit) &&
+              !(r.flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER));
     p.chain = p.fused;
     p.gridX = (unsigned)((r.width + 15) / 16);
     p.gridY = (unsigned)((r.rows + 15) / 16);
@@ -357,6 +365,7 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
 struct RtcPlanSim {
     rtcplan::State st;
     int triPadded, maskWords, legacy;
+    int sphereCount, sphereGate; /* rtc_plan_sim_set_spheres (0 spheres by default) */
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -369,6 +378,15 @@ extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSi
     s->maskWords = (s->triPadded + 63) / 64;
     s->legacy = legacySlotLayout;
     *out = s;
+    return 0;
+}
+
+extern "C" int rtc_plan_sim_set_spheres(RtcPlanSim *s, int sphereCount, int gateAllows)
+{
+    if (!s || sphereCount < 0)
+        return RTC_EINVAL;
+    s->sphereCount = sphereCount;
+    s->sphereGate = gateAllows != 0;
     return 0;
 }
 
@@ -391,7 +409,8 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
     r.rows = rtc_rows_selected(d);
     r.rowStride = d->rowStride;
     r.spp = d->spp;
-    r.sphereCount = 0;
+    r.sphereCount = d->trianglesOnly ? 0 : s->sphereCount;
+    r.sphereSplit = rtcplan::sphere_split(r.sphereCount, s->sphereGate != 0, d->flags);
     r.triPadded = s->triPadded;
     r.maskWords = s->maskWords;
     r.segments = segments != 0;

@@ -24,6 +24,13 @@ constexpr size_t kInlineSumPixels = 600000; /* small shares, and the alternating
 constexpr size_t kSuperCullPixels = 400000; /* launches of more pixels run rtc_super_cull */
 constexpr size_t kSampleBufBudget = (size_t)2 << 30;
 constexpr size_t kSampleSlotBytes = 12;
+/* Sphere scenes through the split launch: at most kSplitSpheresMax spheres (the per-lane sphere loop of
+ * more is the one-lane-per-pixel kernel's own work, and the cull's per-pixel sphere tests would dominate), and only scenes
+ * whose bounce rays mostly escape -- the upload's probe hitShareAll at most kSplitMaxHitShare (a closed scene traces ~10
+ * segments per sample, and a chain window spends one lane per state index: nine lanes in ten would be discarded).
+ * kSplitMaxHitShare: see DESIGN §3.7 for the scenes it separates. */
+constexpr int kSplitSpheresMax = 32;
+constexpr double kSplitMaxHitShare = 0.5;
 
 /* streams of a plan: the caller's, the scene's two cull streams and its side stream */
 enum Stream : int { kStCaller = 0, kStCull0 = 1, kStCull1 = 2, kStSide = 3, kStreams = 4 };
@@ -84,6 +91,7 @@ struct Request {
     int width, rows, rowStride;
     int spp;
     int sphereCount; /* spheres the launch renders (0 with trianglesOnly) */
+    bool sphereSplit; /* a launch with spheres may take the split launch (sphere_split) */
     int triPadded, maskWords;
     bool segments;   /* the caller asked for segment counters (a joined, counting launch) */
     Key key;
@@ -123,6 +131,10 @@ struct Plan {
     Op ops[40];
     State after;         /* the ordering state once every operation is enqueued */
 };
+
+/* Whether a launch that renders sphereCount > 0 spheres may take the split launch: few enough spheres, the scene's gate
+ * (or RTC_F_SPLIT_SPHERES), and none of the flags that select the one-lane-per-pixel kernel */
+bool sphere_split(int sphereCount, bool gateAllows, int flags);
 
 /* Plan one launch; `s` is not modified (the executor adopts plan.after once every operation is enqueued). */
 void plan_launch(const State &s, const Request &r, Plan &p);

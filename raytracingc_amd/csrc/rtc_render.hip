@@ -873,9 +873,18 @@ __global__ __launch_bounds__(64) void rtc_super_cull(RenderParams P, unsigned lo
  * workgroups without a survivor (most of a sky-heavy frame), a per-tile pixel count or the workgroup weights (only
  * rtc_order_blocks reads those, before the one-lane-per-pixel kernel): WRITE_SIZE per 1080p launch 2.13 -> 0.88 MB, the
  * frame unchanged (profiles/r06_j_pmc_writes.log, r06_i_ab_cull_trim_xcd_runs_prefetch.log). */
-__global__ __launch_bounds__(kBlock) void rtc_tile_cull(RenderParams P, unsigned long long *__restrict__ mask,
-                                                       unsigned *__restrict__ weight,
-                                                       unsigned long long *__restrict__ pixMask)
+/* SPH (the sphere split): the launch renders P.sphereCount > 0 spheres through the split launch, so a pixel
+ * is a geometry pixel also when its primary ray records a sphere hit -- the reference's own predicate on the pixel's
+ * primary_dir: raySphere hits with dst < 999999 (calculateRayCollision's initial closest distance, raytracing.c:218-228)
+ * for some sphere.  It is exact, not a bound: the sky pass then renders exactly the pixels whose primary ray hits
+ * neither a sphere nor a triangle candidate.  A NaN direction (height-1 frames) gives dst = NaN, and NaN < 999999 is
+ * false, as in the reference.  The workgroup and superblock shortcuts that skip triangle-free pixels do not skip a
+ * workgroup with a sphere pixel; the tile's triangle mask words are the triangle-only launch's.  A template, not a
+ * uniform branch: rtc_tile_cull (without spheres) is the kernel every other launch ran before, instruction for
+ * instruction. */
+template <bool SPH>
+__device__ __forceinline__ void tile_cull_body(const RenderParams &P, unsigned long long *__restrict__ mask,
+                                               unsigned *__restrict__ weight, unsigned long long *__restrict__ pixMask)
 {
     const bool split = P.geoList != nullptr; /* (uniform) */
     if (KARG(cullPrio)) /* (RenderParams::cullPrio) */
@@ -915,6 +924,25 @@ __global__ __launch_bounds__(kBlock) void rtc_tile_cull(RenderParams P, unsigned
             }
         }
     }
+    bool sphHit = false; /* SPH: this lane's primary ray records a sphere hit */
+    if (SPH) {
+        const PixelRay ps = pixel_ray(P, bx, by);
+        if (ps.valid) {
+            for (int i = 0; i < P.sphereCount; ++i) { /* wave-uniform: the records are scalar loads */
+                const DevSphere sp = KLOAD(P.spheres, i);
+                float d;
+                if (ray_sphere(P.origin, ps.dir, V3{sp.cx, sp.cy, sp.cz}, sp.radius, d) && d < 999999.f)
+                    sphHit = true;
+            }
+        }
+        /* a superblock that keeps no triangle ran no level-1 pass: the block's survivors are none (level 2 reads them
+         * when a sphere pixel keeps the workgroup) */
+        if (!supAny)
+            for (int w = threadIdx.x; w < P.maskWords; w += kBlock)
+                sBlockCand[w] = 0ull;
+        if (__ballot(sphHit) != 0ull && lane == 0)
+            wgAny = 1; /* (the same benign race) */
+    }
     __syncthreads();
     CSTAMP(c1);
     const int tile = wave_tile(bx, by);
@@ -934,7 +962,7 @@ __global__ __launch_bounds__(kBlock) void rtc_tile_cull(RenderParams P, unsigned
     unsigned long long dPre = 0, dLoop = 0, dCand = 0;
 #endif
     const PixelRay px = pixel_ray(P, bx, by);
-    bool anyCand = false;
+    bool anyCand = SPH && sphHit;
     /* level 2: the tile's own prefilter on the block's survivors, then the per-pixel filter */
     const TileCone K = tile_cone(P, tile % (int)(gridDim.x * 2), tile / (int)(gridDim.x * 2));
     for (int w = 0; w < P.maskWords; ++w) {
@@ -1000,6 +1028,23 @@ __global__ __launch_bounds__(kBlock) void rtc_tile_cull(RenderParams P, unsigned
 #ifdef RTC_DIAG
     CREC(blockIdx.y * gridDim.x + blockIdx.x, c0, c1, c6, 1, dPre, dLoop, dCand);
 #endif
+}
+
+/* The kernel of every launch but the sphere split's; rtc_tile_cull_sph<true> is the sphere split's (the same body with SPH).
+ * That one is a template only so that its code is emitted after every other kernel of the library: the kernels of
+ * launches without spheres keep the addresses, relative to one another, that they had before it existed. */
+__global__ __launch_bounds__(kBlock) void rtc_tile_cull(RenderParams P, unsigned long long *__restrict__ mask,
+                                                       unsigned *__restrict__ weight,
+                                                       unsigned long long *__restrict__ pixMask)
+{
+    tile_cull_body<false>(P, mask, weight, pixMask);
+}
+template <bool SPH>
+__global__ __launch_bounds__(kBlock) void rtc_tile_cull_sph(RenderParams P, unsigned long long *__restrict__ mask,
+                                                           unsigned *__restrict__ weight,
+                                                           unsigned long long *__restrict__ pixMask)
+{
+    tile_cull_body<SPH>(P, mask, weight, pixMask);
 }
 
 /* Launch order of the render kernel's workgroups: a counting sort of the weights, heaviest bucket first
@@ -1903,6 +1948,27 @@ __device__ __forceinline__ void closest_primary_listed_lds(const RenderParams &P
     }
 }
 
+/* rtc_render_chain<SPHERES>: calculateRayCollision's sphere loop (raytracing.c:219-228) before the triangles
+ * -- the spheres in index order, each replacing the closest so far only when strictly closer, from 999999; the exact
+ * ray_sphere.  The loop is wave-uniform and the records are scalar loads.  A sphere's index in a Closest is
+ * kChainSphereBase + i (triangle indices stay their own: the tile cull admits fewer than 2^19 triangles), so the triangle
+ * traces that follow -- which replace only when strictly closer, or are compared afterwards -- keep the reference's order:
+ * spheres first, then triangles by index. */
+constexpr int kChainSphereBase = 1 << 30;
+__device__ __forceinline__ void closest_spheres(const RenderParams &P, V3 pos, V3 dir, Closest &c)
+{
+    const DevSphere *const spheres = KARG(spheres);
+    const int n = KARG(sphereCount);
+    for (int i = 0; i < n; ++i) {
+        const DevSphere sp = KLOAD(spheres, i);
+        float d;
+        if (ray_sphere(pos, dir, V3{sp.cx, sp.cy, sp.cz}, sp.radius, d) && d < c.dst) {
+            c.dst = d;
+            c.idx = kChainSphereBase + i;
+        }
+    }
+}
+
 /* rtc_render_chain's dynamic LDS: the clustered records (MULTI: none), then, when the block's budget allows
  * (P.chainPrimF), the primary filter records.  (Staging the primary exact records and the shading records as well
  * measured no faster.) */
@@ -1937,8 +2003,12 @@ __device__ __forceinline__ ChainStage chain_stage(const RenderParams &P, unsigne
  * (without the slot code: frame -0.8 %, chain -1.4 %, 1/8 share -2 %, profiles/r06_w_ab_defer_specialisation.log).
  * Counting launches always take GENERAL.  HITS: the fast instantiation of scenes whose bounces often hit again (the
  * upload's bounce_hit_share above kWgsHitShare, e.g. C3 fsuzane), with the later bounces' one-pass cull and pair build
- * (chain_trace_pairs); the other scenes' instantiation does not carry that code. */
-template <bool MULTI, bool COUNT, bool HITS, bool GENERAL>
+ * (chain_trace_pairs); the other scenes' instantiation does not carry that code.  SPHERES (GENERAL launches only): the
+ * launch renders P.sphereCount > 0 spheres (closest_spheres before the primary trace and before every bounce trace, the
+ * sphere's normal and material at a sphere hit); a hit draws the same 7 values on a sphere as on a triangle
+ * (RandomDiretion and the roulette), so the state-indexed chain, the draw table and the walk are unchanged.  Without it
+ * none of that code is in the kernel. */
+template <bool MULTI, bool COUNT, bool HITS, bool GENERAL, bool SPHERES = false>
 __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC_CHAIN_WAVES))) void rtc_render_chain(
     RenderParams P)
 {
@@ -2088,6 +2158,8 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
         const bool deferred = GENERAL && it < P.sampleCap; /* wave-uniform */
         Closest prim{999999.f, -1};
         if (GENERAL && P.hoist && P.spp > 0 && P.maxBounce > 0) {
+            if constexpr (SPHERES)
+                closest_spheres(P, KARG(origin), pdir, prim);
             closest_primary_listed_lds(P, pdir, prim, mask, m0, m1, sPF, pfStaged);
             if (counting && lane == 0) {
                 segTraced++;
@@ -2132,6 +2204,8 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                         if (GENERAL && P.hoist) {
                             c = prim;
                         } else {
+                            if constexpr (SPHERES)
+                                closest_spheres(P, pos, dir, c);
                             closest_primary_listed_lds(P, dir, c, mask, m0, m1, sPF, pfStaged);
                             if (counting)
                                 tests += L;
@@ -2144,7 +2218,21 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                         maskNext = true;
                     }
                     unsigned t = 0;
-                    c = chain_trace_pairs<MULTI, COUNT, HITS>(P, alive, bounce1, pos, dir, sRec, W, lane, t, sCl);
+                    if constexpr (SPHERES) {
+                        /* the spheres first, every lane (a retired lane's result is not used); then the wave's triangle
+                         * trace, whose hit replaces the sphere's only when strictly closer (raytracing.c:231).  A scene
+                         * without triangles (no cluster) has no triangle trace */
+                        Closest cs{999999.f, -1};
+                        closest_spheres(P, pos, dir, cs);
+                        if (P.clusterCount > 0) /* (uniform) */
+                            c = chain_trace_pairs<MULTI, COUNT, HITS>(P, alive, bounce1, pos, dir, sRec, W, lane, t, sCl);
+                        else
+                            wave_lds_sync(); /* (the draw table's entries, as chain_trace_pairs' syncs order them) */
+                        if (!(c.idx >= 0 && c.dst < cs.dst))
+                            c = cs;
+                    } else {
+                        c = chain_trace_pairs<MULTI, COUNT, HITS>(P, alive, bounce1, pos, dir, sRec, W, lane, t, sCl);
+                    }
                     if (counting && alive) {
                         tests += t;
                         clTests += (unsigned)P.clusterCount;
@@ -2165,17 +2253,46 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                         hits++;
                         /* calcColor hit branch, raytracing.c:272-287 */
                         const V3 hitPoint = add(pos, mul(dir, c.dst)); /* raytracing.c:238 */
-                        DevTri T;
-                        DevMat M;
-                        if (first) { /* the pixel's primary hit: the same triangle in every lane */
-                            const int u = __builtin_amdgcn_readfirstlane(c.idx);
-                            T = KLOAD(KARG(tris), u);
-                            M = KLOAD(KARG(mats), u);
-                        } else {
-                            T = P.tris[c.idx]; /* (kernel-argument pointers: global loads, not flat) */
-                            M = P.mats[c.idx];
+                        V3 normal{0.f, 0.f, 0.f}, color{0.f, 0.f, 0.f};
+                        float emission = 0.f, smoothness = 0.f;
+                        bool onSphere = false;
+                        if constexpr (SPHERES) {
+                            /* a sphere hit: normal = normalized(hitPoint - centre) (raytracing.c:182), the sphere's
+                             * material; at the primary hit the winner is the same in every lane (scalar loads) */
+                            DevSphere sp;
+                            if (first) {
+                                const int u = __builtin_amdgcn_readfirstlane(c.idx);
+                                onSphere = u >= kChainSphereBase; /* (uniform) */
+                                if (onSphere)
+                                    sp = KLOAD(KARG(spheres), u - kChainSphereBase);
+                            } else {
+                                onSphere = c.idx >= kChainSphereBase;
+                                if (onSphere)
+                                    sp = P.spheres[c.idx - kChainSphereBase];
+                            }
+                            if (onSphere) {
+                                normal = normalized(sub(hitPoint, V3{sp.cx, sp.cy, sp.cz}));
+                                color = V3{sp.r, sp.g, sp.b};
+                                emission = sp.emission;
+                                smoothness = sp.smoothness;
+                            }
                         }
-                        const V3 normal{T.nx, T.ny, T.nz}, color{M.r, M.g, M.b};
+                        if (!onSphere) {
+                            DevTri T;
+                            DevMat M;
+                            if (first) { /* the pixel's primary hit: the same triangle in every lane */
+                                const int u = __builtin_amdgcn_readfirstlane(c.idx);
+                                T = KLOAD(KARG(tris), u);
+                                M = KLOAD(KARG(mats), u);
+                            } else {
+                                T = P.tris[c.idx]; /* (kernel-argument pointers: global loads, not flat) */
+                                M = P.mats[c.idx];
+                            }
+                            normal = V3{T.nx, T.ny, T.nz};
+                            color = V3{M.r, M.g, M.b};
+                            emission = M.emission;
+                            smoothness = M.smoothness;
+                        }
                         /* the hit draws (see ChainWaveLds::draw): the primary hit computes the lane's own and enters
                          * them in the table (every active lane hits there: one primary ray per wave); a later hit
                          * reads entry lane + iter, or computes it when that is past the window's active lanes */
@@ -2191,9 +2308,9 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                         }
                         const V3 diffuseDir = normalized(add(normal, V3{D.x, D.y, D.z}));
                         const V3 specularDir = reflect(dir, normal);
-                        dir = lerp(diffuseDir, specularDir, M.smoothness);
+                        dir = lerp(diffuseDir, specularDir, smoothness);
                         pos = hitPoint;
-                        const V3 emitted = mul(color, M.emission);
+                        const V3 emitted = mul(color, emission);
                         light = add(light, mulv(emitted, rayColor));
                         rayColor = mulv(rayColor, color);
                         const float p = fmax_ref(fmax_ref(rayColor.x, rayColor.y), rayColor.z);
@@ -2441,6 +2558,14 @@ static EnvParams env_of(const Scene &s)
 }
 
 
+/* The sphere split's two kernels (rtc_tile_cull_sph<true>, rtc_render_chain<..., SPHERES>), launched from the end of
+ * this file: the instantiations are emitted in the order of their first use, so these come after every kernel of the
+ * launches without spheres, whose code then lies as it did before the sphere split existed */
+static hipError_t launch_sphere_cull(dim3 grid, size_t sh, hipStream_t st, hipEvent_t stop, const RenderParams &P,
+                                     unsigned long long *mask, unsigned *weight, unsigned long long *pixMask);
+static hipError_t launch_sphere_chain(bool multi, bool count, dim3 grid, dim3 block, size_t sh, hipStream_t st,
+                                      hipEvent_t stop, const RenderParams &P);
+
 #ifdef RTC_AB_NO_SLOTS
 constexpr bool kAbNoSlots = true; /* timing experiment only (RTC_EXPERIMENT): deferred samples neither stored nor summed */
 #else
@@ -2527,6 +2652,7 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
     rq.rowStride = d->rowStride;
     rq.spp = d->spp;
     rq.sphereCount = P.sphereCount;
+    rq.sphereSplit = rtcplan::sphere_split(P.sphereCount, s->sphereSplitGate, d->flags);
     rq.triPadded = s->triPadded;
     rq.maskWords = s->maskWords;
     rq.segments = dSegments != nullptr;
@@ -2650,8 +2776,12 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
             HIP_TRY(hipGetLastError());
             break;
         case rtcplan::kKTileCull:
-            HIP_TRY(launch_stop(rtc_tile_cull, grid, dim3(kBlock), (size_t)s->maskWords * sizeof(unsigned long long), os, ev,
-                                P, mask, weight, pixMask));
+            if (pl.chain && P.sphereCount > 0) /* the sphere split: sphere pixels are geometry pixels */
+                HIP_TRY(launch_sphere_cull(grid, (size_t)s->maskWords * sizeof(unsigned long long), os, ev, P, mask, weight,
+                                           pixMask));
+            else
+                HIP_TRY(launch_stop(rtc_tile_cull, grid, dim3(kBlock), (size_t)s->maskWords * sizeof(unsigned long long), os,
+                                    ev, P, mask, weight, pixMask));
             break;
         case rtcplan::kKSky: {
             if (s->timing)
@@ -2678,7 +2808,9 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
             const dim3 cg((unsigned)(wgsPerCu * s->cuCount)), cb(kChainBlock);
             const bool defer = P.sampleCap > 0 || P.hoist || !P.chainPrimF; /* (GENERAL) */
             const bool hits = s->chainWgsFull == RTC_CHAIN_WGS_HIT && RTC_CHAIN_WGS_HIT != RTC_CHAIN_WGS_FULL;
-            if (s->chunkCount > 1 && dSegments)
+            if (P.sphereCount > 0) /* the sphere split: GENERAL, for MULTI x COUNT */
+                HIP_TRY(launch_sphere_chain(s->chunkCount > 1, dSegments != nullptr, cg, cb, chainDyn, os, ev, P));
+            else if (s->chunkCount > 1 && dSegments)
                 HIP_TRY(launch_stop(rtc_render_chain<true, true, false, true>, cg, cb, chainDyn, os, ev, P));
             else if (s->chunkCount > 1) /* (multi-chunk scenes never stage the primary records: GENERAL) */
                 HIP_TRY(launch_stop(rtc_render_chain<true, false, false, true>, cg, cb, chainDyn, os, ev, P));
@@ -2816,4 +2948,23 @@ extern "C" int rtc_copy_async(void *dst, const void *src, size_t bytes, int bloc
                        (const unsigned char *)src, (unsigned char *)dst, bytes);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+/* ---- the sphere split's kernels (see launch_sphere_cull's declaration) ------------------------------- */
+static hipError_t launch_sphere_cull(dim3 grid, size_t sh, hipStream_t st, hipEvent_t stop, const RenderParams &P,
+                                     unsigned long long *mask, unsigned *weight, unsigned long long *pixMask)
+{
+    return launch_stop(rtc_tile_cull_sph<true>, grid, dim3(kBlock), sh, st, stop, P, mask, weight, pixMask);
+}
+
+static hipError_t launch_sphere_chain(bool multi, bool count, dim3 grid, dim3 block, size_t sh, hipStream_t st,
+                                      hipEvent_t stop, const RenderParams &P)
+{
+    if (multi && count)
+        return launch_stop(rtc_render_chain<true, true, false, true, true>, grid, block, sh, st, stop, P);
+    if (multi)
+        return launch_stop(rtc_render_chain<true, false, false, true, true>, grid, block, sh, st, stop, P);
+    if (count)
+        return launch_stop(rtc_render_chain<false, true, false, true, true>, grid, block, sh, st, stop, P);
+    return launch_stop(rtc_render_chain<false, false, false, true, true>, grid, block, sh, st, stop, P);
 }

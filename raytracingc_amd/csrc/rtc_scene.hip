@@ -19,24 +19,39 @@
  * area-weighted random points of the triangles, in directions normal + a random unit vector (the reference's diffuse
  * lobe, raytracing.c:276-279, without the specular part), tested against every triangle in double precision with the
  * reference's backface rule.  Only a scheduling hint (rtc_render_chain's workgroups per CU): it never changes a
- * frame.  Measured shares: fsuzane 0.21, rsuzanne 0.11, ultracomplex 0.019, complex 0.016, cube 0. */
-static double bounce_hit_share(const Triangle *t, int n)
+ * frame.  Measured shares: fsuzane 0.21, rsuzanne 0.11, ultracomplex 0.019, complex 0.016, cube 0.
+ * With spheres (ns > 0: hitShareAll, the sphere split's gate, rtcplan::kSplitMaxHitShare) the origins are drawn from the
+ * triangles and the spheres together, area-weighted (a sphere's area is 4 pi r^2; a sphere's bounce rays leave along its
+ * outward normal, raytracing.c:182), and every ray is tested against the spheres too (raySphere, raytracing.c:162-184, in
+ * double).  Without spheres the draws and tests are the triangle-only probe's, value for value. */
+static double bounce_hit_share(const Triangle *t, int n, const Sphere *sp = nullptr, int ns = 0)
 {
-    if (n <= 0)
+    if (n < 0)
+        n = 0;
+    if (ns < 0 || !sp)
+        ns = 0;
+    if (n + ns <= 0)
         return 0.0;
     struct D3 { double x, y, z; };
     const auto sub3 = [](D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; };
     const auto dot3 = [](D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
     const auto cross3 = [](D3 a, D3 b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
     const auto d3 = [](vec3 v) { return D3{v.x, v.y, v.z}; };
-    std::vector<double> cdf((size_t)n);
+    const int prims = n + ns;
+    std::vector<double> cdf((size_t)prims);
     double total = 0.0;
     for (int i = 0; i < n; ++i) {
         const D3 c = cross3(sub3(d3(t[i].posB), d3(t[i].posA)), sub3(d3(t[i].posC), d3(t[i].posA)));
         total += 0.5 * std::sqrt(dot3(c, c));
         cdf[(size_t)i] = total;
     }
-    if (!(total > 0.0))
+    for (int i = 0; i < ns; ++i) {
+        const double r = sp[i].r;
+        if (r == r && std::isfinite(r))
+            total += 4.0 * 3.14159265358979323846 * r * r;
+        cdf[(size_t)(n + i)] = total;
+    }
+    if (!(total > 0.0) || !std::isfinite(total))
         return 0.0;
     unsigned long long st = 0x9E3779B97F4A7C15ull;
     const auto uni = [&]() { /* xorshift64*, [0, 1) */
@@ -45,39 +60,63 @@ static double bounce_hit_share(const Triangle *t, int n)
         st ^= st >> 27;
         return (double)((st * 0x2545F4914F6CDD1Dull) >> 11) * (1.0 / 9007199254740992.0);
     };
-    /* rays x n ray-triangle tests: ~4 M up to 62.5 k triangles, 64 n beyond (a 1 M-triangle scene: 64 M tests, a few
-     * tenths of a second of upload; scenes past the tile cull's limit skip the probe, rtc_scene_upload) */
-    const int rays = (int)std::min<long long>(2048, std::max<long long>(64, 4000000LL / n));
-    int hits = 0;
-    for (int r = 0; r < rays; ++r) {
-        const int i = (int)(std::lower_bound(cdf.begin(), cdf.end(), uni() * total) - cdf.begin());
-        const Triangle &T = t[std::min(i, n - 1)];
-        double u = uni(), w = uni();
-        if (u + w > 1.0) {
-            u = 1.0 - u;
-            w = 1.0 - w;
-        }
-        const D3 A = d3(T.posA), AB = sub3(d3(T.posB), A), AC = sub3(d3(T.posC), A);
-        D3 nn = d3(T.normal);
-        const double nl = std::sqrt(dot3(nn, nn));
-        if (!(nl > 0.0))
-            continue;
-        nn = D3{nn.x / nl, nn.y / nl, nn.z / nl};
-        D3 q{0, 0, 0};
+    const auto unit = [&](D3 &q) { /* a uniform random unit vector (rejection from the cube) */
         double ql = 0.0;
-        do { /* a uniform random unit vector (rejection from the cube) */
+        do {
             q = D3{2 * uni() - 1, 2 * uni() - 1, 2 * uni() - 1};
             ql = dot3(q, q);
         } while (ql > 1.0 || ql < 1e-12);
         ql = std::sqrt(ql);
-        D3 dir{nn.x + q.x / ql, nn.y + q.y / ql, nn.z + q.z / ql};
+        q = D3{q.x / ql, q.y / ql, q.z / ql};
+    };
+    /* rays x n ray-triangle tests: ~4 M up to 62.5 k triangles, 64 n beyond (a 1 M-triangle scene: 64 M tests, a few
+     * tenths of a second of upload; scenes past the tile cull's limit skip the probe, rtc_scene_upload) */
+    const int rays = (int)std::min<long long>(2048, std::max<long long>(64, 4000000LL / prims));
+    int hits = 0;
+    for (int r = 0; r < rays; ++r) {
+        const int i = std::min((int)(std::lower_bound(cdf.begin(), cdf.end(), uni() * total) - cdf.begin()), prims - 1);
+        D3 nn{0, 0, 0}, O{0, 0, 0}; /* the origin's unit normal, and the point of the surface */
+        if (i < n) {
+            const Triangle &T = t[i];
+            double u = uni(), w = uni();
+            if (u + w > 1.0) {
+                u = 1.0 - u;
+                w = 1.0 - w;
+            }
+            const D3 A = d3(T.posA), AB = sub3(d3(T.posB), A), AC = sub3(d3(T.posC), A);
+            nn = d3(T.normal);
+            const double nl = std::sqrt(dot3(nn, nn));
+            if (!(nl > 0.0))
+                continue;
+            nn = D3{nn.x / nl, nn.y / nl, nn.z / nl};
+            O = D3{A.x + u * AB.x + w * AC.x, A.y + u * AB.y + w * AC.y, A.z + u * AB.z + w * AC.z};
+        } else { /* a uniform point of the sphere; its normal points outwards */
+            const Sphere &S = sp[i - n];
+            unit(nn);
+            O = D3{S.pos.x + S.r * nn.x, S.pos.y + S.r * nn.y, S.pos.z + S.r * nn.z};
+        }
+        D3 q{0, 0, 0};
+        unit(q);
+        D3 dir{nn.x + q.x, nn.y + q.y, nn.z + q.z};
         const double dl = std::sqrt(dot3(dir, dir));
         if (!(dl > 1e-9))
             continue;
         dir = D3{dir.x / dl, dir.y / dl, dir.z / dl};
-        const D3 P{A.x + u * AB.x + w * AC.x + 1e-4 * nn.x, A.y + u * AB.y + w * AC.y + 1e-4 * nn.y,
-                   A.z + u * AB.z + w * AC.z + 1e-4 * nn.z};
-        for (int j = 0; j < n; ++j) { /* rayTriangle's tests (raytracing.c:186-214), in double */
+        const D3 P{O.x + 1e-4 * nn.x, O.y + 1e-4 * nn.y, O.z + 1e-4 * nn.z};
+        bool hit = false;
+        for (int j = 0; j < ns && !hit; ++j) { /* raySphere's tests (raytracing.c:162-184), in double */
+            const D3 off = sub3(P, d3(sp[j].pos));
+            const double b = dot3(off, dir), cc = dot3(off, off) - (double)sp[j].r * (double)sp[j].r;
+            double delta = b * b - cc;
+            if (!(delta >= 0.0))
+                continue;
+            delta = std::sqrt(delta);
+            double dst = -b - delta;
+            if (dst < 1e-3)
+                dst = -b + delta;
+            hit = dst >= 1e-3;
+        }
+        for (int j = 0; j < n && !hit; ++j) { /* rayTriangle's tests (raytracing.c:186-214), in double */
             if (dot3(dir, d3(t[j].normal)) >= 0.0)
                 continue;
             const D3 a = d3(t[j].posA), ab = sub3(d3(t[j].posB), a), ac = sub3(d3(t[j].posC), a);
@@ -93,9 +132,9 @@ static double bounce_hit_share(const Triangle *t, int n)
             const double vv = dot3(dir, qv) / det;
             if (vv < 0.0 || uu + vv > 1.0 || dot3(ac, qv) / det < 1e-3)
                 continue;
-            ++hits;
-            break;
+            hit = true;
         }
+        hits += hit ? 1 : 0;
     }
     return (double)hits / (double)rays;
 }
@@ -322,6 +361,22 @@ extern "C" int rtc_bounce_hit_share(const Triangle *tris, int triCount, float *s
     return 0;
 }
 
+extern "C" int rtc_bounce_hit_share_all(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
+                                        float *share)
+{
+    if (!share || triCount < 0 || sphereCount < 0 || (triCount > 0 && !tris) || (sphereCount > 0 && !spheres))
+        return rtc_fail(RTC_EINVAL, "rtc_bounce_hit_share_all: bad argument");
+    *share = (float)bounce_hit_share(tris, triCount, spheres, sphereCount);
+    return 0;
+}
+
+extern "C" int rtc_scene_sphere_split(const RtcDeviceScene *s)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_sphere_split: null scene");
+    return s->sphereSplitGate ? 1 : 0;
+}
+
 extern "C" int rtc_scene_chain_wgs(const RtcDeviceScene *s)
 {
     if (!s)
@@ -332,7 +387,7 @@ extern "C" int rtc_scene_chain_wgs(const RtcDeviceScene *s)
 extern "C" int rtc_scene_upload(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, int device,
                                 RtcDeviceScene **out)
 {
-    return rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, device, -1.f, out);
+    return rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, device, -1.f, -1.f, out);
 }
 
 
@@ -342,8 +397,21 @@ extern "C" float rtc_upload_hit_share(const Triangle *tris, int triCount)
     return triCount > 0 && tris && maskWords <= kMaxCullMaskWords ? (float)bounce_hit_share(tris, triCount) : 0.f;
 }
 
+extern "C" float rtc_upload_hit_share_all(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
+                                          float hitShare)
+{
+    /* only launches the sphere split could take read it: without spheres it is the triangles' share, and with more
+     * spheres than the split admits (or triangles than the tile cull does) the probe is skipped */
+    const int maskWords = ((triCount + 7) / 8 * 8 + 63) / 64;
+    if (sphereCount <= 0 || !spheres)
+        return hitShare;
+    if (sphereCount > rtcplan::kSplitSpheresMax || maskWords > kMaxCullMaskWords || (triCount > 0 && !tris))
+        return 1.f;
+    return (float)bounce_hit_share(tris, triCount, spheres, sphereCount);
+}
+
 extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
-                                           int device, float hitShare, RtcDeviceScene **out)
+                                           int device, float hitShare, float hitShareAll, RtcDeviceScene **out)
 {
     if (!out || triCount < 0 || sphereCount < 0 || (triCount > 0 && !tris) || (sphereCount > 0 && !spheres))
         return rtc_fail(RTC_EINVAL, "rtc_scene_upload: bad argument");
@@ -386,6 +454,15 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
      * profiles/r05_w4_ab_chain_wgs.log) */
     s->hitShare = hitShare >= 0.f ? (double)hitShare : (double)rtc_upload_hit_share(tris, triCount);
     s->chainWgsFull = s->hitShare > kWgsHitShare ? RTC_CHAIN_WGS_HIT : RTC_CHAIN_WGS_FULL;
+    /* sphere scenes whose bounce rays mostly escape render through the split launch (rtcplan::sphere_split) */
+    s->hitShareAll = hitShareAll >= 0.f
+                         ? (double)hitShareAll
+                         : (double)rtc_upload_hit_share_all(tris, triCount, spheres, sphereCount, (float)s->hitShare);
+    /* (a scene of spheres alone stays on the pixel kernel: no threshold on the share separates it from the open scenes
+     * with triangles -- both measure 0.001 -- and without triangle work a wave per pixel loses to a lane per pixel,
+     * 3.06 vs 2.74 ms per 1080p x64 frame) */
+    s->sphereSplitGate = sphereCount > 0 && sphereCount <= rtcplan::kSplitSpheresMax && triCount > 0 &&
+                         s->hitShareAll <= rtcplan::kSplitMaxHitShare;
     hipError_t e = hipMalloc(&s->tris, dt.size() * sizeof(DevTri));
     if (e == hipSuccess)
         e = hipMalloc(&s->clTris, ct.size() * sizeof(DevTri));
