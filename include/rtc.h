@@ -294,6 +294,11 @@ int rtc_plan_sim_launch(RtcPlanSim *sim, const RtcRenderDesc *d, unsigned long l
 /* The simulated scene's spheres (0 by default) and whether its upload gate would allow the split launch for them; a
  * launch with d->trianglesOnly renders none. */
 int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
+/* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
+ * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
+ * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the
+ * number of rows (at most 10: maxRows must hold them). */
+int rtc_plan_sim_regions(const RtcPlanSim *sim, unsigned long long *rows, int maxRows);
 int rtc_plan_sim_release(RtcPlanSim *sim);
 
 /* Pipelined frames on one device, driven from native code (the per-frame host cost is the launch enqueue alone).

@@ -138,7 +138,7 @@ EXPORTS = [
     "rtc_render", "rtc_render_multi", "rtc_last_multi_info",
     "rtc_scene_upload", "rtc_scene_release", "rtc_rows_selected", "rtc_render_rows_async", "rtc_scene_set_timing", "rtc_scene_kernel_times",
     "rtc_bounce_hit_share", "rtc_scene_chain_wgs", "rtc_bounce_hit_share_all", "rtc_scene_sphere_split",
-    "rtc_plan_sim_set_spheres",
+    "rtc_plan_sim_set_spheres", "rtc_plan_sim_regions",
     "rtc_scene_set_geometry_event", "rtc_scene_set_frame_event",
     "rtc_deinterleave_async", "rtc_deinterleave_bands_async", "rtc_copy_async", "rtc_copy_d2h_dma", "rtc_copy_rows_d2h_dma", "rtc_host_register",
     "rtc_host_unregister", "rtc_plan_sim_create", "rtc_plan_sim_launch", "rtc_plan_sim_release", "rtc_frame_loop", "rtc_frame_loop_cameras", "rtc_dma_pending", "rtc_dma_debug_inflight",
@@ -214,6 +214,8 @@ def lib() -> C.CDLL:
     L.rtc_plan_sim_launch.argtypes = [vp, C.POINTER(RtcRenderDesc), C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, ip, vp,
                                       vp, vp, ip, vp, ip]
     L.rtc_plan_sim_release.argtypes = [vp]
+    if hasattr(L, "rtc_plan_sim_regions"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_plan_sim_regions.argtypes = [vp, vp, ip]
     L.rtc_dma_pending.argtypes = [vp, sz]
     L.rtc_dma_debug_inflight.argtypes = [vp, sz, ip]
     L.rtc_rows_selected.argtypes = [C.POINTER(RtcRenderDesc)]

@@ -121,9 +121,10 @@ struct RtcDeviceScene {
     DevPrimF *primF;
     DevPrimX *primX;
     size_t primStride;
-    /* per-launch scratch (rtc_tile_cull / rtc_order_blocks): kSkySlots slots of the candidate bit-sets, pixel masks,
-     * weights, dispatch order, geometry-pixel sub-lists and superblock survivors (rtcplan::Layout); grown on demand
-     * (plan.scratchCap bytes) */
+    /* per-launch scratch: kSkySlots slots, each the regions of rtcplan::Buf (candidate bit-sets, pixel masks, weights,
+     * dispatch order, geometry-pixel sub-lists, superblock survivors, the merged sky pass's items and colours) at the
+     * offsets of the planner's region table; a launch's kernels get the regions its plan binds (Plan::bound) and no
+     * other pointer into it; grown on demand (plan.scratchCap bytes) */
     unsigned char *scratch;
     /* rtc_render_chain's sub-list counters: a ring of kGeoRing sets, set q % kGeoRing for the q-th split launch;
      * each launch's tile cull zeroes the next launch's set */

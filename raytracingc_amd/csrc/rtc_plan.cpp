@@ -6,8 +6,7 @@
 
 #include <algorithm>
 #include <cstring>
-
-#include "../../include/rtc.h"
+#include <initializer_list>
 
 namespace rtcplan {
 
@@ -31,6 +30,30 @@ struct Emitter {
     void kernel(int st, int k, int stopEv = kEvNone) { op(kOpKernel, st, stopEv, k); }
 };
 
+/* The scratch slot: one row per region (Buf order), one loop for the offsets and the slot size.  An alignment is
+ * budgeted in full in the slot size, so the slot always holds the aligned offsets. */
+void layout_slot(Plan &p, size_t maskWords)
+{
+    const size_t lists = (size_t)kGeoLists * p.geoCap * 4, counters = (size_t)kGeoLists * kGeoCountStride * 4;
+    const struct { size_t used, align, padAfter; } rows[kScratchRegions] = {
+        /* kBufMask      */ {p.tiles * maskWords * 8, 1, 0},
+        /* kBufPixMask   */ {p.tiles * 8, 1, 0},
+        /* kBufWeight    */ {p.blocks * 4, 1, 0},
+        /* kBufOrder     */ {(p.blocks + 4) * 4, 1, counters}, /* historical padding: the sub-list counters' old place */
+        /* kBufGeoList   */ {lists, 1, 0},
+        /* kBufSuperMask */ {(size_t)p.superX * p.superY * maskWords * 8, 8, 0},
+        /* kBufPixItem   */ {p.tiles * 64 * 4, 256, 0},
+        /* kBufGeoColor  */ {lists, 1, p.tiles * 4},           /* historical padding: an int per tile, long unused */
+    };
+    size_t off = 0, budget = 0;
+    for (int b = 0; b < kScratchRegions; ++b) {
+        p.reg[b] = Region{align_up(off, rows[b].align), rows[b].used};
+        off = p.reg[b].offset + rows[b].used + rows[b].padAfter;
+        budget += rows[b].used + rows[b].padAfter + (rows[b].align > 1 ? rows[b].align : 0);
+    }
+    p.slotBytes = align_up(budget, 256);
+}
+
 uint64_t stream_id(int st, uint64_t caller)
 {
     return st == kStCull0 ? kIdCull0 : st == kStCull1 ? kIdCull1 : caller;
@@ -41,6 +64,33 @@ bool sphere_split(int sphereCount, bool gateAllows, int flags)
 {
     return sphereCount > 0 && sphereCount <= kSplitSpheresMax && (gateAllows || (flags & RTC_F_SPLIT_SPHERES)) &&
            !(flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER | RTC_F_NO_TILE_CULL | RTC_F_DEBUG_BOUNCES));
+}
+
+Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uint64_t stream, uint64_t colors,
+                     uint64_t accum, bool segments, const float cam[13], const float env[14])
+{
+    Request r;
+    memset(&r, 0, sizeof r); /* (the key is compared with memcmp) */
+    r.stream = stream;
+    r.flags = d.flags;
+    r.width = d.width;
+    r.rows = rows;
+    r.rowStride = d.rowStride;
+    r.spp = d.spp;
+    r.sphereCount = d.trianglesOnly ? 0 : sc.sphereCount;
+    r.sphereSplit = sphere_split(r.sphereCount, sc.splitGate, d.flags);
+    r.triPadded = sc.triPadded;
+    r.maskWords = sc.maskWords;
+    r.segments = segments;
+    r.key.colors = colors;
+    r.key.accum = accum;
+    memcpy(r.key.cam, cam, sizeof r.key.cam);
+    memcpy(r.key.env, env, sizeof r.key.env);
+    const int dims[9] = {d.width, d.height, rows, d.rowStart, d.rowStride, d.spp, d.maxBounce,
+                         (d.flags & RTC_F_HOIST_PRIMARY) ? 1 : 0, d.rowBand > 1 ? __builtin_ctz((unsigned)d.rowBand) : 0};
+    memcpy(r.key.dims, dims, sizeof dims);
+    memcpy(r.origin, cam, sizeof r.origin);
+    return r;
 }
 
 void plan_launch(const State &s, const Request &r, Plan &p)
@@ -70,8 +120,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     p.tiles = 4 * p.blocks;
     p.superX = (p.gridX + 3) / 4;
     p.superY = (p.gridY + 3) / 4;
-    const size_t maskBytes = p.tiles * (size_t)r.maskWords * 8;
-    const size_t superBytes = (size_t)p.superX * p.superY * (size_t)r.maskWords * 8;
+    p.superCull = p.cull && px > kSuperCullPixels && r.maskWords > 0;
     p.geoCap = (int)((p.tiles + kGeoLists - 1) / kGeoLists * 64); /* sub-list l: the tiles t = l mod kGeoLists */
     /* RTC_F_OVERLAP: the sky pass is not joined into the caller's stream (a launch that counts segments joins: the
      * reduction reads the sky pass's counters) */
@@ -122,26 +171,13 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     /* the scratch: kSlots slots; slot h starts at h x (the allocation's slot size), not h x this launch's size --
      * launches of different sizes are in flight together (round 5 fix; the legacy layout is a test hook) */
     if (p.cull) {
-        const size_t need = maskBytes + p.tiles * 8 + (p.blocks + p.tiles + p.blocks + 4) * 4 +
-                            ((size_t)kGeoLists * kGeoCountStride + (size_t)kGeoLists * p.geoCap) * 4 + 8 + superBytes +
-                            256 + p.tiles * 64 * 4 + (size_t)kGeoLists * p.geoCap * 4; /* + pixItem, geoColor */
-        p.slotBytes = align_up(need, 256);
+        layout_slot(p, (size_t)r.maskWords);
         p.scratchNeed = kSlots * p.slotBytes;
         p.scratchGrow = p.scratchNeed > s.scratchCap;
         if (p.scratchGrow)
             n.scratchCap = p.scratchNeed;
         const size_t slotStride = r.legacySlotLayout ? p.slotBytes : n.scratchCap / kSlots;
         p.slotOffset = (size_t)p.half * slotStride;
-        Layout &L = p.lay;
-        L.mask = 0;
-        L.pixMask = L.mask + maskBytes;
-        L.weight = L.pixMask + p.tiles * 8;
-        L.order = L.weight + p.blocks * 4;
-        L.geoList = L.order + (p.blocks + 4 + (size_t)kGeoLists * kGeoCountStride) * 4;
-        L.superMask = align_up(L.geoList + (size_t)kGeoLists * p.geoCap * 4, 8);
-        L.pixItem = align_up(L.superMask + superBytes, 256);
-        L.geoColor = L.pixItem + p.tiles * 64 * 4;
-        L.end = L.geoColor + (size_t)kGeoLists * p.geoCap * 4;
     }
     if (p.chain) {
         p.geoSet = s.geoSeq % kGeoRing;
@@ -158,6 +194,17 @@ void plan_launch(const State &s, const Request &r, Plan &p)
             p.sampleCap = (int)cap;
         }
     }
+    /* what the launch binds: the executor hands its kernels these buffers and no other, and only these have footprints */
+    const auto bind = [&p](bool on, std::initializer_list<int> bufs) { for (int b : bufs) p.bound |= (unsigned)on << b; };
+    bind(true, {kBufPrim, kBufColors});
+    bind(p.cull, {kBufMask, kBufPixMask, kBufWeight});
+    bind(p.cull && !p.fused, {kBufOrder});
+    bind(p.superCull, {kBufSuperMask});
+    bind(p.chain, {kBufGeoList, kBufGeoSet, kBufGeoSetNext});
+    bind(p.merge, {kBufPixItem, kBufGeoColor});
+    bind(p.sampleCap > 0, {kBufSamples});
+    bind(r.key.accum != 0, {kBufAccum});
+    bind(r.segments, {kBufSegSlots, kBufCallerSegments});
 
     if (p.cs != kStCaller) {
         /* the cull stream runs this launch's first kernels: after everything the caller enqueued before the launch and
@@ -190,7 +237,6 @@ void plan_launch(const State &s, const Request &r, Plan &p)
         n.prepStream[p.half] = csId;
         memcpy(n.prepOrigin[p.half], r.origin, sizeof r.origin);
     }
-    p.superCull = p.cull && px > kSuperCullPixels && r.maskWords > 0;
     if (p.superCull)
         E.kernel(p.cs, kKSuperCull);
     if (!p.cull) {
@@ -262,99 +308,56 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     E.record(kStCaller, kEvFrame);
 }
 
+namespace {
+/* Every access of every kernel: a row counts when the launch binds its buffer and its predicate holds */
+enum When : int { kAlways, kIfMerge, kIfNotMerge, kIfPrepCounts };
+struct Touch {
+    int kernel, buf, access, when;
+};
+const Touch kTouches[] = {
+    {kKPrep, kBufPrim, kWrite, kAlways},          {kKPrep, kBufGeoSet, kWrite, kIfPrepCounts},
+    {kKSuperCull, kBufPrim, kRead, kAlways},      {kKSuperCull, kBufSuperMask, kWrite, kAlways},
+    {kKTileCull, kBufPrim, kRead, kAlways},       {kKTileCull, kBufSuperMask, kRead, kAlways},
+    {kKTileCull, kBufMask, kWrite, kAlways},      {kKTileCull, kBufPixMask, kWrite, kAlways},
+    {kKTileCull, kBufWeight, kWrite, kAlways},    {kKTileCull, kBufGeoList, kWrite, kAlways},
+    {kKTileCull, kBufPixItem, kWrite, kAlways},   {kKTileCull, kBufGeoSet, kAtomic, kAlways},
+    {kKTileCull, kBufGeoSetNext, kWrite, kAlways},
+    {kKSky, kBufPixMask, kRead, kAlways},         {kKSky, kBufPixItem, kRead, kAlways},
+    {kKSky, kBufGeoColor, kRead, kAlways},        {kKSky, kBufGeoSet, kRead, kIfMerge}, /* the counts: an entry's item */
+    {kKSky, kBufColors, kKeyedWrite, kAlways},    {kKSky, kBufAccum, kKeyedWrite, kAlways},
+    {kKSky, kBufSegSlots, kAtomic, kAlways},
+    {kKChain, kBufPrim, kRead, kAlways},          {kKChain, kBufMask, kRead, kAlways},
+    {kKChain, kBufGeoList, kRead, kAlways},       {kKChain, kBufGeoSet, kRead, kAlways},
+    {kKChain, kBufSamples, kWrite, kAlways},      {kKChain, kBufGeoColor, kWrite, kAlways}, /* (merge) or else Color: */
+    {kKChain, kBufColors, kKeyedWrite, kIfNotMerge}, {kKChain, kBufAccum, kKeyedWrite, kAlways},
+    {kKChain, kBufSegSlots, kAtomic, kAlways},
+    {kKAccum, kBufGeoSet, kRead, kAlways},        {kKAccum, kBufSamples, kRead, kAlways},
+    {kKAccum, kBufColors, kKeyedWrite, kAlways},  {kKAccum, kBufAccum, kKeyedWrite, kAlways},
+    {kKOrder, kBufWeight, kRead, kAlways},        {kKOrder, kBufOrder, kWrite, kAlways},
+    {kKRender, kBufPrim, kRead, kAlways},         {kKRender, kBufMask, kRead, kAlways},
+    {kKRender, kBufOrder, kRead, kAlways},        {kKRender, kBufColors, kKeyedWrite, kAlways},
+    {kKRender, kBufAccum, kKeyedWrite, kAlways},  {kKRender, kBufSegSlots, kAtomic, kAlways},
+    {kKReduce, kBufSegSlots, kWrite, kAlways},    {kKReduce, kBufCallerSegments, kWrite, kAlways},
+};
+} // namespace
+
 int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out, int max)
 {
+    /* the resources outside the slot, in Buf order: their kind and identity, one unit each */
+    const struct { int res; unsigned long long id; } outside[kBufs - kScratchRegions] = {
+        {kResPrim, (unsigned long long)p.half}, {kResGeoSet, p.geoSet}, {kResGeoSet, p.geoSetNext}, {kResSamples, 0},
+        {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0}};
     int k = 0;
-    auto put = [&](int res, int acc, unsigned long long id, unsigned long long lo, unsigned long long hi) {
-        if (k < max)
-            out[k] = Footprint{res, acc, id, lo, hi};
+    for (const Touch &t : kTouches) {
+        const bool when = t.when == kAlways || (t.when == kIfPrepCounts ? p.prepCounts : p.merge == (t.when == kIfMerge));
+        if (t.kernel != kernel || !p.binds(t.buf) || !when)
+            continue;
+        if (k < max && t.buf < kScratchRegions)
+            out[k] = Footprint{kResScratch, t.access, 0, p.slotOffset + p.reg[t.buf].offset,
+                               p.slotOffset + p.reg[t.buf].offset + p.reg[t.buf].size};
+        else if (k < max)
+            out[k] = Footprint{outside[t.buf - kScratchRegions].res, t.access, outside[t.buf - kScratchRegions].id, 0, 1};
         ++k;
-    };
-    const unsigned long long o = p.slotOffset;
-    const Layout &L = p.lay;
-    auto scratch = [&](int acc, size_t lo, size_t hi) { put(kResScratch, acc, 0, o + lo, o + hi); };
-    const bool colorsKeyed = true;
-    auto colors = [&]() {
-        put(kResColors, colorsKeyed ? kKeyedWrite : kWrite, r.key.colors, 0, 1);
-        if (r.key.accum)
-            put(kResAccum, kKeyedWrite, r.key.accum, 0, 1);
-    };
-    switch (kernel) {
-    case kKPrep:
-        put(kResPrim, kWrite, (unsigned long long)p.half, 0, 1);
-        if (p.prepCounts)
-            put(kResGeoSet, kWrite, p.geoSet, 0, 1);
-        break;
-    case kKSuperCull:
-        put(kResPrim, kRead, (unsigned long long)p.half, 0, 1);
-        scratch(kWrite, L.superMask, L.end);
-        break;
-    case kKTileCull:
-        put(kResPrim, kRead, (unsigned long long)p.half, 0, 1);
-        if (p.superCull)
-            scratch(kRead, L.superMask, L.end);
-        scratch(kWrite, L.mask, L.order); /* mask, pixMask, weight */
-        if (p.chain) {
-            scratch(kWrite, L.geoList, L.superMask);
-            if (p.merge)
-                scratch(kWrite, L.pixItem, L.geoColor);
-            put(kResGeoSet, kAtomic, p.geoSet, 0, 1);
-            put(kResGeoSet, kWrite, p.geoSetNext, 0, 1);
-        }
-        break;
-    case kKSky:
-        scratch(kRead, L.pixMask, L.weight);
-        if (p.merge) {
-            scratch(kRead, L.pixItem, L.geoColor);
-            scratch(kRead, L.geoColor, L.end);
-            put(kResGeoSet, kRead, p.geoSet, 0, 1); /* the counts: an entry's item */
-        }
-        colors();
-        if (r.segments)
-            put(kResSegSlots, kAtomic, 0, 0, 1);
-        break;
-    case kKChain:
-        put(kResPrim, kRead, (unsigned long long)p.half, 0, 1);
-        scratch(kRead, L.mask, L.pixMask);
-        scratch(kRead, L.geoList, L.superMask);
-        put(kResGeoSet, kRead, p.geoSet, 0, 1);
-        if (p.sampleCap > 0)
-            put(kResSamples, kWrite, 0, 0, 1);
-        if (p.merge) {
-            scratch(kWrite, L.geoColor, L.end);
-            if (r.key.accum)
-                put(kResAccum, kKeyedWrite, r.key.accum, 0, 1);
-        } else {
-            colors();
-        }
-        if (r.segments)
-            put(kResSegSlots, kAtomic, 0, 0, 1);
-        break;
-    case kKAccum:
-        put(kResGeoSet, kRead, p.geoSet, 0, 1);
-        put(kResSamples, kRead, 0, 0, 1);
-        colors();
-        break;
-    case kKOrder:
-        scratch(kRead, L.weight, L.order);
-        scratch(kWrite, L.order, L.order + (p.blocks + 4) * 4);
-        break;
-    case kKRender:
-        put(kResPrim, kRead, (unsigned long long)p.half, 0, 1);
-        if (p.cull) {
-            scratch(kRead, L.mask, L.pixMask);
-            scratch(kRead, L.order, L.order + (p.blocks + 4) * 4);
-        }
-        colors();
-        if (r.segments)
-            put(kResSegSlots, kAtomic, 0, 0, 1);
-        break;
-    case kKReduce:
-        put(kResSegSlots, kWrite, 0, 0, 1);
-        put(kResCallerSegments, kWrite, 0, 0, 1);
-        break;
-    default:
-        break;
     }
     return k;
 }
@@ -364,8 +367,9 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
 /* ---- the CPU test hook (include/rtc.h rtc_plan_sim_*) ---------------------------------------------------------- */
 struct RtcPlanSim {
     rtcplan::State st;
-    int triPadded, maskWords, legacy;
-    int sphereCount, sphereGate; /* rtc_plan_sim_set_spheres (0 spheres by default) */
+    rtcplan::SceneShape shape; /* rtc_plan_sim_set_spheres: 0 spheres by default */
+    int legacy;
+    rtcplan::Plan last; /* rtc_plan_sim_regions */
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -374,8 +378,8 @@ extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSi
         return RTC_EINVAL;
     RtcPlanSim *s = new RtcPlanSim();
     rtcplan::init(s->st);
-    s->triPadded = (triCount + 7) / 8 * 8;
-    s->maskWords = (s->triPadded + 63) / 64;
+    s->shape.triPadded = (triCount + 7) / 8 * 8;
+    s->shape.maskWords = (s->shape.triPadded + 63) / 64;
     s->legacy = legacySlotLayout;
     *out = s;
     return 0;
@@ -385,8 +389,8 @@ extern "C" int rtc_plan_sim_set_spheres(RtcPlanSim *s, int sphereCount, int gate
 {
     if (!s || sphereCount < 0)
         return RTC_EINVAL;
-    s->sphereCount = sphereCount;
-    s->sphereGate = gateAllows != 0;
+    s->shape.sphereCount = sphereCount;
+    s->shape.splitGate = gateAllows != 0;
     return 0;
 }
 
@@ -402,28 +406,10 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
 {
     if (!s || !d || !cam || !env)
         return RTC_EINVAL;
-    rtcplan::Request r{};
-    r.stream = stream;
-    r.flags = d->flags;
-    r.width = d->width;
-    r.rows = rtc_rows_selected(d);
-    r.rowStride = d->rowStride;
-    r.spp = d->spp;
-    r.sphereCount = d->trianglesOnly ? 0 : s->sphereCount;
-    r.sphereSplit = rtcplan::sphere_split(r.sphereCount, s->sphereGate != 0, d->flags);
-    r.triPadded = s->triPadded;
-    r.maskWords = s->maskWords;
-    r.segments = segments != 0;
-    r.key.colors = colors;
-    r.key.accum = accum;
-    memcpy(r.key.cam, cam, sizeof r.key.cam);
-    memcpy(r.key.env, env, sizeof r.key.env);
-    const int dims[9] = {d->width, d->height, r.rows, d->rowStart, d->rowStride, d->spp, d->maxBounce,
-                         (d->flags & RTC_F_HOIST_PRIMARY) ? 1 : 0, d->rowBand > 1 ? __builtin_ctz((unsigned)d->rowBand) : 0};
-    memcpy(r.key.dims, dims, sizeof dims);
-    memcpy(r.origin, cam, sizeof r.origin);
+    rtcplan::Request r = rtcplan::make_request(*d, rtc_rows_selected(d), s->shape, stream, colors, accum, segments != 0,
+                                               cam, env);
     r.legacySlotLayout = s->legacy != 0;
-    static thread_local rtcplan::Plan p;
+    rtcplan::Plan &p = s->last;
     rtcplan::plan_launch(s->st, r, p);
     s->st = p.after;
     /* ops: 4 ints each (kind, stream, event, kernel); per kernel op, its footprint entries (5 u64 each: op index, res,
@@ -450,4 +436,18 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
         q[4] = p.overlap, q[5] = p.slotOffset;
     }
     return p.nOps | ((nf + 1) << 8);
+}
+
+extern "C" int rtc_plan_sim_regions(const RtcPlanSim *s, unsigned long long *out, int maxRows)
+{
+    if (!s || !out || maxRows < 2 + rtcplan::kScratchRegions)
+        return RTC_EINVAL;
+    const rtcplan::Plan &p = s->last;
+    unsigned long long *q = out;
+    *q++ = p.slotOffset, *q++ = p.slotBytes, *q++ = p.scratchNeed;
+    *q++ = p.after.scratchCap, *q++ = p.samplesNeed, *q++ = p.bound;
+    for (int b = 0; b < rtcplan::kScratchRegions; ++b)
+        if (p.binds(b))
+            *q++ = (unsigned long long)b, *q++ = p.slotOffset + p.reg[b].offset, *q++ = p.reg[b].size;
+    return (int)((q - out) / 3);
 }

@@ -5,14 +5,23 @@
  * up to four streams: the caller's, two cull streams and the scene's side stream.  Pipelined
  * launches (RTC_F_OVERLAP) are in flight together, so every buffer two of them may touch at once needs either its own
  * copy (a scratch slot, a counter set) or an event between them.  rtc_plan_launch decides all of it from the scene's
- * ordering state and the launch's shape -- the scratch slot and its byte layout, the streams, every event record and
- * wait, which kernels run and which event each one completes -- as a list of operations; the HIP side only executes
- * that list (rtc_render.hip).  The same function drives the CPU test of the ordering (tests/test_plan.py through
- * rtc_plan_sim_*), which checks that every two kernels that may run together touch disjoint memory.
+ * ordering state and the launch's shape -- the scratch slot, the streams, every event record and wait, which kernels
+ * run and which event each one completes -- as a list of operations; the HIP side only executes that list
+ * (rtc_render.hip).  The same function drives the CPU test of the ordering (tests/test_plan.py through rtc_plan_sim_*),
+ * which checks that every two kernels that may run together touch disjoint memory.
+ *
+ * A launch's buffers are described once, by the Buf enumeration: one table (rtc_plan.cpp layout_slot) gives every scratch
+ * region its used size, alignment and padding, and one loop over it the offsets and the slot size; plan_launch records
+ * which buffers the launch binds (Plan::bound); the executor takes every scratch pointer from those bound regions and
+ * nothing else; and kernel_footprint evaluates one static list of (kernel, buffer, access) rows (kTouches) against
+ * them, so the ordering test sees the regions the executor binds.  A new buffer is a name in Buf, a row in layout_slot's
+ * table if it lies in the slot, its condition in plan_launch's bindings and its rows in kTouches.
  */
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#include "../../include/rtc.h"
 
 namespace rtcplan {
 
@@ -100,12 +109,37 @@ struct Request {
     bool noMerge;          /* the sky pass beside the geometry kernel even where it could follow it (A/B) */
 };
 
-/* byte offsets inside one scratch slot (the tile cull's outputs, rtc_render.hip) */
-struct Layout {
-    size_t mask, pixMask, weight, order, geoList, superMask;
-    size_t pixItem;  /* per pixel (tile * 64 + bit) of the geometry pixels: its item (merged sky pass) */
-    size_t geoColor; /* per item: its Color bytes (merged sky pass) */
-    size_t end;
+/* the scene's shape as the planner needs it (RtcDeviceScene; rtc_plan_sim_create / _set_spheres) */
+struct SceneShape {
+    int triPadded, maskWords, sphereCount;
+    bool splitGate; /* sphere_split's gate */
+};
+/* The one constructor of a Request (the executor's and the test hook's): rows = rtc_rows_selected(d); the key is the
+ * camera cam[13] = origin, ex, ey, ez, fov, the environment env[14] = sun, horizon, zenith, ground, focus, intensity and
+ * nine dims of the launch; legacySlotLayout and noMerge are left clear */
+Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uint64_t stream, uint64_t colors,
+                     uint64_t accum, bool segments, const float cam[13], const float env[14]);
+
+/* The launch-scoped buffers: the regions of one scratch slot, in slot order, then the resources outside it */
+enum Buf : int {
+    kBufMask,      /* per tile: maskWords u64 of candidate triangles */
+    kBufPixMask,   /* per tile: its pixels with a candidate */
+    kBufWeight,    /* per workgroup block: its weight (rtc_order_blocks) */
+    kBufOrder,     /* launch slot -> workgroup block (one-lane-per-pixel kernel) */
+    kBufGeoList,   /* kGeoLists sub-lists of geoCap geometry pixels */
+    kBufSuperMask, /* per superblock: maskWords u64 of survivors (rtc_super_cull) */
+    kBufPixItem,   /* per pixel (tile * 64 + bit) of the geometry pixels: its item (merged sky pass) */
+    kBufGeoColor,  /* per item: its Color bytes (merged sky pass) */
+    kScratchRegions,
+    kBufPrim = kScratchRegions, /* the slot's primary records */
+    kBufGeoSet, kBufGeoSetNext, /* this split launch's counter set and the next one's */
+    kBufSamples,                /* the deferred sample slots */
+    kBufSegSlots,
+    kBufColors, kBufAccum, kBufCallerSegments, /* the caller's */
+    kBufs
+};
+struct Region {
+    size_t offset, size; /* inside the slot; size: the bytes in use (padding and alignment gaps belong to no region) */
 };
 
 struct Plan {
@@ -119,7 +153,9 @@ struct Plan {
     int geoCap;
     size_t slotBytes;    /* bytes per slot (halfBytes: what this launch needs) */
     size_t slotOffset;   /* where slot `half` starts */
-    Layout lay;
+    Region reg[kScratchRegions];
+    unsigned bound;      /* bit b: the launch binds Buf b (an unbound buffer: a null pointer, no footprint row) */
+    bool binds(int b) const { return (bound >> b & 1u) != 0; }
     size_t scratchNeed;  /* kSlots x slotBytes: grow the scratch to it first (hipFree synchronises the device) */
     bool scratchGrow, samplesGrow, needCst2;
     size_t samplesNeed;

@@ -2521,26 +2521,6 @@ static hipError_t launch_stop(void (*k)(K...), dim3 g, dim3 b, size_t sh, hipStr
     return hipGetLastError();
 }
 
-/* what an unjoined sky pass writes (rtcplan::Key): its buffers and everything that decides their values */
-static rtcplan::Key sky_key(const RenderParams &P)
-{
-    rtcplan::Key k;
-    memset(&k, 0, sizeof k);
-    k.colors = (uint64_t)(uintptr_t)P.colors;
-    k.accum = (uint64_t)(uintptr_t)P.accum;
-    const V3 c[4] = {P.origin, P.ex, P.ey, P.ez}, e[4] = {P.env.sun, P.env.horizon, P.env.zenith, P.env.ground};
-    for (int i = 0; i < 4; ++i) {
-        k.cam[3 * i] = c[i].x, k.cam[3 * i + 1] = c[i].y, k.cam[3 * i + 2] = c[i].z;
-        k.env[3 * i] = e[i].x, k.env[3 * i + 1] = e[i].y, k.env[3 * i + 2] = e[i].z;
-    }
-    k.cam[12] = P.fov;
-    k.env[12] = P.env.focus;
-    k.env[13] = P.env.intensity;
-    const int dims[9] = {P.width, P.height, P.rows, P.rowStart, P.rowStride, P.spp, P.maxBounce, P.hoist, P.rowBandShift};
-    memcpy(k.dims, dims, sizeof dims);
-    return k;
-}
-
 static EnvParams env_of(const Scene &s)
 {
     EnvParams e{};
@@ -2571,19 +2551,23 @@ constexpr bool kAbNoSlots = true; /* timing experiment only (RTC_EXPERIMENT): de
 #else
 constexpr bool kAbNoSlots = false;
 #endif
-extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
-                                     const RtcRenderDesc *d, void *dColors, float *dAccum,
-                                     unsigned long long *dSegments, void *stream)
+/* One launch as its planned kernels see it */
+struct Launch {
+    const RtcDeviceScene *s;
+    const rtcplan::Plan &pl;
+    RenderParams P;
+    int wgsPerCu;    /* the geometry kernel's workgroups per CU */
+    size_t chainDyn; /* and its dynamic LDS */
+    dim3 grid() const { return dim3(pl.gridX, pl.gridY); } /* one 16x16 workgroup block each */
+    /* every pointer into the scratch: a region the plan binds (rtcplan::Buf), in the launch's slot; unbound: null */
+    template <typename T> T *region(int buf) const
+    {
+        return pl.binds(buf) ? (T *)(s->scratch + pl.slotOffset + pl.reg[buf].offset) : nullptr;
+    }
+};
+
+static int check_arguments(const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d, const void *dColors)
 {
-    if (!s)
-        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null scene");
-    RtcDeviceScene *const ms = const_cast<RtcDeviceScene *>(s);
-    /* The hooks are one-shot: this launch takes the events armed before it and forgets them -- before any early
-     * return, so a later launch never records an event its caller has since released (rtc_scene_set_geometry_event /
-     * _frame_event); a launch that fails records neither */
-    const hipEvent_t geoEvent = s->geoEvent, frameEvent = s->frameEvent;
-    ms->geoEvent = nullptr;
-    ms->frameEvent = nullptr;
     if (!scene || !cam || !d || !dColors)
         return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null argument");
     if (d->width <= 0 || d->height <= 0 || d->rowStride <= 0 || d->rowStart < 0 || d->rowBand < 0 || d->rowBand > 64 ||
@@ -2595,266 +2579,282 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
     if (d->flags & (RTC_F_COOP4 | RTC_F_COOP8 | RTC_F_PIPE | RTC_F_SPEC))
         return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: RTC_F_COOP4 / COOP8 / PIPE / SPEC name kernels that were "
                                     "removed (rtc_render_chain renders every geometry pixel)");
-    const int rows = rtc_rows_selected(d);
-    /* the scene's buffers, scratch and kernels live on s->device; the caller's current device is restored */
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "rtc_render_rows_async: cannot select the scene's device %d", s->device);
-    if (rows == 0) { /* nothing to render: the (empty) frame is complete once `stream` gets here */
-        for (hipEvent_t ev : {geoEvent, frameEvent})
-            if (ev)
-                HIP_TRY(hipEventRecord(ev, (hipStream_t)stream));
-        return 0;
-    }
+    return 0;
+}
+
+/* what the kernels read of the scene, the launch's shape and the camera (the plan's buffers: bind_plan) */
+static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, const RtcCamera &cam,
+                                  const RtcRenderDesc &d, int rows, void *dColors, float *dAccum,
+                                  unsigned long long *dSegments)
+{
     RenderParams P;
     memset(&P, 0, sizeof P);
-    P.tris = s->tris;
-    P.mats = s->mats;
-    P.spheres = s->spheres;
-    P.colors = (unsigned char *)dColors;
-    P.accum = dAccum;
-    P.segments = dSegments;
-    P.segSlots = s->segSlots;
-    P.triCount = s->triCount;
-    P.triPadded = s->triPadded;
-    P.clTris = s->clTris;
-    P.clusters = s->clusters;
-    P.chunks = s->chunks;
-    P.chunkCount = s->chunkCount;
-    P.clusterCount = s->clusterCount;
-    P.clusterCull = !(d->flags & RTC_F_NO_CLUSTER_CULL);
-    P.sphereCount = d->trianglesOnly ? 0 : s->sphereCount;
-    P.maskWords = s->maskWords;
-    P.width = d->width;
-    P.height = d->height;
-    P.rows = rows;
-    P.rowStart = d->rowStart;
-    P.rowStride = d->rowStride;
-    P.rowBandShift = d->rowBand > 1 ? __builtin_ctz((unsigned)d->rowBand) : 0;
-    P.spp = d->spp;
-    P.maxBounce = d->maxBounce;
-    P.hoist = (d->flags & RTC_F_HOIST_PRIMARY) ? 1 : 0;
-    P.invSpp = d->spp > 0 ? (float)(1. / (double)d->spp) : 0.f;
-    P.origin = v3(cam->origin);
-    P.ex = v3(cam->ex);
-    P.ey = v3(cam->ey);
-    P.ez = v3(cam->ez);
-    P.fov = cam->fov;
-    P.env = env_of(*scene);
-    hipStream_t st = (hipStream_t)stream;
-    /* every ordering decision -- slot, streams, events, which kernels -- comes from the planner (rtc_plan.h); this
-     * function executes its operations */
-    rtcplan::Request rq{};
-    rq.stream = (uint64_t)(uintptr_t)st;
-    rq.flags = d->flags;
-    rq.width = d->width;
-    rq.rows = rows;
-    rq.rowStride = d->rowStride;
-    rq.spp = d->spp;
-    rq.sphereCount = P.sphereCount;
-    rq.sphereSplit = rtcplan::sphere_split(P.sphereCount, s->sphereSplitGate, d->flags);
-    rq.triPadded = s->triPadded;
-    rq.maskWords = s->maskWords;
-    rq.segments = dSegments != nullptr;
-    rq.key = sky_key(P);
-    memcpy(rq.origin, &P.origin, sizeof rq.origin);
-    rq.noMerge = !RTC_SKY_MERGE;
-    static thread_local rtcplan::Plan pl;
-    rtcplan::plan_launch(s->plan, rq, pl);
-    /* the saved state claims only what has been enqueued: until every operation below is, a later launch sees none of
-     * this launch's primary records or counter zeroing (it re-runs rtc_prep_primary) */
-    ms->plan.prepValid[pl.half] = false;
-    ms->plan.cullValid = false;
+    P.tris = s->tris, P.mats = s->mats, P.spheres = s->spheres;
+    P.triCount = s->triCount, P.triPadded = s->triPadded, P.maskWords = s->maskWords;
+    P.sphereCount = d.trianglesOnly ? 0 : s->sphereCount;
+    P.clTris = s->clTris, P.clusters = s->clusters, P.clusterCount = s->clusterCount;
+    P.chunks = s->chunks, P.chunkCount = s->chunkCount, P.clusterCull = !(d.flags & RTC_F_NO_CLUSTER_CULL);
+    P.colors = (unsigned char *)dColors, P.accum = dAccum;
+    P.segments = dSegments, P.segSlots = s->segSlots;
+    P.width = d.width, P.height = d.height;
+    P.rows = rows, P.rowStart = d.rowStart, P.rowStride = d.rowStride;
+    P.rowBandShift = d.rowBand > 1 ? __builtin_ctz((unsigned)d.rowBand) : 0;
+    P.spp = d.spp, P.maxBounce = d.maxBounce;
+    P.hoist = (d.flags & RTC_F_HOIST_PRIMARY) ? 1 : 0;
+    P.invSpp = d.spp > 0 ? (float)(1. / (double)d.spp) : 0.f;
+    P.origin = v3(cam.origin), P.ex = v3(cam.ex), P.ey = v3(cam.ey), P.ez = v3(cam.ez), P.fov = cam.fov;
+    P.env = env_of(scene);
+    return P;
+}
+
+/* every slot of the scratch, or the sample slots (hipFree synchronises the device: no launch still reads the old ones) */
+static int regrow(unsigned char *&buf, size_t &cap, size_t need)
+{
+    if (buf)
+        HIP_TRY(hipFree(buf));
+    buf = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(&buf, need));
+    cap = need;
+    return 0;
+}
+
+/* the second cull stream, the scratch and the sample slots the plan asks for */
+static int grow_capacity(RtcDeviceScene *ms, const rtcplan::Plan &pl)
+{
     if (pl.needCst2) { /* created on first use: whole frames keep three streams (one more costs them ~1 %) */
         int leastPrio = 0, greatestPrio = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&leastPrio, &greatestPrio));
         HIP_TRY(hipStreamCreateWithPriority(&ms->cst2, hipStreamNonBlocking, greatestPrio));
         ms->plan.cst2 = true;
     }
-    if (pl.scratchGrow) { /* every slot (hipFree synchronises the device: no launch still reads the old scratch) */
-        if (ms->scratch)
-            HIP_TRY(hipFree(ms->scratch));
-        ms->scratch = nullptr;
-        ms->plan.scratchCap = 0;
-        HIP_TRY(hipMalloc(&ms->scratch, pl.scratchNeed));
-        ms->plan.scratchCap = pl.scratchNeed;
-    }
-    if (pl.samplesGrow) {
-        if (ms->samples)
-            HIP_TRY(hipFree(ms->samples));
-        ms->samples = nullptr;
-        ms->plan.samplesCap = 0;
-        HIP_TRY(hipMalloc(&ms->samples, pl.samplesNeed));
-        ms->plan.samplesCap = pl.samplesNeed;
-    }
-    const int half = pl.half;
-    P.primF = s->primF + (size_t)half * s->primStride;
-    P.primX = s->primX + (size_t)half * s->primStride;
+    if (const int rc = pl.scratchGrow ? regrow(ms->scratch, ms->plan.scratchCap, pl.scratchNeed) : 0)
+        return rc;
+    return pl.samplesGrow ? regrow(ms->samples, ms->plan.samplesCap, pl.samplesNeed) : 0;
+}
+
+/* the plan's buffers as RenderParams fields (the kernel arguments beside P: the run_ functions) */
+static void bind_plan(Launch &L, int flags)
+{
+    const RtcDeviceScene *s = L.s;
+    const rtcplan::Plan &pl = L.pl;
+    RenderParams &P = L.P;
+    P.primF = s->primF + (size_t)pl.half * s->primStride;
+    P.primX = s->primX + (size_t)pl.half * s->primStride;
     P.blocksX = (int)pl.gridX;
-    unsigned long long *mask = nullptr, *pixMask = nullptr, *superMask = nullptr;
-    unsigned *weight = nullptr;
-    int *order = nullptr;
-    if (pl.cull) {
-        unsigned char *slot = s->scratch + pl.slotOffset;
-        mask = (unsigned long long *)(slot + pl.lay.mask);
-        pixMask = (unsigned long long *)(slot + pl.lay.pixMask);
-        weight = (unsigned *)(slot + pl.lay.weight);
-        order = (int *)(slot + pl.lay.order);
-        superMask = (unsigned long long *)(slot + pl.lay.superMask);
-        if (pl.merge) {
-            P.pixItem = (unsigned *)(slot + pl.lay.pixItem);
-            P.geoColor = (unsigned *)(slot + pl.lay.geoColor);
-        }
-        P.tileMask = mask;
-        P.pixMask = pixMask;
-        if (!pl.fused)
-            P.order = (d->flags & RTC_F_NO_REORDER) ? nullptr : order;
-    }
-    if (pl.superCull) {
-        P.superMask = superMask;
-        P.superX = (int)pl.superX;
-    }
-    if (pl.chain) {
+    /* (read-only aliases of rtc_tile_cull's mask / pixMask arguments) */
+    P.tileMask = L.region<unsigned long long>(rtcplan::kBufMask);
+    P.pixMask = L.region<unsigned long long>(rtcplan::kBufPixMask);
+    /* RTC_F_NO_REORDER: rtc_order_blocks still runs and writes the bound region; the render kernel takes raster order */
+    P.order = (flags & RTC_F_NO_REORDER) ? nullptr : L.region<int>(rtcplan::kBufOrder);
+    P.superMask = L.region<unsigned long long>(rtcplan::kBufSuperMask);
+    P.superX = P.superMask ? (int)pl.superX : 0;
+    P.geoList = L.region<int>(rtcplan::kBufGeoList);
+    P.pixItem = L.region<unsigned>(rtcplan::kBufPixItem);
+    P.geoColor = L.region<unsigned>(rtcplan::kBufGeoColor);
+    if (pl.binds(rtcplan::kBufGeoSet)) {
         P.geoCount = s->geoCounts + (size_t)pl.geoSet * kGeoSetInts;
         P.geoCountNext = s->geoCounts + (size_t)pl.geoSetNext * kGeoSetInts;
-        P.geoList = (int *)(s->scratch + pl.slotOffset + pl.lay.geoList);
         P.geoCap = pl.geoCap;
         P.cullPrio = pl.cullPrio;
-        if (pl.sampleCap > 0) {
-            P.sampleBuf = (SampleSlot *)s->samples;
-            P.itemPix = (int *)(s->samples + (size_t)pl.sampleCap * (size_t)d->spp * sizeof(SampleSlot));
-            P.sampleCap = pl.sampleCap;
-        }
     }
-    /* dynamic LDS of the geometry kernel: the clustered records (single-chunk scenes), then the primary filter records
-     * when the block stays within its workgroups per CU */
-    const int wgsPerCu = pl.smallShare ? RTC_CHAIN_WGS_SHARE : s->chainWgsFull;
+    if (pl.binds(rtcplan::kBufSamples)) {
+        P.sampleBuf = (SampleSlot *)s->samples;
+        P.itemPix = (int *)(s->samples + (size_t)pl.sampleCap * (size_t)P.spp * sizeof(SampleSlot));
+        P.sampleCap = pl.sampleCap;
+    }
+}
+
+/* dynamic LDS of the geometry kernel: the clustered records (single-chunk scenes), then the primary filter records
+ * when the block stays within its workgroups per CU */
+static void size_chain_lds(Launch &L)
+{
+    const RtcDeviceScene *s = L.s;
+    L.wgsPerCu = L.pl.smallShare ? RTC_CHAIN_WGS_SHARE : s->chainWgsFull;
     const size_t recLds = s->chunkCount <= 1 ? (size_t)soa_slots(s->clusterCount * kClusterSize) * sizeof(DevTri) : 0;
     const size_t pfLds = (size_t)s->triPadded * sizeof(DevPrimF);
-    P.chainPrimF = s->chunkCount <= 1 && kChainStaticLds + recLds + pfLds <= kCuLds / (size_t)wgsPerCu;
-    const size_t floorLds = chain_lds_floor(wgsPerCu);
-    const size_t chainDyn = std::max<size_t>(recLds + (P.chainPrimF ? pfLds : 0),
-                                             floorLds > kChainStaticLds ? floorLds - kChainStaticLds : 0);
-    const dim3 grid(pl.gridX, pl.gridY);
+    L.P.chainPrimF = s->chunkCount <= 1 && kChainStaticLds + recLds + pfLds <= kCuLds / (size_t)L.wgsPerCu;
+    const size_t floorLds = chain_lds_floor(L.wgsPerCu);
+    L.chainDyn = std::max<size_t>(recLds + (L.P.chainPrimF ? pfLds : 0),
+                                  floorLds > kChainStaticLds ? floorLds - kChainStaticLds : 0);
+}
+
+/* ---- one function per planned kernel, in rtcplan::Kernel's order (kPlanned): on stream `os`, completing `ev`.
+ * The device code is emitted in the order these functions first name the kernels: keep that order. */
+static int run_prep(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    const int n = L.s->triPadded;
+    HIP_TRY(launch_stop(rtc_prep_primary, dim3((n + 8 + 63) / 64), dim3(64), 0, os, nullptr, L.s->tris,
+                        const_cast<DevPrimF *>(L.P.primF), const_cast<DevPrimX *>(L.P.primX), n > 0 ? n + 8 : 0,
+                        L.P.origin, L.pl.prepCounts ? L.P.geoCount : nullptr));
+    return 0;
+}
+
+static int run_super_cull(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    HIP_TRY(launch_stop(rtc_super_cull, dim3(L.pl.superX, L.pl.superY), dim3(64), 0, os, nullptr, L.P,
+                        L.region<unsigned long long>(rtcplan::kBufSuperMask)));
+    return 0;
+}
+
+static int run_tile_cull(const Launch &L, hipStream_t os, hipEvent_t ev)
+{
+    unsigned long long *const mask = L.region<unsigned long long>(rtcplan::kBufMask);
+    unsigned long long *const pixMask = L.region<unsigned long long>(rtcplan::kBufPixMask);
+    unsigned *const weight = L.region<unsigned>(rtcplan::kBufWeight);
+    const size_t lds = (size_t)L.s->maskWords * sizeof(unsigned long long);
+    if (L.P.geoList && L.P.sphereCount > 0) /* the sphere split: sphere pixels are geometry pixels */
+        HIP_TRY(launch_sphere_cull(L.grid(), lds, os, ev, L.P, mask, weight, pixMask));
+    else
+        HIP_TRY(launch_stop(rtc_tile_cull, L.grid(), dim3(kBlock), lds, os, ev, L.P, mask, weight, pixMask));
+    return 0;
+}
+
+static int run_sky(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    const RenderParams &P = L.P;
+    const bool wide = L.pl.smallShare && (size_t)P.width * (size_t)P.rows > 400000; /* four-wave workgroups */
+    const bool general = P.geoColor || P.hoist || P.accum || P.segments;
+    static void (*const kSky[2][2])(RenderParams) = {{rtc_render_sky_rows<4, true>, rtc_render_sky_rows<4, false>},
+                                                     {rtc_render_sky_rows<1, true>, rtc_render_sky_rows<1, false>}};
+    if (L.s->timing)
+        HIP_TRY(hipEventRecord(L.s->evSky0, os));
+    const dim3 grid((P.width + 63) / 64, wide ? (P.rows + 3) / 4 : P.rows);
+    HIP_TRY(launch_stop(kSky[!wide][!general], grid, dim3(wide ? 256 : 64), 0, os, nullptr, P));
+    if (L.s->timing)
+        HIP_TRY(hipEventRecord(L.s->evSky1, os));
+    return 0;
+}
+
+static int run_chain(const Launch &L, hipStream_t os, hipEvent_t ev)
+{
+    const RtcDeviceScene *s = L.s;
+    const RenderParams &P = L.P;
+    const dim3 cg((unsigned)(L.wgsPerCu * s->cuCount)), cb(kChainBlock);
+    const bool multi = s->chunkCount > 1, count = P.segments != nullptr;
+    const bool defer = P.sampleCap > 0 || P.hoist || !P.chainPrimF; /* (GENERAL) */
+    const bool hits = s->chainWgsFull == RTC_CHAIN_WGS_HIT && RTC_CHAIN_WGS_HIT != RTC_CHAIN_WGS_FULL;
+    /* <MULTI, COUNT, HITS, GENERAL> (multi-chunk scenes never stage the primary records: GENERAL) */
+    static void (*const kChain[6])(RenderParams) = {
+        rtc_render_chain<true, true, false, true>,   rtc_render_chain<true, false, false, true>,
+        rtc_render_chain<false, true, false, true>,  rtc_render_chain<false, false, false, true>,
+        rtc_render_chain<false, false, true, false>, rtc_render_chain<false, false, false, false>};
+    const int variant = multi ? !count : count ? 2 : defer ? 3 : hits ? 4 : 5;
+    if (s->timing)
+        HIP_TRY(hipEventRecord(s->evHeavy0, os));
+    if (P.sphereCount > 0) /* the sphere split: GENERAL, for MULTI x COUNT */
+        HIP_TRY(launch_sphere_chain(multi, count, cg, cb, L.chainDyn, os, ev, P));
+    else
+        HIP_TRY(launch_stop(kChain[variant], cg, cb, L.chainDyn, os, ev, P));
+    if (s->timing) /* the chain kernel alone (rocprof's rtc_render_chain row) */
+        HIP_TRY(hipEventRecord(s->evHeavy1, os));
+    return 0;
+}
+
+static int run_accumulate(const Launch &L, hipStream_t os, hipEvent_t ev)
+{
+    const unsigned g = (unsigned)std::min<size_t>(((size_t)L.P.sampleCap + 255) / 256, 1024);
+    if (!kAbNoSlots)
+        HIP_TRY(launch_stop(rtc_accumulate_samples, dim3(g), dim3(256), 0, os, ev, L.P));
+    else if (ev)
+        HIP_TRY(hipEventRecord(ev, os));
+    return 0;
+}
+
+static int run_order(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    HIP_TRY(launch_stop(rtc_order_blocks, dim3(1), dim3(1024), 0, os, nullptr, L.region<unsigned>(rtcplan::kBufWeight),
+                        (int)L.pl.blocks, L.region<int>(rtcplan::kBufOrder)));
+    return 0;
+}
+
+static int run_render(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    static void (*const kRender[2][2])(RenderParams) = {{rtc_render_kernel<true, true>, rtc_render_kernel<true, false>},
+                                                        {rtc_render_kernel<false, true>, rtc_render_kernel<false, false>}};
+    HIP_TRY(launch_stop(kRender[L.P.sphereCount <= 0][!L.pl.debug], L.grid(), dim3(kBlock), 0, os, nullptr, L.P));
+    return 0;
+}
+
+static int run_reduce(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    HIP_TRY(launch_stop(rtc_reduce_segments, dim3(1), dim3(kSegSlots), 0, os, nullptr, L.P.segSlots, L.P.segments));
+    return 0;
+}
+
+static int (*const kPlanned[])(const Launch &, hipStream_t, hipEvent_t) = { /* by rtcplan::Kernel */
+    run_prep, run_super_cull, run_tile_cull, run_sky, run_chain, run_accumulate, run_order, run_render, run_reduce};
+static_assert(sizeof kPlanned / sizeof kPlanned[0] == rtcplan::kKReduce + 1, "one function per planned kernel");
+
+extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                                     const RtcRenderDesc *d, void *dColors, float *dAccum,
+                                     unsigned long long *dSegments, void *stream)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null scene");
+    RtcDeviceScene *const ms = const_cast<RtcDeviceScene *>(s);
+    /* The hooks are one-shot: this launch takes the events armed before it and forgets them -- before any early
+     * return, so a later launch never records an event its caller has since released (rtc_scene_set_geometry_event /
+     * _frame_event); a launch that fails records neither */
+    const hipEvent_t geoEvent = s->geoEvent, frameEvent = s->frameEvent;
+    ms->geoEvent = ms->frameEvent = nullptr;
+    if (const int rc = check_arguments(scene, cam, d, dColors))
+        return rc;
+    const int rows = rtc_rows_selected(d);
+    /* the scene's buffers, scratch and kernels live on s->device; the caller's current device is restored */
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_render_rows_async: cannot select the scene's device %d", s->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (rows == 0) { /* nothing to render: the (empty) frame is complete once `stream` gets here */
+        for (hipEvent_t ev : {geoEvent, frameEvent})
+            if (ev)
+                HIP_TRY(hipEventRecord(ev, st));
+        return 0;
+    }
+    static thread_local rtcplan::Plan pl;
+    Launch L{s, pl, render_params(s, *scene, *cam, *d, rows, dColors, dAccum, dSegments), 0, 0};
+    /* every ordering decision -- slot, streams, events, which kernels, which buffers -- comes from the planner
+     * (rtc_plan.h); this function executes its operations */
+    const RenderParams &P = L.P;
+    const EnvParams &E = P.env;
+    const float camKey[13] = {P.origin.x, P.origin.y, P.origin.z, P.ex.x, P.ex.y, P.ex.z, P.ey.x,
+                              P.ey.y,     P.ey.z,     P.ez.x,     P.ez.y, P.ez.z, P.fov};
+    const float envKey[14] = {E.sun.x,    E.sun.y,    E.sun.z,    E.horizon.x, E.horizon.y, E.horizon.z, E.zenith.x,
+                              E.zenith.y, E.zenith.z, E.ground.x, E.ground.y,  E.ground.z,  E.focus,     E.intensity};
+    rtcplan::Request rq = rtcplan::make_request(
+        *d, rows, rtcplan::SceneShape{s->triPadded, s->maskWords, s->sphereCount, s->sphereSplitGate},
+        (uint64_t)(uintptr_t)st, (uint64_t)(uintptr_t)dColors, (uint64_t)(uintptr_t)dAccum, dSegments != nullptr, camKey,
+        envKey);
+    rq.noMerge = !RTC_SKY_MERGE;
+    rtcplan::plan_launch(s->plan, rq, pl);
+    /* the saved state claims only what has been enqueued: until every operation below is, a later launch sees none of
+     * this launch's primary records or counter zeroing (it re-runs rtc_prep_primary) */
+    ms->plan.prepValid[pl.half] = false;
+    ms->plan.cullValid = false;
+    if (const int rc = grow_capacity(ms, pl))
+        return rc;
+    bind_plan(L, d->flags);
+    size_chain_lds(L);
     const hipStream_t streams[rtcplan::kStreams] = {st, s->cst, ms->cst2, s->side};
-    const auto event = [&](int e) -> hipEvent_t {
-        if (e >= rtcplan::kEvSkyDone0 && e < rtcplan::kEvSkyDone0 + kSkySlots)
-            return s->evSkyDone[e - rtcplan::kEvSkyDone0];
-        if (e >= rtcplan::kEvGeoDone0 && e < rtcplan::kEvGeoDone0 + kSkySlots)
-            return s->evGeoDone[e - rtcplan::kEvGeoDone0];
-        switch (e) {
-        case rtcplan::kEvCullSync: return s->evCullSync;
-        case rtcplan::kEvFork: return s->evFork;
-        case rtcplan::kEvJoin: return s->evJoin;
-        case rtcplan::kEvFrame: return frameEvent;
-        case rtcplan::kEvGeometry: return geoEvent;
-        default: return nullptr;
-        }
-    };
+    hipEvent_t events[rtcplan::kEvents] = {}; /* (the caller's hooks may be unarmed: null) */
+    events[rtcplan::kEvCullSync] = s->evCullSync, events[rtcplan::kEvFork] = s->evFork, events[rtcplan::kEvJoin] = s->evJoin;
+    events[rtcplan::kEvFrame] = frameEvent, events[rtcplan::kEvGeometry] = geoEvent;
+    for (int h = 0; h < kSkySlots; ++h)
+        events[rtcplan::kEvSkyDone0 + h] = s->evSkyDone[h], events[rtcplan::kEvGeoDone0 + h] = s->evGeoDone[h];
     for (int i = 0; i < pl.nOps; ++i) {
         const rtcplan::Op &op = pl.ops[i];
         const hipStream_t os = streams[op.stream];
-        const hipEvent_t ev = event(op.event);
+        const hipEvent_t ev = op.event >= 0 && op.event < rtcplan::kEvents ? events[op.event] : nullptr;
         if (op.kind == rtcplan::kOpRecord) {
-            if (ev) /* (the caller's hooks may be unarmed) */
+            if (ev)
                 HIP_TRY(hipEventRecord(ev, os));
-            continue;
-        }
-        if (op.kind == rtcplan::kOpWait) {
+        } else if (op.kind == rtcplan::kOpWait) {
             HIP_TRY(hipStreamWaitEvent(os, ev, 0));
-            continue;
-        }
-        switch (op.kernel) {
-        case rtcplan::kKPrep:
-            hipLaunchKernelGGL(rtc_prep_primary, dim3((s->triPadded + 8 + 63) / 64), dim3(64), 0, os, s->tris,
-                               const_cast<DevPrimF *>(P.primF), const_cast<DevPrimX *>(P.primX),
-                               s->triPadded > 0 ? s->triPadded + 8 : 0, P.origin, pl.prepCounts ? P.geoCount : nullptr);
-            HIP_TRY(hipGetLastError());
-            break;
-        case rtcplan::kKSuperCull:
-            hipLaunchKernelGGL(rtc_super_cull, dim3(pl.superX, pl.superY), dim3(64), 0, os, P, superMask);
-            HIP_TRY(hipGetLastError());
-            break;
-        case rtcplan::kKTileCull:
-            if (pl.chain && P.sphereCount > 0) /* the sphere split: sphere pixels are geometry pixels */
-                HIP_TRY(launch_sphere_cull(grid, (size_t)s->maskWords * sizeof(unsigned long long), os, ev, P, mask, weight,
-                                           pixMask));
-            else
-                HIP_TRY(launch_stop(rtc_tile_cull, grid, dim3(kBlock), (size_t)s->maskWords * sizeof(unsigned long long), os,
-                                    ev, P, mask, weight, pixMask));
-            break;
-        case rtcplan::kKSky: {
-            if (s->timing)
-                HIP_TRY(hipEventRecord(s->evSky0, os));
-            const bool skyWide = pl.smallShare && (size_t)d->width * (size_t)rows > 400000; /* four-wave workgroups */
-            const bool general = P.geoColor || P.hoist || P.accum || P.segments;
-            const dim3 g4((d->width + 63) / 64, (rows + 3) / 4), g1((d->width + 63) / 64, rows);
-            if (skyWide && general)
-                hipLaunchKernelGGL((rtc_render_sky_rows<4, true>), g4, dim3(256), 0, os, P);
-            else if (skyWide)
-                hipLaunchKernelGGL((rtc_render_sky_rows<4, false>), g4, dim3(256), 0, os, P);
-            else if (general)
-                hipLaunchKernelGGL((rtc_render_sky_rows<1, true>), g1, dim3(64), 0, os, P);
-            else
-                hipLaunchKernelGGL((rtc_render_sky_rows<1, false>), g1, dim3(64), 0, os, P);
-            HIP_TRY(hipGetLastError());
-            if (s->timing)
-                HIP_TRY(hipEventRecord(s->evSky1, os));
-            break;
-        }
-        case rtcplan::kKChain: {
-            if (s->timing)
-                HIP_TRY(hipEventRecord(s->evHeavy0, os));
-            const dim3 cg((unsigned)(wgsPerCu * s->cuCount)), cb(kChainBlock);
-            const bool defer = P.sampleCap > 0 || P.hoist || !P.chainPrimF; /* (GENERAL) */
-            const bool hits = s->chainWgsFull == RTC_CHAIN_WGS_HIT && RTC_CHAIN_WGS_HIT != RTC_CHAIN_WGS_FULL;
-            if (P.sphereCount > 0) /* the sphere split: GENERAL, for MULTI x COUNT */
-                HIP_TRY(launch_sphere_chain(s->chunkCount > 1, dSegments != nullptr, cg, cb, chainDyn, os, ev, P));
-            else if (s->chunkCount > 1 && dSegments)
-                HIP_TRY(launch_stop(rtc_render_chain<true, true, false, true>, cg, cb, chainDyn, os, ev, P));
-            else if (s->chunkCount > 1) /* (multi-chunk scenes never stage the primary records: GENERAL) */
-                HIP_TRY(launch_stop(rtc_render_chain<true, false, false, true>, cg, cb, chainDyn, os, ev, P));
-            else if (dSegments)
-                HIP_TRY(launch_stop(rtc_render_chain<false, true, false, true>, cg, cb, chainDyn, os, ev, P));
-            else if (defer)
-                HIP_TRY(launch_stop(rtc_render_chain<false, false, false, true>, cg, cb, chainDyn, os, ev, P));
-            else if (hits)
-                HIP_TRY(launch_stop(rtc_render_chain<false, false, true, false>, cg, cb, chainDyn, os, ev, P));
-            else
-                HIP_TRY(launch_stop(rtc_render_chain<false, false, false, false>, cg, cb, chainDyn, os, ev, P));
-            if (s->timing) /* the chain kernel alone (rocprof's rtc_render_chain row) */
-                HIP_TRY(hipEventRecord(s->evHeavy1, os));
-            break;
-        }
-        case rtcplan::kKAccum:
-            if (!kAbNoSlots) {
-                const unsigned g = (unsigned)std::min<size_t>(((size_t)P.sampleCap + 255) / 256, 1024);
-                HIP_TRY(launch_stop(rtc_accumulate_samples, dim3(g), dim3(256), 0, os, ev, P));
-            } else if (ev) {
-                HIP_TRY(hipEventRecord(ev, os));
-            }
-            break;
-        case rtcplan::kKOrder:
-            hipLaunchKernelGGL(rtc_order_blocks, dim3(1), dim3(1024), 0, os, weight, (int)pl.blocks, order);
-            HIP_TRY(hipGetLastError());
-            break;
-        case rtcplan::kKRender:
-            if (P.sphereCount > 0 && pl.debug)
-                hipLaunchKernelGGL((rtc_render_kernel<true, true>), grid, dim3(kBlock), 0, os, P);
-            else if (P.sphereCount > 0)
-                hipLaunchKernelGGL((rtc_render_kernel<true, false>), grid, dim3(kBlock), 0, os, P);
-            else if (pl.debug)
-                hipLaunchKernelGGL((rtc_render_kernel<false, true>), grid, dim3(kBlock), 0, os, P);
-            else
-                hipLaunchKernelGGL((rtc_render_kernel<false, false>), grid, dim3(kBlock), 0, os, P);
-            HIP_TRY(hipGetLastError());
-            break;
-        case rtcplan::kKReduce:
-            hipLaunchKernelGGL(rtc_reduce_segments, dim3(1), dim3(kSegSlots), 0, os, s->segSlots, dSegments);
-            HIP_TRY(hipGetLastError());
-            break;
-        default:
+        } else if (op.kernel < 0 || op.kernel > rtcplan::kKReduce) {
             return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: unknown planned kernel %d", op.kernel);
+        } else if (const int rc = kPlanned[op.kernel](L, os, ev)) {
+            return rc;
         }
     }
     ms->timed = pl.fused && s->timing;

@@ -25,6 +25,7 @@ KERNEL, RECORD, WAIT = 0, 1, 2
 KEYED_WRITE, READ, WRITE, ATOMIC = 3, 0, 1, 2
 RES_NAMES = ["scratch", "prim", "geoset", "samples", "segslots", "colors", "accum", "caller_segments"]
 KNAMES = ["prep", "super_cull", "tile_cull", "sky", "chain", "accum", "order", "render", "reduce"]
+REGIONS = ["mask", "pixMask", "weight", "order", "geoList", "superMask", "pixItem", "geoColor"]  # rtc_plan.h Buf
 N_EVENTS = 5 + 2 * 8
 EV_FRAME, EV_GEOMETRY = 3 + 16, 4 + 16
 
@@ -132,7 +133,18 @@ class Scenario:
             self.accesses.append((o, res, acc, ident, lo, hi, key, self.n, k))
         self.n += 1
         self.last_ops = [tuple(int(v) for v in self.ops[4 * i: 4 * i + 4]) for i in range(nops)]
+        # the last launch's scratch footprint rows, in op order: (op clock, kernel, access, lo, hi)
+        self.last_scratch = [(*kernel_ops[int(r[0])], int(r[2]), int(r[4]), int(r[5])) for r in fps[:-1] if int(r[1]) == 0]
         return {"slot": int(info[2]), "alt": bool(info[3]), "overlap": bool(info[4]), "offset": int(info[5])}
+
+    def regions(self):
+        """The last launch's slot and bound scratch regions (rtc_plan_sim_regions)."""
+        rows = (C.c_ulonglong * 30)()
+        n = self.L.rtc_plan_sim_regions(self.h, rows, 10)
+        assert n >= 2, n
+        r = [[int(v) for v in rows[3 * i: 3 * i + 3]] for i in range(n)]
+        return {"slot_offset": r[0][0], "slot_bytes": r[0][1], "scratch_need": r[0][2], "scratch_cap": r[1][0],
+                "bound": {REGIONS[i]: (lo, lo + size) for i, lo, size in r[2:]}}
 
     def kernel_order(self):
         """The last launch's kernels in enqueue order, as (name, stream)."""
@@ -199,15 +211,13 @@ def _random_launch(rng, shape):
     return _desc(W, H, rng.choice([1, 16, 64]), r * (band or 1), G, band, flags)
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_random_launch_sequences_are_race_free(seed):
-    """Thousands of launches: 50 random sequences of 24 launches per seed, each on its own scene handle: frame sizes from
-    256x256 to 4K (so the scratch is regrown and launches of different sizes are in flight together), shares of 1-8
-    ranks in rows or bands of 8, pipelined or joined, three Color buffers, cameras and environments that change, counting
-    launches, caller stream switches (the null stream included).  No unordered pair of conflicting kernels."""
+def _random_sequences(seed, after_launch=lambda sc: None):
+    """50 random sequences of 24 launches, each on its own scene handle: frame sizes from 256x256 to 4K (so the scratch is
+    regrown and launches of different sizes are in flight together), shares of 1-8 ranks in rows or bands of 8, pipelined
+    or joined, three Color buffers, cameras and environments that change, counting launches, caller stream switches (the
+    null stream included).  Yields each sequence's Scenario once its launches are planned."""
     rng = random.Random(1000 + seed)
     shapes = [(1920, 1080), (3840, 2160), (640, 360), (256, 256), (1000, 700)]
-    total = 0
     for _ in range(50):
         sc = Scenario(rng.choice([12, 120, 300, 5208]))
         streams = [rng.choice([0, 0x7f001000, 0x7f002000])]
@@ -223,12 +233,104 @@ def test_random_launch_sequences_are_race_free(seed):
                 colors = rng.choice([0x1000, 0x2000, 0x3000])
                 accum = rng.choice([0, 0, 0, 0x9000 + colors])
                 sc.launch(d, rng.choice(streams), colors, accum, seg, rng.choice(CAMS), rng.choice(ENVS))
-                total += 1
-            hz = sc.hazards()
-            assert not hz, f"unordered conflicting kernels: {hz}"
+                after_launch(sc)
+            yield sc
         finally:
             sc.close()
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_launch_sequences_are_race_free(seed):
+    """Thousands of launches (_random_sequences): no unordered pair of conflicting kernels."""
+    total = 0
+    for sc in _random_sequences(seed):
+        total += sc.n
+        hz = sc.hazards()
+        assert not hz, f"unordered conflicting kernels: {hz}"
     assert total == 50 * 24
+
+
+def _check_bound_regions(sc):
+    """The last launch's footprints against the scratch regions it binds (the regions the executor takes its pointers
+    from): the planner's buffer table, the bindings and the footprint rows describe the same bytes."""
+    g = sc.regions()
+    bound = g["bound"]
+    slot = (g["slot_offset"], g["slot_offset"] + g["slot_bytes"])
+    spans = sorted(bound.values())
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), f"bound regions overlap: {bound}"
+    assert all(slot[0] <= lo <= hi <= slot[1] for lo, hi in spans), f"a region leaves the slot {slot}: {bound}"
+    # the slot lies inside the scratch: the bytes this launch needs, unless an earlier launch allocated more (slots are
+    # spaced by the allocation's slot size, so a smaller launch's slot h starts past its own h slot sizes)
+    assert g["scratch_need"] <= g["scratch_cap"]
+    assert slot[1] <= g["scratch_cap"], (slot, g)
+    if g["scratch_cap"] == g["scratch_need"]:
+        assert slot[1] <= g["scratch_need"]
+    writers, reads = {}, []
+    for o, k, acc, lo, hi in sc.last_scratch:
+        inside = [name for name, (rlo, rhi) in bound.items() if rlo <= lo and hi <= rhi]
+        assert len(inside) == 1, f"{KNAMES[k]}'s scratch range [{lo}, {hi}) lies in the bound regions {inside} of {bound}"
+        if acc == READ:
+            reads.append((o, k, inside[0]))
+        else:
+            writers.setdefault(inside[0], []).append(o)
+    for name in bound:  # a buffer the executor binds that no footprint row declares: a forgotten row
+        assert name in writers, f"no kernel of the launch declares that it writes the bound region {name}"
+    for o, k, name in reads:
+        assert any(StreamModel.before(w, o) for w in writers[name]), \
+            f"{KNAMES[k]} reads {name}, which no earlier kernel of the launch writes"
+    return g
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_footprints_match_bound_regions(seed):
+    """Over the same random sequences: every launch's bound scratch regions are disjoint and inside its slot, the slot
+    inside the scratch; every scratch footprint row lies inside exactly one bound region (none in an unbound region or
+    in padding); every bound region has a kernel that writes it, and every read follows a write of the same launch."""
+    checked = [0]
+
+    def check(sc):
+        checked[0] += bool(_check_bound_regions(sc)["bound"])
+
+    for _ in _random_sequences(seed, check):
+        pass
+    assert checked[0] > 1000  # (brute-force launches bind no scratch)
+
+
+def test_sphere_split_and_no_reorder_launches_match_bound_regions():
+    """The same checks for one sphere-split launch and one RTC_F_NO_REORDER launch (whose render kernel gets no order
+    although rtc_order_blocks writes the bound region)."""
+    sc = Scenario(120)
+    try:
+        assert sc.L.rtc_plan_sim_set_spheres(sc.h, 5, 1) == 0
+        sc.launch(_desc(1920, 1080, 64, 0, 1, 0, OVERLAP), 0x7f001000, 0x1000, 0, False, CAMS[0], ENVS[0])
+        assert "chain" in [k for k, _ in sc.kernel_order()]
+        assert set(_check_bound_regions(sc)["bound"]) == {"mask", "pixMask", "weight", "geoList", "superMask"}
+        sc.launch(_desc(1920, 1080, 64, 0, 1, 0, rt.RTC_F_NO_REORDER), 0x7f001000, 0x1000, 0, True, CAMS[0], ENVS[0])
+        assert [k for k, _ in sc.kernel_order()][-3:] == ["order", "render", "reduce"]
+        assert set(_check_bound_regions(sc)["bound"]) == {"mask", "pixMask", "weight", "order", "superMask"}
+    finally:
+        sc.close()
+
+
+def test_super_cull_writes_only_the_superblock_masks():
+    """The drift the buffer table ended: rtc_super_cull was declared to write from the superblock masks to the slot's end,
+    which since the merged sky pass holds pixItem and geoColor; it writes superX * superY * maskWords words.  A 1080p 1/4
+    share (more than kSuperCullPixels pixels, merged sky pass): the declared write is the superMask region alone."""
+    sc = Scenario(120)
+    try:
+        sc.launch(_desc(1920, 1080, 64, 1, 4, 0, OVERLAP), 0x7f001000, 0x1000, 0, False, CAMS[0], ENVS[0])
+        ks = [k for k, _ in sc.kernel_order()]
+        assert "super_cull" in ks and ks.index("chain") < ks.index("sky")  # super cull, merged
+        bound = _check_bound_regions(sc)["bound"]
+        assert {"superMask", "pixItem", "geoColor"} <= set(bound)
+        wrote = [(lo, hi) for _, k, acc, lo, hi in sc.last_scratch if KNAMES[k] == "super_cull" and acc == WRITE]
+        assert wrote == [bound["superMask"]]
+        words = ((1920 + 63) // 64) * ((270 + 63) // 64) * ((120 + 63) // 64)
+        assert wrote[0][1] - wrote[0][0] == 8 * words
+        for other in ("pixItem", "geoColor"):
+            assert wrote[0][1] <= bound[other][0] or bound[other][1] <= wrote[0][0]
+    finally:
+        sc.close()
 
 
 def _band_share_sequence(legacy):
