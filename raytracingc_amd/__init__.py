@@ -437,15 +437,27 @@ def getEnvironmentLight(rays: np.ndarray, scenes: np.ndarray) -> np.ndarray:
     return out
 
 
-def sun_vanish_probe(rays: np.ndarray, scenes: np.ndarray):
-    """The sky kernel's per-pixel sun skip on the GPU: (vanish int32 [n], environment float32 [n, 3] evaluated with it)."""
+def sky_miss_probe(rays: np.ndarray, scene, spp: int = 1):
+    """The sky kernel's per-pixel sun skip on the GPU for one scene, with the limit and gating a launch computes on the
+    host: (vanish int32 [n], environment float32 [n, 3] evaluated with it, the sky kernel's pixel sum float32 [n, 3] of spp
+    camera-ray misses)."""
     r = np.ascontiguousarray(rays, RAY_DT)
-    s = np.ascontiguousarray(scenes, SCENE_DT)
+    s = np.ascontiguousarray(scene, SCENE_DT).reshape(1)
     n = len(r)
     v = np.zeros(n, np.int32)
     out = np.zeros((n, 3), np.float32)
-    check(lib().rtc_probe_sun_vanish(_ptr(r), _ptr(s), n, _ptr(v), _ptr(out)), "rtc_probe_sun_vanish")
-    return v, out
+    acc = np.zeros((n, 3), np.float32)
+    check(lib().rtc_probe_sun_vanish(_ptr(r), _ptr(s), n, spp, _ptr(v), _ptr(out), _ptr(acc)), "rtc_probe_sun_vanish")
+    return v, out, acc
+
+
+def sun_vanish_probe(rays: np.ndarray, scenes: np.ndarray):
+    """sky_miss_probe's (vanish, environment) for one scene, given once or once per ray (the probe runs one scene per
+    launch, as a render does)."""
+    s = np.ascontiguousarray(scenes, SCENE_DT).reshape(-1)
+    if len(s) == 0 or s.tobytes() != s[:1].tobytes() * len(s):  # (bytes: a NaN intensity equals itself)
+        raise ValueError("sun_vanish_probe: one scene per call")
+    return sky_miss_probe(rays, s[0], 1)[:2]
 
 
 def env_vanish_limit(scene) -> float:

@@ -230,7 +230,7 @@ def lib() -> C.CDLL:
     L.rtc_probe_random.argtypes = [vp, sz, ip, vp, vp, vp]
     L.rtc_probe_cluster_bound.argtypes = [vp, ip, vp, sz, vp]
     if hasattr(L, "rtc_probe_sun_vanish"):  # (absent from libraries of earlier rounds loaded for A/B timing)
-        L.rtc_probe_sun_vanish.argtypes = [vp, vp, sz, vp, vp]
+        L.rtc_probe_sun_vanish.argtypes = [vp, vp, sz, ip, vp, vp, vp]
         L.rtc_env_vanish_limit.argtypes = [vp, vp]
     _lib = L
     return L

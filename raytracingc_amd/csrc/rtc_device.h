@@ -279,14 +279,22 @@ __host__ __device__ __forceinline__ bool env_sun_skippable(float focus, float in
  * zenith colours >= m > 0, each component of lerp(ground, lerp(horizon, zenith, a), b) = g (1 - b) + s b (a, b in [0, 1];
  * fl(1 - b) >= (1 - b)(1 - u), each product and sum rounded) is >= m (1 - u)^6, so its exponent is at least
  * E = floor(log2(m (1 - 2^-20))) and the spacing above it at least 2^(E - 23): with H = 2^(E - 24), a sun term
- * 0 <= sv < H leaves every component's sum e + sv == e (round to nearest).  sv = fl(powf(x, focus) * intensity) for
- * sunMask = 1, and glibc's powf is exp2 of the double ylogx = focus * log2(x) it computes (powf_log2 and the same product:
- * the bits sun_vanishes compares) with a relative error below 2^-23 (its exp2 polynomial ~2^-30, the float rounding
- * 2^-24); with the product's rounding sv <= 2^ylogx * intensity * (1 + 2^-22).  So ylogx < log2(H / intensity) - 1e-5
- * (env_vanish_limit, on the host in double) proves sv < H.  Required: focus > 0 and finite (sunSkip), intensity > 0 and
- * finite, x a normal float in (0, 1), every colour component in [2^-60, 2^60] (no product underflows or overflows; else
- * the limit is -inf).  Skipping the powf then is the sunKnown skip of a value known to vanish (tests/test_gpu_parity.py
- * whole frames, tests/test_sun_vanish.py the bound against the oracle's environment on every tested direction). */
+ * 0 <= sv < H leaves every component's sum e + sv == e (round to nearest; sv == H would be a tie, which moves an e with
+ * an odd mantissa).  sv = fl(p * intensity) for sunMask = 1, where p is powf's float result, and glibc's powf is exp2 of
+ * the double ylogx = focus * log2(x) it computes (powf_log2 and the same product: the bits sun_vanishes compares), its
+ * exp2 polynomial within ~2^-30, rounded to float.  That rounding is relative (2^-24) only while the result is a normal
+ * float; a subnormal result is rounded absolutely, by up to 2^-150 (and results below 2^-150 become 0).  So, for every
+ * result, p <= 2^ylogx (1 + 2^-23) + 2^-150.  With L = log2(H / intensity) and ylogx < L - 1e-5:
+ *     p * intensity < H 2^-1e-5 (1 + 2^-23) + 2^-150 intensity,
+ * and 2^-1e-5 (1 + 2^-23)(1 + 2^-24) < 1 - 6.7e-6 leaves room for an absolute term of up to 6.7e-6 H > 2^-18 H beside the
+ * product's own rounding (relative 2^-24; H >= 2^-85, so sv near H is normal).  The absolute term fits when
+ * 2^-150 intensity <= 2^-18 H, that is L >= -132: then sv < H.  Below that (powf's results near the limit subnormal or
+ * nearly so, the 2^-150 no longer negligible against H / intensity) the limit is -inf: with L = -148 the term was
+ * exactly H on most admitted rays.  env_vanish_limit (on the host in double) returns L - 1e-5.  Required: focus > 0 and
+ * finite (sunSkip), intensity > 0 and finite, x a normal float in (0, 1), every colour component in [2^-60, 2^60] (no
+ * product underflows or overflows), L >= -132; else the limit is -inf.  Skipping the powf then is the sunKnown skip of a
+ * value known to vanish (tests/test_gpu_parity.py and tests/test_gpu_env_frames.py whole frames, tests/test_sun_vanish.py
+ * the bound against the oracle's environment on every tested direction, scenes at L = -125 .. -149 included). */
 __host__ __device__ inline double env_vanish_limit(float focus, float intensity, const float col[9])
 {
     if (!(focus > 0.f) || !(intensity > 0.f) || !(focus < 3.0e38f) || !(intensity < 3.0e38f))
@@ -300,7 +308,10 @@ __host__ __device__ inline double env_vanish_limit(float focus, float intensity,
     int E = 0;
     (void)frexp(m * (1.0 - 0x1p-20), &E); /* m (1 - 2^-20) = f 2^E, f in [0.5, 1): floor(log2) = E - 1 */
     const double H = ldexp(1.0, (E - 1) - 24);
-    return log2(H / (double)intensity) - 1e-5;
+    const double L = log2(H / (double)intensity);
+    if (!(L >= -132.0)) /* powf's absolute rounding error of a subnormal result, 2^-150, stays below 2^-18 H / intensity */
+        return -__builtin_inf();
+    return L - 1e-5;
 }
 __device__ __forceinline__ bool sun_vanishes(V3 dir, const EnvParams &s)
 {

@@ -200,6 +200,28 @@ __device__ __forceinline__ bool cluster_culled(V3 pos, V3 dir, float rho, float 
 
 __host__ __device__ static inline V3 v3(vec3 v) { return V3{v.x, v.y, v.z}; }
 
+#ifndef RTC_SUN_VANISH
+#define RTC_SUN_VANISH 1 /* (A/B switch, round 6) */
+#endif
+/* What the kernels read of a Scene's environment, built on the host (the powf tables are attached by each workgroup,
+ * PowTablesLds): the one construction of a launch's (render_params) and of the sun-skip probe's (rtc_probe_sun_vanish), so
+ * that the probe tests the limit and the gating the sky kernel runs with. */
+static inline EnvParams env_of(const Scene &s)
+{
+    EnvParams e{};
+    e.sun = v3(s.normalizedSunDirection);
+    e.horizon = v3(s.skyColorHorizon);
+    e.zenith = v3(s.skyColorZenith);
+    e.ground = v3(s.groundColor);
+    e.focus = s.sunFocus;
+    e.intensity = s.sunIntensity;
+    e.sunSkip = env_sun_skippable(e.focus, e.intensity);
+    const float col[9] = {e.ground.x, e.ground.y, e.ground.z, e.horizon.x, e.horizon.y, e.horizon.z,
+                          e.zenith.x, e.zenith.y, e.zenith.z};
+    e.vanishLim = RTC_SUN_VANISH && e.sunSkip ? env_vanish_limit(e.focus, e.intensity, col) : -__builtin_inf();
+    return e;
+}
+
 /* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB: 393,216 triangles); larger
  * scenes render without it, and without the geometry kernel whose occupancy bounce_hit_share chooses */
 constexpr int kMaxCullMaskWords = 6144;

@@ -67,16 +67,12 @@ __global__ void probe_env_kernel(const Ray *rays, const Scene *scenes, size_t n,
     out[i] = vec3{c.x, c.y, c.z};
 }
 
-__host__ __device__ static double rtc_env_vanish_limit_of(const Scene &s)
-{
-    const float col[9] = {s.groundColor.x,     s.groundColor.y,     s.groundColor.z,
-                          s.skyColorHorizon.x, s.skyColorHorizon.y, s.skyColorHorizon.z,
-                          s.skyColorZenith.x,  s.skyColorZenith.y,  s.skyColorZenith.z};
-    return env_vanish_limit(s.sunFocus, s.sunIntensity, col);
-}
-
-/* the sky kernel's per-pixel sun skip (rtc_device.h sun_vanishes) and the environment evaluated with it */
-__global__ void probe_vanish_kernel(const Ray *rays, const Scene *scenes, size_t n, int *vanish, vec3 *out)
+/* the sky kernel's per-pixel sun skip (rtc_device.h sun_vanishes) with the environment a launch would carry (env_of, built
+ * on the host: its limit and gating, one scene for every lane as in a launch, so the wave-uniform branches of
+ * environment_t are a render's): the flag, the environment evaluated with it, and the sky kernel's pixel sum of spp samples
+ * of environment_miss_term (rtc_render_sky_rows: acc = acc + m * (1 / spp) from +0) */
+__global__ void probe_vanish_kernel(const Ray *rays, EnvParams env, size_t n, int spp, float invSpp, int *vanish,
+                                    vec3 *out, vec3 *sum)
 {
     __shared__ PowTablesLds sPow;
     sPow.fill(threadIdx.x);
@@ -84,22 +80,17 @@ __global__ void probe_vanish_kernel(const Ray *rays, const Scene *scenes, size_t
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const Scene s = scenes[i];
-    EnvParams e{};
+    EnvParams e = env;
     sPow.attach(e);
-    e.sun = v3(s.normalizedSunDirection);
-    e.horizon = v3(s.skyColorHorizon);
-    e.zenith = v3(s.skyColorZenith);
-    e.ground = v3(s.groundColor);
-    e.focus = s.sunFocus;
-    e.intensity = s.sunIntensity;
-    e.sunSkip = env_sun_skippable(e.focus, e.intensity);
-    e.vanishLim = rtc_env_vanish_limit_of(s);
     const V3 d = v3(rays[i].dir);
     const bool v = sun_vanishes(d, e);
     vanish[i] = v ? 1 : 0;
     const V3 c = environment_t<false>(d, e, v);
     out[i] = vec3{c.x, c.y, c.z};
+    V3 acc{0.f, 0.f, 0.f};
+    for (int s = 0; s < spp; ++s)
+        acc = add(acc, mul(environment_miss_term(d, e, v), invSpp));
+    sum[i] = vec3{acc.x, acc.y, acc.z};
 }
 
 __global__ void probe_random_kernel(const unsigned *seeds, size_t n, int draws, float *uni, float *nrm, vec3 *dirs)
@@ -270,34 +261,39 @@ extern "C" int rtc_probe_environment(const Ray *rays, const Scene *scenes, size_
     return 0;
 }
 
-extern "C" int rtc_probe_sun_vanish(const Ray *rays, const Scene *scenes, size_t n, int *vanish, vec3 *out)
+extern "C" int rtc_probe_sun_vanish(const Ray *rays, const Scene *scene, size_t n, int spp, int *vanish, vec3 *out,
+                                    vec3 *sum)
 {
+    if (!scene || spp < 0 || (n > 0 && (!rays || !vanish || !out || !sum)))
+        return rtc_fail(RTC_EINVAL, "rtc_probe_sun_vanish: bad argument");
     if (int rc = probe_prelude())
         return rc;
     if (n == 0)
         return 0;
     Scratch sc;
     Ray *dr;
-    Scene *ds;
     int *dv;
-    vec3 *dout;
+    vec3 *dout, *dsum;
     ALLOC_IN(dr, rays, n * sizeof(Ray));
-    ALLOC_IN(ds, scenes, n * sizeof(Scene));
     ALLOC_OUT(dv, n * sizeof(int));
     ALLOC_OUT(dout, n * sizeof(vec3));
-    hipLaunchKernelGGL(probe_vanish_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, dr, ds, n, dv, dout);
+    ALLOC_OUT(dsum, n * sizeof(vec3));
+    const float invSpp = spp > 0 ? (float)(1. / (double)spp) : 0.f; /* as a launch's (render_params) */
+    hipLaunchKernelGGL(probe_vanish_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, dr, env_of(*scene), n, spp,
+                       invSpp, dv, dout, dsum);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(vanish, dv, n * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out, dout, n * sizeof(vec3), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sum, dsum, n * sizeof(vec3), hipMemcpyDeviceToHost));
     return 0;
 }
 
-/* the limit sun_vanishes compares with (host code: no device needed) */
+/* the limit sun_vanishes compares with in a launch of this scene (host code: no device needed) */
 extern "C" int rtc_env_vanish_limit(const Scene *scene, double *limit)
 {
     if (!scene || !limit)
         return RTC_EINVAL;
-    *limit = rtc_env_vanish_limit_of(*scene);
+    *limit = env_of(*scene).vanishLim;
     return 0;
 }
 

@@ -1485,9 +1485,6 @@ static_assert(sizeof(SampleSlot) == rtcplan::kSampleSlotBytes, "the planner size
  * pipelined, prepare, cull and run their geometry kernel on the two cull streams.  Round 4 raised it
  * from 400 k to 600 k pixels so that the 1080p 1/4 share (518 k) is one: 0.137 -> 0.117 ms per pipelined share; the
  * 1/2 share and the 4K 1/8 share (1.04 M) measured no better that way (tools/scale_probe.py, profiles/r04_y_*) */
-#ifndef RTC_SUN_VANISH
-#define RTC_SUN_VANISH 1 /* (A/B switch, round 6) */
-#endif
 #ifndef RTC_SKY_MERGE
 #define RTC_SKY_MERGE 1 /* (A/B switch, round 6) */
 #endif
@@ -2520,23 +2517,6 @@ static hipError_t launch_stop(void (*k)(K...), dim3 g, dim3 b, size_t sh, hipStr
     hipLaunchKernelGGL(k, g, b, sh, st, args...);
     return hipGetLastError();
 }
-
-static EnvParams env_of(const Scene &s)
-{
-    EnvParams e{};
-    e.sun = V3{s.normalizedSunDirection.x, s.normalizedSunDirection.y, s.normalizedSunDirection.z};
-    e.horizon = V3{s.skyColorHorizon.x, s.skyColorHorizon.y, s.skyColorHorizon.z};
-    e.zenith = V3{s.skyColorZenith.x, s.skyColorZenith.y, s.skyColorZenith.z};
-    e.ground = V3{s.groundColor.x, s.groundColor.y, s.groundColor.z};
-    e.focus = s.sunFocus;
-    e.intensity = s.sunIntensity;
-    e.sunSkip = env_sun_skippable(e.focus, e.intensity);
-    const float col[9] = {e.ground.x, e.ground.y, e.ground.z, e.horizon.x, e.horizon.y, e.horizon.z,
-                          e.zenith.x, e.zenith.y, e.zenith.z};
-    e.vanishLim = RTC_SUN_VANISH && e.sunSkip ? env_vanish_limit(e.focus, e.intensity, col) : -INFINITY;
-    return e;
-}
-
 
 /* The sphere split's two kernels (rtc_tile_cull_sph<true>, rtc_render_chain<..., SPHERES>), launched from the end of
  * this file: the instantiations are emitted in the order of their first use, so these come after every kernel of the

@@ -13,11 +13,12 @@ import numpy as np
 import pytest
 
 from conftest import load_tris, render_golden, scene_spheres, setup_from_flags
+from env_edge_scenes import primary_rays
 from sphere_scenes import closing_sphere, open5, open5_padded, tie_scene
 
 import oracle.binding as orc
 import raytracingc_amd as rt
-from raytracingc_amd._abi import RAY_DT, RtcRenderDesc
+from raytracingc_amd._abi import RtcRenderDesc
 from raytracingc_amd.distributed import band_rows, rank_config, rows_per_rank
 
 pytestmark = pytest.mark.gpu
@@ -140,22 +141,6 @@ def test_path_taken(gpu_available):
 
 
 # ---- the test scene is not vacuous ------------------------------------------------------------------------------
-def _primary_rays(cam, W, H):
-    """main.c:88-94 in float32 (the renderer's primary_dir; used here only to classify pixels)."""
-    f = np.float32
-    v = lambda a: np.array([a.x, a.y, a.z], f)
-    xs, ys = np.meshgrid(np.arange(W), np.arange(H))
-    dx = ((xs - W // 2).astype(f) / f(H // 2))[..., None]
-    dy = ((ys - H // 2).astype(f) / f(H // 2))[..., None]
-    d = (v(cam.ex) * dx + v(cam.ey) * dy + v(cam.ez) * f(cam.fov)).astype(f)
-    d = d * (f(1) / np.sqrt((d * d).sum(-1, dtype=f)))[..., None]
-    rays = np.zeros(W * H, RAY_DT)
-    for k, c in enumerate("xyz"):
-        rays["pos"][c] = v(cam.origin)[k]
-        rays["dir"][c] = d[..., k].reshape(-1)
-    return rays
-
-
 def test_open5_covers_every_case(gpu_available):
     """The conditions that keep the open5 tests from passing vacuously, on the oracle at 96x54.  From debug-bounce
     renders of the parts (maxBounce 1: a pixel is white where its primary ray hits the part): each of spheres 0-3 covers
@@ -174,7 +159,7 @@ def test_open5_covers_every_case(gpu_available):
     parts = [part(None, sph[i:i + 1]) for i in range(len(sph))] + [part(tris, None)]
     print(f"open5 96x54 coverage of the parts: spheres {parts[:5]}, triangles {parts[5]}")
     assert all(c >= 10 for c in parts[:4]) and parts[4] == 0 and parts[5] >= 100
-    rays = _primary_rays(cam, W, H)
+    rays = primary_rays(cam, W, H)
     n = len(rays)
     best = np.full(n, 999999.0, np.float32)
     owner = np.full(n, -1)
