@@ -361,6 +361,16 @@ int rtc_env_vanish_limit(const Scene *scene, double *limit);
  * calls unreachable from the ray's origin (0 when sound), [6] (ray, triangle) pairs it calls so. */
 int rtc_probe_cluster_bound(const Triangle *tris, int triCount, const Ray *rays, size_t n,
                             unsigned long long counts[7]);
+/* The split launch's item records (no reference counterpart; main.c:88-94 is the ray each must carry): uploads the
+ * scene to the current device, runs the preparation and the culls of the launch `d` as rtc_render_rows_async would (no
+ * render kernel) and copies back counts[16] = the entries of the 16 geometry-pixel sub-lists, info[4] = {entries a
+ * sub-list can hold, 8x8 tiles per launch row, tiles, 1 when the launch has more than 65,535 columns or launch rows},
+ * records = the sub-lists' records one after the other, 4 dwords each: x | launch row << 16 (tile * 64 + bit in such a wide
+ * launch) and the float bits of the pixel's primary direction, and pixMask = per tile its pixels with a primary candidate
+ * (bit = (row % 8) * 8 + x % 8).  RTC_EINVAL when the launch is not a split launch or an output is too small. */
+int rtc_probe_item_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, const Scene *scene,
+                           const RtcCamera *cam, const RtcRenderDesc *d, int counts[16], int info[4],
+                           unsigned int *records, size_t maxRecords, unsigned long long *pixMask, size_t maxTiles);
 
 #ifdef __cplusplus
 }

@@ -491,3 +491,22 @@ def cluster_bound_probe(tris: np.ndarray, rays: np.ndarray) -> dict:
     return {"violations": int(c[0]), "culled": int(c[1]), "tests": int(c[2]), "hits": int(c[3]),
             "max_excess": float(np.array([c[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
             "reach_violations": int(c[5]), "unreachable": int(c[6])}
+
+
+def item_records_probe(tris, spheres, scene: Scene, cam: RtcCamera, cfg: RenderConfig) -> dict:
+    """The split launch's item records for the launch `cfg` (rtc_probe_item_records: its preparation and culls, no render
+    kernel): counts [16] the sub-lists' entries, records uint32 [n, 4] (dword 0 = x | launch row << 16, or tile * 64 + bit
+    when `wide`; dwords 1-3 the float bits of the pixel's primary direction), pix_mask uint64 [tiles], and the launch's
+    cap (entries a sub-list holds), tiles_x, tiles, wide."""
+    t, nt = _arr(tris, TRIANGLE_DT)
+    s, ns = _arr(spheres, SPHERE_DT)
+    rows = cfg.rows()
+    tiles = 4 * ((cfg.width + 15) // 16) * ((rows + 15) // 16)
+    counts, info = np.zeros(16, np.int32), np.zeros(4, np.int32)
+    rec = np.zeros((tiles * 64, 4), np.uint32)
+    pm = np.zeros(tiles, np.uint64)
+    d = cfg.desc()
+    check(lib().rtc_probe_item_records(_ptr(t), nt, _ptr(s), ns, C.byref(scene), C.byref(cam), C.byref(d), _ptr(counts),
+                                       _ptr(info), _ptr(rec), len(rec), _ptr(pm), len(pm)), "rtc_probe_item_records")
+    return {"counts": counts, "records": rec[: int(counts.sum())].copy(), "pix_mask": pm, "cap": int(info[0]),
+            "tiles_x": int(info[1]), "tiles": int(info[2]), "wide": bool(info[3])}

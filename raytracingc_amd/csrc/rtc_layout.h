@@ -98,10 +98,11 @@ constexpr double kWgsHitShare = 0.15;
 /* rtc_render_chain's geometry-pixel sub-lists: kGeoLists counters, kGeoCountStride ints (one 128-B line) apart; a ring
  * of kGeoRing counter sets of kGeoSetInts ints (see RtcDeviceScene::geoCounts) */
 constexpr int kGeoLists = 16, kGeoCountStride = 32;
+constexpr int kItemRecDwords = 4; /* a geometry pixel's item record (item_record, rtc_render.hip) */
 constexpr int kGeoRing = 16, kGeoSetInts = kGeoLists * kGeoCountStride;
 static_assert(kGeoSetInts >= kGeoLists * kGeoCountStride, "a counter set holds every sub-list counter");
 static_assert(kSkySlots == rtcplan::kSlots && kGeoRing == rtcplan::kGeoRing && kGeoLists == rtcplan::kGeoLists &&
-                  kGeoCountStride == rtcplan::kGeoCountStride,
+                  kGeoCountStride == rtcplan::kGeoCountStride && kItemRecDwords * 4 == rtcplan::kItemRecordBytes,
               "the planner's slot and counter-set layout is the device's");
 struct RtcDeviceScene {
     int device;
@@ -159,6 +160,20 @@ struct RtcDeviceScene {
     bool timing; /* record them (rtc_scene_set_timing; off by default: each record costs the launch a few us) */
     bool timed;  /* the last launch was a split launch that recorded them */
 };
+
+/* A split launch's geometry-pixel lists once its culls have run, for rtc_probe_item_records: the launch's preparation,
+ * superblock and tile culls on the null stream and none of its render kernels (rtc_render.hip); device pointers into the
+ * launch's counter set and scratch slot, valid until the scene's next launch */
+struct RtcCullItems {
+    const int *geoCount;      /* sub-list l's entries: geoCount[l * kGeoCountStride] (clamp to geoCap) */
+    const unsigned *geoList;  /* sub-list l's records from l * geoCap * kItemRecDwords */
+    const unsigned long long *pixMask;
+    int geoCap, tilesX;
+    size_t tiles;
+    int wide;                 /* the records keep tile * 64 + bit (RenderParams::wideItems) */
+};
+int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                   void *dColors, RtcCullItems *items);
 
 /* True when the bounce ray (pos, dir) provably cannot hit any triangle of cluster K (see DevCluster): the
  * half-line's distance to the ball centre exceeds T >= r + eps.  rho = |dir|_1 >= |dir| bounds the eps terms;

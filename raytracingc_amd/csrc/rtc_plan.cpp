@@ -34,16 +34,17 @@ struct Emitter {
  * budgeted in full in the slot size, so the slot always holds the aligned offsets. */
 void layout_slot(Plan &p, size_t maskWords)
 {
-    const size_t lists = (size_t)kGeoLists * p.geoCap * 4, counters = (size_t)kGeoLists * kGeoCountStride * 4;
+    /* one entry per pixel at worst: an item record per entry of the lists, a colour word per entry of geoColor */
+    const size_t entries = (size_t)kGeoLists * p.geoCap, counters = (size_t)kGeoLists * kGeoCountStride * 4;
     const struct { size_t used, align, padAfter; } rows[kScratchRegions] = {
         /* kBufMask      */ {p.tiles * maskWords * 8, 1, 0},
         /* kBufPixMask   */ {p.tiles * 8, 1, 0},
         /* kBufWeight    */ {p.blocks * 4, 1, 0},
         /* kBufOrder     */ {(p.blocks + 4) * 4, 1, counters}, /* historical padding: the sub-list counters' old place */
-        /* kBufGeoList   */ {lists, 1, 0},
+        /* kBufGeoList   */ {entries * kItemRecordBytes, kItemRecordBytes, 0}, /* (written as whole 16-B records) */
         /* kBufSuperMask */ {(size_t)p.superX * p.superY * maskWords * 8, 8, 0},
         /* kBufPixItem   */ {p.tiles * 64 * 4, 256, 0},
-        /* kBufGeoColor  */ {lists, 1, p.tiles * 4},           /* historical padding: an int per tile, long unused */
+        /* kBufGeoColor  */ {entries * 4, 1, p.tiles * 4},           /* historical padding: an int per tile, long unused */
     };
     size_t off = 0, budget = 0;
     for (int b = 0; b < kScratchRegions; ++b) {
@@ -122,6 +123,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     p.superY = (p.gridY + 3) / 4;
     p.superCull = p.cull && px > kSuperCullPixels && r.maskWords > 0;
     p.geoCap = (int)((p.tiles + kGeoLists - 1) / kGeoLists * 64); /* sub-list l: the tiles t = l mod kGeoLists */
+    p.wideItems = r.width > kItemCoordMax || r.rows > kItemCoordMax;
     /* RTC_F_OVERLAP: the sky pass is not joined into the caller's stream (a launch that counts segments joins: the
      * reduction reads the sky pass's counters) */
     p.overlap = (r.flags & RTC_F_OVERLAP) && p.fused && !r.segments;

@@ -29,6 +29,10 @@ constexpr int kSlots = 8;     /* scratch slots the pipelined launches cycle thro
 constexpr int kGeoRing = 16;  /* geometry-pixel counter sets (one per split launch, a ring) */
 constexpr int kGeoLists = 16; /* sub-lists per counter set */
 constexpr int kGeoCountStride = 32;
+/* a geometry pixel's item record in kBufGeoList: dword 0 = x | launch row << 16 (a launch of more than kItemCoordMax
+ * columns or launch rows, Plan::wideItems: tile * 64 + bit), dwords 1-3 = the bits of its primary direction */
+constexpr size_t kItemRecordBytes = 16;
+constexpr int kItemCoordMax = 65535;
 constexpr size_t kInlineSumPixels = 600000; /* small shares, and the alternating cull streams' limit for whole frames */
 constexpr size_t kSuperCullPixels = 400000; /* launches of more pixels run rtc_super_cull */
 constexpr size_t kSampleBufBudget = (size_t)2 << 30;
@@ -126,7 +130,7 @@ enum Buf : int {
     kBufPixMask,   /* per tile: its pixels with a candidate */
     kBufWeight,    /* per workgroup block: its weight (rtc_order_blocks) */
     kBufOrder,     /* launch slot -> workgroup block (one-lane-per-pixel kernel) */
-    kBufGeoList,   /* kGeoLists sub-lists of geoCap geometry pixels */
+    kBufGeoList,   /* kGeoLists sub-lists of geoCap geometry pixels' item records (kItemRecordBytes each) */
     kBufSuperMask, /* per superblock: maskWords u64 of survivors (rtc_super_cull) */
     kBufPixItem,   /* per pixel (tile * 64 + bit) of the geometry pixels: its item (merged sky pass) */
     kBufGeoColor,  /* per item: its Color bytes (merged sky pass) */
@@ -151,6 +155,7 @@ struct Plan {
     unsigned gridX, gridY, superX, superY;
     size_t blocks, tiles;
     int geoCap;
+    bool wideItems;      /* more than kItemCoordMax columns or launch rows: the records keep tile * 64 + bit */
     size_t slotBytes;    /* bytes per slot (halfBytes: what this launch needs) */
     size_t slotOffset;   /* where slot `half` starts */
     Region reg[kScratchRegions];

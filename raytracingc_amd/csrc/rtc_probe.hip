@@ -364,3 +364,53 @@ extern "C" int rtc_probe_cluster_bound(const Triangle *tris, int triCount, const
     rtc_scene_release(s);
     return rc;
 }
+
+/* The split launch's item records (rtc_render.hip item_record): uploads the scene, runs the preparation and culls of the
+ * launch `d` (rtc_cull_items) and copies back the sub-lists' counts, the records (the sub-lists one after the other) and
+ * the tiles' pixel masks */
+extern "C" int rtc_probe_item_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
+                                      const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d, int counts[16],
+                                      int info[4], unsigned *records, size_t maxRecords, unsigned long long *pixMask,
+                                      size_t maxTiles)
+{
+    static_assert(kGeoLists == 16, "counts[16]: one per sub-list");
+    if (!scene || !cam || !d || !counts || !info || !records || !pixMask || triCount < 0 || sphereCount < 0)
+        return rtc_fail(RTC_EINVAL, "rtc_probe_item_records: bad argument");
+    if (int rc = probe_prelude())
+        return rc;
+    RtcDeviceScene *s = nullptr;
+    if (int rc = rtc_scene_upload(tris, triCount, spheres, sphereCount, -1, &s))
+        return rc;
+    Scratch sc;
+    int rc = 0;
+    const auto run = [&]() -> int {
+        unsigned char *dColors = nullptr; /* (the launch's key; no kernel of the probe's writes it) */
+        HIP_TRY(sc.alloc((void **)&dColors, (size_t)d->width * (size_t)(rtc_rows_selected(d) > 0 ? rtc_rows_selected(d) : 1) * 3));
+        RtcCullItems it{};
+        if (const int r = rtc_cull_items(s, scene, cam, d, dColors, &it))
+            return r;
+        HIP_TRY(hipDeviceSynchronize());
+        int raw[kGeoSetInts];
+        HIP_TRY(hipMemcpy(raw, it.geoCount, sizeof raw, hipMemcpyDeviceToHost));
+        size_t total = 0;
+        for (int l = 0; l < kGeoLists; ++l) {
+            counts[l] = raw[l * kGeoCountStride] < it.geoCap ? raw[l * kGeoCountStride] : it.geoCap;
+            total += (size_t)counts[l];
+        }
+        info[0] = it.geoCap, info[1] = it.tilesX, info[2] = (int)it.tiles, info[3] = it.wide;
+        if (total > maxRecords || it.tiles > maxTiles)
+            return rtc_fail(RTC_EINVAL, "rtc_probe_item_records: %zu records, %zu tiles: the outputs are smaller", total,
+                            it.tiles);
+        size_t at = 0;
+        for (int l = 0; l < kGeoLists; ++l) {
+            HIP_TRY(hipMemcpy(records + at * kItemRecDwords, it.geoList + (size_t)l * it.geoCap * kItemRecDwords,
+                              (size_t)counts[l] * kItemRecDwords * 4, hipMemcpyDeviceToHost));
+            at += (size_t)counts[l];
+        }
+        HIP_TRY(hipMemcpy(pixMask, it.pixMask, it.tiles * 8, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    rc = run();
+    rtc_scene_release(s);
+    return rc;
+}

@@ -115,16 +115,17 @@ struct RenderParams {
      * superX per row of superblocks); null: rtc_tile_cull tests every triangle at level 1 */
     const unsigned long long *__restrict__ superMask;
     int superX;
-    /* rtc_render_chain's work: kGeoLists sub-lists of geometry pixels (tile*64 + bit), filled by rtc_tile_cull
-     * (tile t appends to sub-list t % kGeoLists, one atomic per tile with geometry, spread over kGeoLists
-     * counters in separate cache lines); geoCount[l * 32] = entries of sub-list l, zeroed by the previous split
-     * launch's rtc_tile_cull on the same stream, or by rtc_prep_primary */
+    /* rtc_render_chain's work: kGeoLists sub-lists of geometry pixels, one item record (kItemRecDwords dwords, see
+     * item_record) each, filled by rtc_tile_cull (tile t appends to sub-list t % kGeoLists, one atomic per tile with
+     * geometry, spread over kGeoLists counters in separate cache lines); geoCount[l * 32] = entries of sub-list l,
+     * zeroed by the previous split launch's rtc_tile_cull on the same stream, or by rtc_prep_primary */
     int *__restrict__ geoCount;
     int *__restrict__ geoCountNext; /* the next split launch's counters, zeroed by this launch's rtc_tile_cull */
-    int *__restrict__ geoList;
-    int geoCap; /* entries per sub-list */
+    unsigned *__restrict__ geoList;
+    int geoCap; /* entries (records) per sub-list */
     int cullPrio; /* rtc_tile_cull's waves at issue priority 3 (kCullPrioMinPixels) */
     int blocksX; /* 16x16 blocks per row of the launch */
+    int wideItems; /* the launch has more than 65,535 columns or launch rows: see item_record */
     /* merged sky pass (rtcplan::Plan::merge; null: none): rtc_tile_cull writes each geometry pixel's item (pixItem[tile * 64
      * + bit]), rtc_render_chain each item's Color bytes (geoColor[item], bytes 0-2), and the sky pass -- after it -- every
      * pixel's Color in whole lines */
@@ -179,14 +180,6 @@ template <typename T> __device__ __forceinline__ T kload(const T *p, int i)
  * between uses.  rtc_render_chain keeps ~60 SGPRs of launch constants (camera, environment, dimensions, pointers)
  * otherwise, and spilled 155 SGPRs to VGPR lanes (v_writelane / v_readlane in its loops).  For fields
  * read once per item, window or escaped bounce: a scalar-cache hit against a register that would have been spilled. */
-/* 0 in a vector register the compiler cannot see through: a wave-uniform address plus vzero() is read by a vector load
- * (waited for by vmcnt, in order) instead of a scalar load */
-__device__ __forceinline__ int vzero()
-{
-    int z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
 /* a dword of global memory by a global (not flat) vector load: a flat load's wait would also cover the LDS and scalar
  * loads (lgkmcnt) */
 template <typename T> __device__ __forceinline__ unsigned gload(const T *p, size_t i)
@@ -257,6 +250,17 @@ __device__ __forceinline__ PixelRay pixel_ray(const RenderParams &P, int bx, int
     px.y = launch_row_y(P, px.r);
     px.dir = primary_dir(P, px.x, px.y);
     return px;
+}
+
+/* A geometry pixel's item record, rtc_tile_cull -> rtc_render_chain (private to the two: the list has no other reader).
+ * Dword 0: x | launch row << 16; a launch with more than 65,535 columns or launch rows (P.wideItems) keeps tile * 64 + bit
+ * there instead, which the chain kernel decodes by a divide.  Dwords 1-3: the bits of the pixel's primary direction
+ * (main.c:88-94, formed once per pixel as in the reference), which the cull's lane holds already: the chain kernel's
+ * wave does not rebuild it for 64 lanes from the camera. */
+__device__ __forceinline__ uint4 item_record(const RenderParams &P, const PixelRay &px, int tile, int bit)
+{
+    const unsigned d0 = P.wideItems ? (unsigned)(tile * 64 + bit) : (unsigned)px.x | (unsigned)px.r << 16;
+    return uint4{d0, __float_as_uint(px.dir.x), __float_as_uint(px.dir.y), __float_as_uint(px.dir.z)};
 }
 
 /* This wave's 8x8 tile in the launch (made provably wave-uniform, so tile data is scalar-loaded). */
@@ -1010,7 +1014,7 @@ __device__ __forceinline__ void tile_cull_body(const RenderParams &P, unsigned l
              * 0; a stale counter must not write past it (the readers clamp the counts to geoCap too) */
             if (((gb >> lane) & 1ull) && base + __popcll(gb) <= P.geoCap) {
                 const int pos = base + __popcll(gb & ((1ull << lane) - 1ull));
-                P.geoList[(size_t)l * P.geoCap + pos] = tile * 64 + lane;
+                ((uint4 *)P.geoList)[(size_t)l * P.geoCap + pos] = item_record(P, px, tile, lane);
                 if (P.pixItem) /* the pixel's entry: pos of sub-list l (the sky pass turns it into its item) */
                     P.pixItem[(size_t)tile * 64 + lane] = (unsigned)(pos * kGeoLists + l);
             }
@@ -2082,28 +2086,36 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
             incl += v;
     }
     const int nItems = __builtin_amdgcn_readlane(incl, kGeoLists - 1);
-    /* Prefetch (round 5): an item's list entry and its tile's first two mask words were written by the tile cull on
+    /* Prefetch (round 5): an item's record and its tile's first two mask words were written by the tile cull on
      * other XCDs, so their first reads miss this XCD's L2; read as scalar loads at the item's start they were a chain
      * of dependent misses on the critical path of every item (round-4 stamps: item setup 17 % of the waves' lifetime).
-     * Here they are VECTOR loads issued one item ahead: the next item's entry at this item's start, its tile's mask
-     * dwords (lane j < 4: dword j) at this item's first bounce iteration, once the entry is back.  Vector loads return in
-     * order and are waited for by vmcnt, so a scalar wait never completes them early.  Each lives in one register that
-     * is consumed before it is reloaded (a loop-carried copy of an in-flight load would wait for it at the copy), and
-     * neither is in flight at a loop preheader that flushes vmcnt (after the bounce loop, the walk's did). */
+     * Here they are VECTOR loads issued one item ahead: the next item's record (lane j: dword j & 3 of it, so the
+     * address differs by lane and the load is a vector one) at this item's start, its tile's mask dwords (lane j < 4:
+     * dword j) at this item's first bounce iteration, once the record is back.  Vector loads return in order and are
+     * waited for by vmcnt, so a scalar wait never completes them early.  Each lives in one register that is consumed
+     * before it is reloaded (a loop-carried copy of an in-flight load would wait for it at the copy), and neither is in
+     * flight at a loop preheader that flushes vmcnt (after the bounce loop, the walk's did). */
     const auto entry_of = [&](int it2) -> size_t {
         const int l = (int)__popcll(__ballot(lane < kGeoLists && incl <= it2));
         const int base = l ? __builtin_amdgcn_readlane(incl, l - 1) : 0;
         return (size_t)l * KARG(geoCap) + (size_t)(it2 - base);
     };
-    const auto mask_dwords = [&](int code2) -> unsigned {
-        const unsigned *mw = (const unsigned *)(KARG(tileMask) + (size_t)(code2 >> 6) * P.maskWords);
+    const auto record_dwords = [&](int it2) -> unsigned {
+        return gload(KARG(geoList), entry_of(it2) * (size_t)kItemRecDwords + (size_t)(lane & (kItemRecDwords - 1)));
+    };
+    /* the tile of a record (its dword 0, item_record) */
+    const auto record_tile = [&](unsigned d0) -> int {
+        return KARG(wideItems) ? (int)(d0 >> 6) : (int)(d0 >> 19) * (KARG(blocksX) * 2) + (int)((d0 & 0xffffu) >> 3);
+    };
+    const auto mask_dwords = [&](unsigned d0) -> unsigned {
+        const unsigned *mw = (const unsigned *)(KARG(tileMask) + (size_t)record_tile(d0) * P.maskWords);
         return lane < 2 * P.maskWords && lane < 4 ? gload(mw, (size_t)lane) : 0u;
     };
     int it = __builtin_amdgcn_readfirstlane(nextIt);
-    unsigned vc = 0, vm = 0; /* the current item's entry and mask dwords (vector registers) */
+    unsigned vc = 0, vm = 0; /* the current item's record and mask dwords (vector registers) */
     if (it < nItems) {
-        vc = gload(KARG(geoList), entry_of(it) + (size_t)vzero());
-        vm = mask_dwords(__builtin_amdgcn_readfirstlane((int)vc));
+        vc = record_dwords(it);
+        vm = mask_dwords((unsigned)__builtin_amdgcn_readfirstlane((int)vc));
     }
     if (lane == 0)
         nextIt = next_item();
@@ -2120,7 +2132,11 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
         const unsigned long long dSect = lane < kItemSects ? s_rtc_sect[threadIdx.x >> 6][item_sect_id(lane)] : 0ull;
         unsigned long long dItemTests = 0;
 #endif
-        const int code = __builtin_amdgcn_readfirstlane((int)vc);
+        const unsigned d0 = (unsigned)__builtin_amdgcn_readfirstlane((int)vc);
+        /* the pixel's primary direction (main.c:88-94), as the tile cull's lane formed it (item_record) */
+        const V3 pdir{__uint_as_float((unsigned)__builtin_amdgcn_readlane((int)vc, 1)),
+                      __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)vc, 2)),
+                      __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)vc, 3))};
         const unsigned long long m0 = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 0) |
                                       (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 1) << 32;
         const unsigned long long m1 = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 2) |
@@ -2129,23 +2145,19 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
          * the one after */
         const int itNext = __builtin_amdgcn_readfirstlane(nextIt);
         if (itNext < nItems)
-            vc = gload(KARG(geoList), entry_of(itNext) + (size_t)vzero());
+            vc = record_dwords(itNext);
         /* the next item's mask dwords requested (none needed past the end) */
         bool maskNext = itNext >= nItems;
         if (lane == 0)
             nextIt = next_item();
-        const int tile = code >> 6, bit = code & 63;
-        const int tilesX = KARG(blocksX) * 2;
-        const int x = (tile % tilesX) * 8 + (bit & 7), r = (tile / tilesX) * 8 + (bit >> 3);
+        const int tile = record_tile(d0);
+        int x = (int)(d0 & 0xffffu), r = (int)(d0 >> 16);
+        if (KARG(wideItems)) { /* (uniform; launches of more than 65,535 columns or launch rows) */
+            const int tilesX = KARG(blocksX) * 2, bit = (int)(d0 & 63u);
+            x = (tile % tilesX) * 8 + (bit & 7), r = (tile / tilesX) * 8 + (bit >> 3);
+        }
         const int sh = KARG(rowBandShift); /* launch_row_y */
         const int y = KARG(rowStart) + ((r >> sh) * KARG(rowStride) << sh) + (r & ((1 << sh) - 1));
-        V3 pdir; /* main.c:88-94, as primary_dir */
-        {
-            const int W = KARG(width), H = KARG(height);
-            const float dx = (float)(x - W / 2) / (float)(H / 2);
-            const float dy = (float)(y - H / 2) / (float)(H / 2);
-            pdir = normalized(add(add(mul(KARG(ex), dx), mul(KARG(ey), dy)), mul(KARG(ez), KARG(fov))));
-        }
         const unsigned long long *mask = KARG(tileMask) + (size_t)tile * P.maskWords;
         unsigned L = 0;
         if (counting)
@@ -2211,7 +2223,7 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                     DMARK(dcur, 1); /* primary trace */
                 } else { /* bounce segments of the live lanes (the whole wave takes part) */
                     if (!maskNext) { /* the next item's mask dwords (see the prefetch above) */
-                        vm = mask_dwords(__builtin_amdgcn_readfirstlane((int)vc));
+                        vm = mask_dwords((unsigned)__builtin_amdgcn_readfirstlane((int)vc));
                         maskNext = true;
                     }
                     unsigned t = 0;
@@ -2454,7 +2466,7 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                 P.accum[o] = acc;
         }
         if (!maskNext) /* (an item without a bounce iteration) */
-            vm = mask_dwords(__builtin_amdgcn_readfirstlane((int)vc));
+            vm = mask_dwords((unsigned)__builtin_amdgcn_readfirstlane((int)vc));
 #ifdef RTC_DIAG
         if (lane == 0 && it < kItemLog) {
             g_rtc_itemlog[it][0] = dItemT0;
@@ -2629,13 +2641,14 @@ static void bind_plan(Launch &L, int flags)
     P.order = (flags & RTC_F_NO_REORDER) ? nullptr : L.region<int>(rtcplan::kBufOrder);
     P.superMask = L.region<unsigned long long>(rtcplan::kBufSuperMask);
     P.superX = P.superMask ? (int)pl.superX : 0;
-    P.geoList = L.region<int>(rtcplan::kBufGeoList);
+    P.geoList = L.region<unsigned>(rtcplan::kBufGeoList);
     P.pixItem = L.region<unsigned>(rtcplan::kBufPixItem);
     P.geoColor = L.region<unsigned>(rtcplan::kBufGeoColor);
     if (pl.binds(rtcplan::kBufGeoSet)) {
         P.geoCount = s->geoCounts + (size_t)pl.geoSet * kGeoSetInts;
         P.geoCountNext = s->geoCounts + (size_t)pl.geoSetNext * kGeoSetInts;
         P.geoCap = pl.geoCap;
+        P.wideItems = pl.wideItems;
         P.cullPrio = pl.cullPrio;
     }
     if (pl.binds(rtcplan::kBufSamples)) {
@@ -2766,9 +2779,11 @@ static int (*const kPlanned[])(const Launch &, hipStream_t, hipEvent_t) = { /* b
     run_prep, run_super_cull, run_tile_cull, run_sky, run_chain, run_accumulate, run_order, run_render, run_reduce};
 static_assert(sizeof kPlanned / sizeof kPlanned[0] == rtcplan::kKReduce + 1, "one function per planned kernel");
 
-extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
-                                     const RtcRenderDesc *d, void *dColors, float *dAccum,
-                                     unsigned long long *dSegments, void *stream)
+/* rtc_render_rows_async; with `items` (rtc_cull_items) the launch's preparation and culls alone: the kernels after the
+ * tile cull are not enqueued (the plan's events are, so the ordering state stays true: a launch whose render kernels did
+ * nothing), and `items` gets the launch's counter set and list regions */
+static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                       void *dColors, float *dAccum, unsigned long long *dSegments, void *stream, RtcCullItems *items)
 {
     if (!s)
         return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null scene");
@@ -2833,13 +2848,36 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
             HIP_TRY(hipStreamWaitEvent(os, ev, 0));
         } else if (op.kernel < 0 || op.kernel > rtcplan::kKReduce) {
             return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: unknown planned kernel %d", op.kernel);
+        } else if (items && op.kernel > rtcplan::kKTileCull) {
+            if (ev) /* (the skipped kernel's completion) */
+                HIP_TRY(hipEventRecord(ev, os));
         } else if (const int rc = kPlanned[op.kernel](L, os, ev)) {
             return rc;
         }
     }
     ms->timed = pl.fused && s->timing;
     ms->plan = pl.after; /* every operation is enqueued */
+    if (items) {
+        if (!pl.chain)
+            return rtc_fail(RTC_EINVAL, "rtc_cull_items: not a split launch");
+        *items = RtcCullItems{P.geoCount, P.geoList, P.pixMask, P.geoCap, P.blocksX * 2, pl.tiles, P.wideItems};
+    }
     return 0;
+}
+
+extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                                     const RtcRenderDesc *d, void *dColors, float *dAccum,
+                                     unsigned long long *dSegments, void *stream)
+{
+    return render_rows(s, scene, cam, d, dColors, dAccum, dSegments, stream, nullptr);
+}
+
+int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                   void *dColors, RtcCullItems *items)
+{
+    if (!items)
+        return rtc_fail(RTC_EINVAL, "rtc_cull_items: null argument");
+    return render_rows(s, scene, cam, d, dColors, nullptr, nullptr, nullptr, items);
 }
 
 /* ---- row de-interleave after a gather (bytes) ----------------------------------------------------- */
