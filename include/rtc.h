@@ -371,6 +371,21 @@ int rtc_probe_cluster_bound(const Triangle *tris, int triCount, const Ray *rays,
 int rtc_probe_item_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, const Scene *scene,
                            const RtcCamera *cam, const RtcRenderDesc *d, int counts[16], int info[4],
                            unsigned int *records, size_t maxRecords, unsigned long long *pixMask, size_t maxTiles);
+/* Soundness probe of the primary cull (no reference counterpart; a test decides hits with rayTriangle on the CPU): uploads
+ * the triangles, runs the preparation and the culls of the launch `d` as rtc_render_rows_async would (no render kernel) and
+ * copies back kept[(launch row * width + x) * triCount + t] = 1 when the primary filter keeps triangle t for that pixel
+ * (evaluated by the render kernels' own functions on the launch's records and the pixel's primary direction, for every
+ * triangle whatever the tile prefilter said), tileBits = per 8x8 tile its candidate bit-set (info[2] words of 64
+ * triangles; tile = (row / 8) * info[1] + x / 8), pixMask as rtc_probe_item_records, and info[4] = {tiles, tiles per
+ * launch row, words per tile, 1 when the superblock level of the tile cull ran}.  Optional (null: not wanted): primF =
+ * the launch's filter records, 16 floats per triangle {N, mnd, sigma Gd, c, sigma Gu, -m, sigma q0, 0}; cones and pruned
+ * (both or neither, maxTiles tiles) = per tile the prefilter's {eDir, vmin, vmax, 1 when the cone is usable} and
+ * pruned[tile * triCount + t] = 1 when the tile's own prefilter prunes triangle t.  RTC_EINVAL when the launch is not a
+ * split launch or an output is too small. */
+int rtc_probe_primary_cull(const Triangle *tris, int triCount, const Scene *scene, const RtcCamera *cam,
+                           const RtcRenderDesc *d, unsigned char *kept, size_t maxKept, unsigned long long *tileBits,
+                           size_t maxWords, unsigned long long *pixMask, size_t maxTiles, int info[4], float *primF,
+                           double *cones, unsigned char *pruned);
 
 #ifdef __cplusplus
 }

@@ -510,3 +510,29 @@ def item_records_probe(tris, spheres, scene: Scene, cam: RtcCamera, cfg: RenderC
                                        _ptr(info), _ptr(rec), len(rec), _ptr(pm), len(pm)), "rtc_probe_item_records")
     return {"counts": counts, "records": rec[: int(counts.sum())].copy(), "pix_mask": pm, "cap": int(info[0]),
             "tiles_x": int(info[1]), "tiles": int(info[2]), "wide": bool(info[3])}
+
+
+def primary_cull_probe(tris, scene: Scene, cam: RtcCamera, cfg: RenderConfig) -> dict:
+    """The primary cull of the launch `cfg` (rtc_probe_primary_cull: its preparation and culls, no render kernel): kept
+    uint8 [rows, width, triangles] the per-pixel filter's verdict for every triangle, tile_bits uint64 [tiles, words] the
+    tiles' candidate bit-sets, pix_mask uint64 [tiles], and tiles, tiles_x, words, level0 (the superblock level ran); prim_f
+    float32 [triangles, 16] the launch's filter records (DevPrimF), cones float64 [tiles, 4] the tiles' prefilter {eDir,
+    vmin, vmax, usable} and pruned uint8 [tiles, triangles] the tiles' own prefilter verdicts."""
+    t, nt = _arr(tris, TRIANGLE_DT)
+    rows = cfg.rows()
+    tiles = 4 * ((cfg.width + 15) // 16) * ((rows + 15) // 16)
+    words = ((nt + 7) // 8 * 8 + 63) // 64
+    kept = np.zeros((rows, cfg.width, nt), np.uint8)
+    bits = np.zeros((tiles, words), np.uint64)
+    pm = np.zeros(tiles, np.uint64)
+    info = np.zeros(4, np.int32)
+    prim_f = np.zeros((nt, 16), np.float32)
+    cones = np.zeros((tiles, 4), np.float64)
+    pruned = np.zeros((tiles, nt), np.uint8)
+    d = cfg.desc()
+    check(lib().rtc_probe_primary_cull(_ptr(t), nt, C.byref(scene), C.byref(cam), C.byref(d), _ptr(kept), kept.size,
+                                       _ptr(bits), bits.size, _ptr(pm), len(pm), _ptr(info), _ptr(prim_f), _ptr(cones),
+                                       _ptr(pruned)), "rtc_probe_primary_cull")
+    assert int(info[0]) == tiles and int(info[2]) == words, info
+    return {"kept": kept, "tile_bits": bits, "pix_mask": pm, "tiles": int(info[0]), "tiles_x": int(info[1]),
+            "words": int(info[2]), "level0": bool(info[3]), "prim_f": prim_f, "cones": cones, "pruned": pruned}

@@ -144,6 +144,7 @@ EXPORTS = [
     "rtc_host_unregister", "rtc_plan_sim_create", "rtc_plan_sim_launch", "rtc_plan_sim_release", "rtc_frame_loop", "rtc_frame_loop_cameras", "rtc_dma_pending", "rtc_dma_debug_inflight",
     "rtc_probe_ray_triangle", "rtc_probe_ray_sphere", "rtc_probe_environment", "rtc_probe_random",
     "rtc_probe_cluster_bound", "rtc_probe_sun_vanish", "rtc_env_vanish_limit", "rtc_probe_item_records",
+    "rtc_probe_primary_cull",
 ]
 
 _lib = None
@@ -235,6 +236,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "rtc_probe_item_records"):  # (absent from libraries of earlier rounds loaded for A/B timing)
         L.rtc_probe_item_records.argtypes = [vp, ip, vp, ip, C.POINTER(Scene), C.POINTER(RtcCamera),
                                              C.POINTER(RtcRenderDesc), vp, vp, vp, sz, vp, sz]
+    if hasattr(L, "rtc_probe_primary_cull"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_probe_primary_cull.argtypes = [vp, ip, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
+                                             vp, sz, vp, sz, vp, sz, vp, vp, vp, vp]
     _lib = L
     return L
 

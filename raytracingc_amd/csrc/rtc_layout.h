@@ -48,6 +48,151 @@ struct __attribute__((aligned(64))) DevPrimX {
     float abx, aby, abz, acx, acy, acz, s0x, s0y, s0z, q0x, q0y, q0z, dac0, pad[3];
 };
 
+/* The pixel -> primary ray map and the primary filter's per-pixel verdict, shared by the render kernels (rtc_render.hip,
+ * where the proofs are) and the filter's soundness probe (rtc_probe_primary_cull).  P is any record with the launch's
+ * width, height, rowStart, rowStride, rowBandShift, ex, ey, ez and fov: RenderParams, or the probe's PrimaryView. */
+struct PrimaryView {
+    int width, height, rows, rowStart, rowStride, rowBandShift;
+    V3 ex, ey, ez;
+    float fov;
+};
+
+template <typename PT> __device__ __forceinline__ V3 primary_dir(const PT &P, int x, int y)
+{
+    /* integer halves, then int->float, f32 divide */
+    const float dx = (float)(x - P.width / 2) / (float)(P.height / 2);
+    const float dy = (float)(y - P.height / 2) / (float)(P.height / 2);
+    return normalized(add(add(mul(P.ex, dx), mul(P.ey, dy)), mul(P.ez, P.fov)));
+}
+
+/* Launch row r -> image row y: y = rowStart + k*rowStride (main.c:84's interleave), or bands of 2^rowBandShift rows
+ * (rtc.h rowBand): y = rowStart + (r / B)*rowStride*B + r % B */
+template <typename PT> __device__ __forceinline__ int launch_row_y(const PT &P, int r)
+{
+    const int sh = P.rowBandShift;
+    return P.rowStart + ((r >> sh) * P.rowStride << sh) + (r & ((1 << sh) - 1));
+}
+
+__device__ __forceinline__ float fdot(V3 d, float x, float y, float z) { return fmaf(d.z, z, fmaf(d.y, y, d.x * x)); }
+
+__device__ __forceinline__ bool prim_backfacing(V3 dir, const DevPrimF &F)
+{
+    return fdot(dir, F.nx, F.ny, F.nz) > F.mnd;
+}
+
+__device__ __forceinline__ bool prim_pass(V3 dir, const DevPrimF &F)
+{
+    const float dt = fdot(dir, F.gdx, F.gdy, F.gdz);
+    const float ut = fdot(dir, F.gux, F.guy, F.guz);
+    const float vt = fdot(dir, F.q0x, F.q0y, F.q0z);
+    const float wt = (dt - ut) - vt;
+    return (dt >= F.c) & (fminf(fminf(ut, vt), wt) >= F.negm);
+}
+
+/* The tile prefilter (its derivation: rtc_render.hip, "Tile prefilter"): the cone of a pixel rectangle and the test that no
+ * pixel of it can pass the filter for a record.  P: as for primary_dir, with the launch's `rows`. */
+struct TileCone {
+    double c[4][3];
+    double vmin, vmax, eDir;
+    double ivmin, ivmax; /* 1 / vmin, 1 / vmax (cone_range multiplies and widens instead of dividing) */
+    bool ok;
+};
+
+/* the cone of the pixel rectangle [x0, x1] x [r0, r1] (launch rows) */
+template <typename PT> __device__ TileCone rect_cone(const PT &P, int x0, int x1, int r0, int r1)
+{
+    TileCone K;
+    x1 = min(x1, P.width - 1);
+    r1 = min(r1, P.rows - 1);
+    const int y0 = launch_row_y(P, r0), y1 = launch_row_y(P, r1); /* (y is increasing in the launch row) */
+    /* the same f32 expressions as primary_dir */
+    const float dxs[2] = {(float)(x0 - P.width / 2) / (float)(P.height / 2),
+                          (float)(x1 - P.width / 2) / (float)(P.height / 2)};
+    const float dys[2] = {(float)(y0 - P.height / 2) / (float)(P.height / 2),
+                          (float)(y1 - P.height / 2) / (float)(P.height / 2)};
+    const double ezl = sqrt((double)P.ez.x * P.ez.x + (double)P.ez.y * P.ez.y + (double)P.ez.z * P.ez.z);
+    double vmin = 1e300, vmax = 0.0;
+    bool finite = ezl > 0.0 && ezl < 1e300;
+    for (int k = 0; k < 4; ++k) {
+        const double dx = dxs[k & 1], dy = dys[k >> 1];
+        const double v[3] = {(double)P.ex.x * dx + (double)P.ey.x * dy + (double)P.ez.x * P.fov,
+                             (double)P.ex.y * dx + (double)P.ey.y * dy + (double)P.ez.y * P.fov,
+                             (double)P.ex.z * dx + (double)P.ey.z * dy + (double)P.ez.z * P.fov};
+        for (int i = 0; i < 3; ++i) {
+            K.c[k][i] = v[i];
+            finite = finite && (v[i] - v[i] == 0.0);
+        }
+        vmax = fmax(vmax, sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+        vmin = fmin(vmin, (v[0] * P.ez.x + v[1] * P.ez.y + v[2] * P.ez.z) / ezl);
+    }
+    const double u = 5.9604644775390625e-08;
+    const double S = fmax(fabs((double)dxs[0]), fabs((double)dxs[1])) + fmax(fabs((double)dys[0]), fabs((double)dys[1])) +
+                     fabs((double)P.fov);
+    K.vmin = vmin * (1.0 - 1e-12);
+    K.vmax = vmax * (1.0 + 1e-12);
+    K.eDir = 16.0 * u * S / K.vmin + 4.0 * u;
+    K.ivmin = 1.0 / K.vmin;
+    K.ivmax = 1.0 / K.vmax;
+    /* basis components <= 1 (normalized f32 vectors) is assumed by the error bound */
+    const bool unitBasis = fabs(P.ex.x) <= 1.0001f && fabs(P.ex.y) <= 1.0001f && fabs(P.ex.z) <= 1.0001f &&
+                           fabs(P.ey.x) <= 1.0001f && fabs(P.ey.y) <= 1.0001f && fabs(P.ey.z) <= 1.0001f &&
+                           fabs(P.ez.x) <= 1.0001f && fabs(P.ez.y) <= 1.0001f && fabs(P.ez.z) <= 1.0001f;
+    K.ok = finite && unitBasis && K.vmin > 1e-6 && K.eDir < 1e-3 && S - S == 0.0;
+    return K;
+}
+
+template <typename PT> __device__ TileCone tile_cone(const PT &P, int tx, int ty)
+{
+    return rect_cone(P, tx * 8, tx * 8 + 7, ty * 8, ty * 8 + 7);
+}
+
+/* [LB, UB] of g.v/|v| over the tile (see TileCone) */
+__device__ __forceinline__ void cone_range(const TileCone &K, double gx, double gy, double gz, double &lb, double &ub)
+{
+    double mx = -1e300, mn = 1e300;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double a = gx * K.c[k][0] + gy * K.c[k][1] + gz * K.c[k][2];
+        mx = fmax(mx, a);
+        mn = fmin(mn, a);
+    }
+    /* mx / vmin (or / vmax) as a product with the rounded reciprocal: two double roundings, < 2^-51 relative, so
+     * widening by 2^-50 of the magnitude keeps ub above (lb below) the exact quotient -- the bound only loosens */
+    ub = mx * (mx >= 0.0 ? K.ivmin : K.ivmax);
+    lb = mn * (mn >= 0.0 ? K.ivmax : K.ivmin);
+    ub += fabs(ub) * 0x1p-50;
+    lb -= fabs(lb) * 0x1p-50;
+}
+
+/* true: no pixel of the tile can pass prim_backfacing / prim_pass for F */
+__device__ bool tile_prunes(const TileCone &K, const DevPrimF &F)
+{
+    const double u = 5.9604644775390625e-08;
+    const double e = K.eDir + 3.01 * u;
+    auto n1 = [](double a, double b, double c) { return fabs(a) + fabs(b) + fabs(c); };
+    double lb, ub;
+    /* every pixel back-facing: nd > mnd */
+    cone_range(K, F.nx, F.ny, F.nz, lb, ub);
+    if (lb - n1(F.nx, F.ny, F.nz) * e > (double)F.mnd)
+        return true;
+    const double nd = n1(F.gdx, F.gdy, F.gdz), nu = n1(F.gux, F.guy, F.guz), nv = n1(F.q0x, F.q0y, F.q0z);
+    cone_range(K, F.gdx, F.gdy, F.gdz, lb, ub);
+    if (ub + nd * e < (double)F.c)
+        return true;
+    cone_range(K, F.gux, F.guy, F.guz, lb, ub);
+    if (ub + nu * e < (double)F.negm)
+        return true;
+    cone_range(K, F.q0x, F.q0y, F.q0z, lb, ub);
+    if (ub + nv * e < (double)F.negm)
+        return true;
+    /* wt = (dt - ut) - vt: the three slacks plus two f32 subtractions */
+    cone_range(K, (double)F.gdx - F.gux - F.q0x, (double)F.gdy - F.guy - F.q0y, (double)F.gdz - F.guz - F.q0z, lb,
+               ub);
+    if (ub + (nd + nu + nv) * (e + 2.01 * u * 1.0001) < (double)F.negm)
+        return true;
+    return false;
+}
+
 /* ---- triangle clusters for bounce rays (rtc_render_chain) -----------------------------------------------
  * The triangles are grouped into clusters of kClusterSize (spatial median splits, rtc_build_clusters); a
  * bounce ray skips a whole cluster when its half-line provably passes farther from the cluster's bounding
@@ -171,6 +316,14 @@ struct RtcCullItems {
     int geoCap, tilesX;
     size_t tiles;
     int wide;                 /* the records keep tile * 64 + bit (RenderParams::wideItems) */
+    /* for rtc_probe_primary_cull: the tiles' candidate bit-sets (maskWords u64 per tile; a split launch leaves the words
+     * of a workgroup without a survivor unwritten: its tiles' pixMask is 0), the launch's primary filter records, and
+     * whether rtc_super_cull (level 0) ran */
+    const unsigned long long *tileMask;
+    int maskWords;
+    const DevPrimF *primF;
+    int triPadded;
+    int level0;
 };
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items);

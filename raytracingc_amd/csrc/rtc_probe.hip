@@ -1,7 +1,8 @@
 /*
  * rtc_probe.hip -- the reference's single functions on the device for known-answer tests (include/rtc.h rtc_probe_*):
  * rayTriangle (raytracing.c:186-214), raySphere (:162-184), getEnvironmentLight (:151-160), the RNG
- * (moremath.c:89-108), and the soundness probe of the bounce-ray cluster culling (rtc_layout.h cluster_culled).
+ * (moremath.c:89-108), the soundness probe of the bounce-ray cluster culling (rtc_layout.h cluster_culled), the split
+ * launch's item records, and the soundness probe of the primary cull (the primary filter and the tile prefilter).
  */
 #include <hip/hip_runtime.h>
 
@@ -411,6 +412,103 @@ extern "C" int rtc_probe_item_records(const Triangle *tris, int triCount, const 
         return 0;
     };
     rc = run();
+    rtc_scene_release(s);
+    return rc;
+}
+
+/* The primary filter's verdict for every (pixel of the launch, triangle): !prim_backfacing && prim_pass (rtc_layout.h, the
+ * render kernels' own functions) on the launch's DevPrimF records and the pixel's primary_dir.  One thread per pixel
+ * (launch row r, column x: pixel r * width + x); kept[pixel * triCount + t]. */
+__global__ void probe_primary_kernel(PrimaryView V, int rows, const DevPrimF *primF, int triCount, unsigned char *kept)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= (size_t)rows * (size_t)V.width)
+        return;
+    const int x = (int)(i % (size_t)V.width), r = (int)(i / (size_t)V.width);
+    const V3 dir = primary_dir(V, x, launch_row_y(V, r));
+    for (int t = 0; t < triCount; ++t) {
+        const DevPrimF F = primF[t];
+        kept[i * (size_t)triCount + t] = !prim_backfacing(dir, F) && prim_pass(dir, F) ? 1 : 0;
+    }
+}
+
+/* The tile prefilter per 8x8 tile (level 2 of rtc_tile_cull: tile_cone / tile_prunes, rtc_layout.h): one thread per tile;
+ * cones[tile * 4 ..] = {eDir, vmin, vmax, ok}, pruned[tile * triCount + t] = the cone is usable and prunes record t */
+__global__ void probe_cone_kernel(PrimaryView V, int tilesX, int tiles, const DevPrimF *primF, int triCount, double *cones,
+                                  unsigned char *pruned)
+{
+    const int tile = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tile >= tiles)
+        return;
+    const TileCone K = tile_cone(V, tile % tilesX, tile / tilesX);
+    cones[tile * 4 + 0] = K.eDir, cones[tile * 4 + 1] = K.vmin, cones[tile * 4 + 2] = K.vmax, cones[tile * 4 + 3] = K.ok ? 1.0 : 0.0;
+    for (int t = 0; t < triCount; ++t)
+        pruned[(size_t)tile * (size_t)triCount + t] = K.ok && tile_prunes(K, primF[t]) ? 1 : 0;
+}
+
+/* Soundness probe of the primary cull (include/rtc.h): the launch's own preparation and culls (rtc_cull_items), then the
+ * per-pixel verdicts by probe_primary_kernel; the tiles' bit-sets and pixel masks are the launch's */
+extern "C" int rtc_probe_primary_cull(const Triangle *tris, int triCount, const Scene *scene, const RtcCamera *cam,
+                                      const RtcRenderDesc *d, unsigned char *kept, size_t maxKept,
+                                      unsigned long long *tileBits, size_t maxWords, unsigned long long *pixMask,
+                                      size_t maxTiles, int info[4], float *primF, double *cones, unsigned char *pruned)
+{
+    if (!tris || triCount <= 0 || !scene || !cam || !d || !kept || !tileBits || !pixMask || !info)
+        return rtc_fail(RTC_EINVAL, "rtc_probe_primary_cull: bad argument");
+    if (int rc = probe_prelude())
+        return rc;
+    RtcDeviceScene *s = nullptr;
+    if (int rc = rtc_scene_upload(tris, triCount, nullptr, 0, -1, &s))
+        return rc;
+    Scratch sc;
+    const auto run = [&]() -> int {
+        const int rows = rtc_rows_selected(d);
+        if (rows <= 0)
+            return rtc_fail(RTC_EINVAL, "rtc_probe_primary_cull: the launch has no rows");
+        unsigned char *dColors = nullptr; /* (the launch's key; no kernel of the probe's writes it) */
+        HIP_TRY(sc.alloc((void **)&dColors, (size_t)d->width * (size_t)rows * 3));
+        RtcCullItems it{};
+        if (const int r = rtc_cull_items(s, scene, cam, d, dColors, &it))
+            return r;
+        HIP_TRY(hipDeviceSynchronize());
+        const size_t pixels = (size_t)rows * (size_t)d->width, words = it.tiles * (size_t)it.maskWords;
+        info[0] = (int)it.tiles, info[1] = it.tilesX, info[2] = it.maskWords, info[3] = it.level0;
+        if (pixels * (size_t)triCount > maxKept || words > maxWords || it.tiles > maxTiles || triCount > it.triPadded)
+            return rtc_fail(RTC_EINVAL, "rtc_probe_primary_cull: %zu verdicts, %zu words, %zu tiles: the outputs are smaller",
+                            pixels * (size_t)triCount, words, it.tiles);
+        unsigned char *dk = nullptr;
+        HIP_TRY(sc.alloc((void **)&dk, pixels * (size_t)triCount));
+        PrimaryView V{};
+        V.width = d->width, V.height = d->height, V.rows = rows, V.rowStart = d->rowStart, V.rowStride = d->rowStride;
+        V.rowBandShift = d->rowBand > 1 ? __builtin_ctz((unsigned)d->rowBand) : 0; /* as render_params */
+        V.ex = v3(cam->ex), V.ey = v3(cam->ey), V.ez = v3(cam->ez), V.fov = cam->fov;
+        hipLaunchKernelGGL(probe_primary_kernel, dim3(probe_blocks(pixels)), dim3(256), 0, nullptr, V, rows, it.primF,
+                           triCount, dk);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(kept, dk, pixels * (size_t)triCount, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pixMask, it.pixMask, it.tiles * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tileBits, it.tileMask, words * 8, hipMemcpyDeviceToHost));
+        if (primF) /* the launch's filter records, 16 floats each (DevPrimF) */
+            HIP_TRY(hipMemcpy(primF, it.primF, (size_t)triCount * sizeof(DevPrimF), hipMemcpyDeviceToHost));
+        if (cones && pruned) { /* (sized by the caller from info's tiles: maxTiles tiles) */
+            double *dc = nullptr;
+            unsigned char *dp = nullptr;
+            HIP_TRY(sc.alloc((void **)&dc, it.tiles * 4 * sizeof(double)));
+            HIP_TRY(sc.alloc((void **)&dp, it.tiles * (size_t)triCount));
+            hipLaunchKernelGGL(probe_cone_kernel, dim3(probe_blocks(it.tiles)), dim3(256), 0, nullptr, V, it.tilesX,
+                               (int)it.tiles, it.primF, triCount, dc, dp);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(cones, dc, it.tiles * 4 * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(pruned, dp, it.tiles * (size_t)triCount, hipMemcpyDeviceToHost));
+        }
+        /* a split launch writes no words for the tiles of a workgroup without a survivor (rtc_tile_cull): their lists
+         * are empty, which their pixMask says */
+        for (size_t t = 0; t < it.tiles; ++t)
+            if (pixMask[t] == 0ull)
+                memset(tileBits + t * (size_t)it.maskWords, 0, (size_t)it.maskWords * 8);
+        return 0;
+    };
+    const int rc = run();
     rtc_scene_release(s);
     return rc;
 }

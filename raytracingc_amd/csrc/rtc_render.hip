@@ -223,22 +223,7 @@ struct PixelRay {
     V3 dir;
 };
 
-__device__ __forceinline__ V3 primary_dir(const RenderParams &P, int x, int y)
-{
-    /* integer halves, then int->float, f32 divide */
-    const float dx = (float)(x - P.width / 2) / (float)(P.height / 2);
-    const float dy = (float)(y - P.height / 2) / (float)(P.height / 2);
-    return normalized(add(add(mul(P.ex, dx), mul(P.ey, dy)), mul(P.ez, P.fov)));
-}
-
-/* Launch row r -> image row y: y = rowStart + k*rowStride (main.c:84's interleave), or bands of 2^rowBandShift rows
- * (rtc.h rowBand): y = rowStart + (r / B)*rowStride*B + r % B */
-__device__ __forceinline__ int launch_row_y(const RenderParams &P, int r)
-{
-    const int sh = P.rowBandShift;
-    return P.rowStart + ((r >> sh) * P.rowStride << sh) + (r & ((1 << sh) - 1));
-}
-
+/* (primary_dir and launch_row_y: rtc_layout.h, shared with the primary filter's probe) */
 __device__ __forceinline__ PixelRay pixel_ray(const RenderParams &P, int bx, int by)
 {
     PixelRay px;
@@ -380,22 +365,8 @@ constexpr float kTiny = 8.67361738e-19f; /* 2^-60 */
  *   min(sigma*u~, sigma*v~, sigma*w~) < -m => u < 0, v < 0 or u+v > 1       (:200-204)
  * The exact reference arithmetic runs only for lanes the filter keeps (NaN directions are never kept:
  * their det is NaN, so the reference cannot record a hit either).  Records are scalar-loaded in batches.
- * prim_backfacing / prim_pass are THE filter: the render kernel and rtc_tile_cull both use them. */
-__device__ __forceinline__ float fdot(V3 d, float x, float y, float z) { return fmaf(d.z, z, fmaf(d.y, y, d.x * x)); }
-
-__device__ __forceinline__ bool prim_backfacing(V3 dir, const DevPrimF &F)
-{
-    return fdot(dir, F.nx, F.ny, F.nz) > F.mnd;
-}
-
-__device__ __forceinline__ bool prim_pass(V3 dir, const DevPrimF &F)
-{
-    const float dt = fdot(dir, F.gdx, F.gdy, F.gdz);
-    const float ut = fdot(dir, F.gux, F.guy, F.guz);
-    const float vt = fdot(dir, F.q0x, F.q0y, F.q0z);
-    const float wt = (dt - ut) - vt;
-    return (dt >= F.c) & (fminf(fminf(ut, vt), wt) >= F.negm);
-}
+ * prim_backfacing / prim_pass (rtc_layout.h) are THE filter: the render kernel and rtc_tile_cull both use them, and
+ * rtc_probe_primary_cull returns their verdicts for tests/test_gpu_primary_cull.py. */
 
 /* One primary record (see closest_primary). */
 __device__ __forceinline__ void primary_test(const RenderParams &P, V3 dir, const DevPrimF &F, int t, int base,
@@ -747,107 +718,7 @@ extern "C" int rtc_diag_sections(unsigned long long *out, int reset)
  * point of that range -- then it fails for every pixel, exactly as the per-pixel filter would decide.
  * Computed in double per (tile, triangle); a tile whose bounds are not finite or whose vmin <= 0 is never
  * pruned. */
-struct TileCone {
-    double c[4][3];
-    double vmin, vmax, eDir;
-    double ivmin, ivmax; /* 1 / vmin, 1 / vmax (cone_range multiplies and widens instead of dividing) */
-    bool ok;
-};
-
-/* the cone of the pixel rectangle [x0, x1] x [r0, r1] (launch rows) */
-__device__ TileCone rect_cone(const RenderParams &P, int x0, int x1, int r0, int r1)
-{
-    TileCone K;
-    x1 = min(x1, P.width - 1);
-    r1 = min(r1, P.rows - 1);
-    const int y0 = launch_row_y(P, r0), y1 = launch_row_y(P, r1); /* (y is increasing in the launch row) */
-    /* the same f32 expressions as primary_dir */
-    const float dxs[2] = {(float)(x0 - P.width / 2) / (float)(P.height / 2),
-                          (float)(x1 - P.width / 2) / (float)(P.height / 2)};
-    const float dys[2] = {(float)(y0 - P.height / 2) / (float)(P.height / 2),
-                          (float)(y1 - P.height / 2) / (float)(P.height / 2)};
-    const double ezl = sqrt((double)P.ez.x * P.ez.x + (double)P.ez.y * P.ez.y + (double)P.ez.z * P.ez.z);
-    double vmin = 1e300, vmax = 0.0;
-    bool finite = ezl > 0.0 && ezl < 1e300;
-    for (int k = 0; k < 4; ++k) {
-        const double dx = dxs[k & 1], dy = dys[k >> 1];
-        const double v[3] = {(double)P.ex.x * dx + (double)P.ey.x * dy + (double)P.ez.x * P.fov,
-                             (double)P.ex.y * dx + (double)P.ey.y * dy + (double)P.ez.y * P.fov,
-                             (double)P.ex.z * dx + (double)P.ey.z * dy + (double)P.ez.z * P.fov};
-        for (int i = 0; i < 3; ++i) {
-            K.c[k][i] = v[i];
-            finite = finite && (v[i] - v[i] == 0.0);
-        }
-        vmax = fmax(vmax, sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
-        vmin = fmin(vmin, (v[0] * P.ez.x + v[1] * P.ez.y + v[2] * P.ez.z) / ezl);
-    }
-    const double u = 5.9604644775390625e-08;
-    const double S = fmax(fabs((double)dxs[0]), fabs((double)dxs[1])) + fmax(fabs((double)dys[0]), fabs((double)dys[1])) +
-                     fabs((double)P.fov);
-    K.vmin = vmin * (1.0 - 1e-12);
-    K.vmax = vmax * (1.0 + 1e-12);
-    K.eDir = 16.0 * u * S / K.vmin + 4.0 * u;
-    K.ivmin = 1.0 / K.vmin;
-    K.ivmax = 1.0 / K.vmax;
-    /* basis components <= 1 (normalized f32 vectors) is assumed by the error bound */
-    const bool unitBasis = fabs(P.ex.x) <= 1.0001f && fabs(P.ex.y) <= 1.0001f && fabs(P.ex.z) <= 1.0001f &&
-                           fabs(P.ey.x) <= 1.0001f && fabs(P.ey.y) <= 1.0001f && fabs(P.ey.z) <= 1.0001f &&
-                           fabs(P.ez.x) <= 1.0001f && fabs(P.ez.y) <= 1.0001f && fabs(P.ez.z) <= 1.0001f;
-    K.ok = finite && unitBasis && K.vmin > 1e-6 && K.eDir < 1e-3 && S - S == 0.0;
-    return K;
-}
-
-__device__ TileCone tile_cone(const RenderParams &P, int tx, int ty)
-{
-    return rect_cone(P, tx * 8, tx * 8 + 7, ty * 8, ty * 8 + 7);
-}
-
-/* [LB, UB] of g.v/|v| over the tile (see TileCone) */
-__device__ __forceinline__ void cone_range(const TileCone &K, double gx, double gy, double gz, double &lb, double &ub)
-{
-    double mx = -1e300, mn = 1e300;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double a = gx * K.c[k][0] + gy * K.c[k][1] + gz * K.c[k][2];
-        mx = fmax(mx, a);
-        mn = fmin(mn, a);
-    }
-    /* mx / vmin (or / vmax) as a product with the rounded reciprocal: two double roundings, < 2^-51 relative, so
-     * widening by 2^-50 of the magnitude keeps ub above (lb below) the exact quotient -- the bound only loosens */
-    ub = mx * (mx >= 0.0 ? K.ivmin : K.ivmax);
-    lb = mn * (mn >= 0.0 ? K.ivmax : K.ivmin);
-    ub += fabs(ub) * 0x1p-50;
-    lb -= fabs(lb) * 0x1p-50;
-}
-
-/* true: no pixel of the tile can pass prim_backfacing / prim_pass for F */
-__device__ bool tile_prunes(const TileCone &K, const DevPrimF &F)
-{
-    const double u = 5.9604644775390625e-08;
-    const double e = K.eDir + 3.01 * u;
-    auto n1 = [](double a, double b, double c) { return fabs(a) + fabs(b) + fabs(c); };
-    double lb, ub;
-    /* every pixel back-facing: nd > mnd */
-    cone_range(K, F.nx, F.ny, F.nz, lb, ub);
-    if (lb - n1(F.nx, F.ny, F.nz) * e > (double)F.mnd)
-        return true;
-    const double nd = n1(F.gdx, F.gdy, F.gdz), nu = n1(F.gux, F.guy, F.guz), nv = n1(F.q0x, F.q0y, F.q0z);
-    cone_range(K, F.gdx, F.gdy, F.gdz, lb, ub);
-    if (ub + nd * e < (double)F.c)
-        return true;
-    cone_range(K, F.gux, F.guy, F.guz, lb, ub);
-    if (ub + nu * e < (double)F.negm)
-        return true;
-    cone_range(K, F.q0x, F.q0y, F.q0z, lb, ub);
-    if (ub + nv * e < (double)F.negm)
-        return true;
-    /* wt = (dt - ut) - vt: the three slacks plus two f32 subtractions */
-    cone_range(K, (double)F.gdx - F.gux - F.q0x, (double)F.gdy - F.guy - F.q0y, (double)F.gdz - F.guz - F.q0z, lb,
-               ub);
-    if (ub + (nd + nu + nv) * (e + 2.01 * u * 1.0001) < (double)F.negm)
-        return true;
-    return false;
-}
+/* (TileCone, rect_cone, tile_cone, cone_range and tile_prunes: rtc_layout.h, shared with the primary cull's probe) */
 
 /* Level 0 of the tile cull: the same prefilter over a superblock of kSuperBlocks x kSuperBlocks workgroup blocks (64 x 64
  * pixels of the launch's rows), one wave each.  A triangle it prunes fails the filter for every pixel of the superblock,
@@ -2860,7 +2731,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
     if (items) {
         if (!pl.chain)
             return rtc_fail(RTC_EINVAL, "rtc_cull_items: not a split launch");
-        *items = RtcCullItems{P.geoCount, P.geoList, P.pixMask, P.geoCap, P.blocksX * 2, pl.tiles, P.wideItems};
+        *items = RtcCullItems{P.geoCount, P.geoList,   P.pixMask, P.geoCap,    P.blocksX * 2,        pl.tiles, P.wideItems,
+                              P.tileMask, P.maskWords, P.primF,   P.triPadded, pl.superCull ? 1 : 0};
     }
     return 0;
 }

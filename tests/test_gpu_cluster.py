@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from adversarial_scenes import SCENES as ADVERSARIAL
 from conftest import load_tris
 
 import raytracingc_amd as rt
@@ -98,9 +99,20 @@ def _free_rays(tris, n, rng):
     return pos, _unit(rng.normal(size=(n, 3)))
 
 
+def _finite(tris):
+    """The triangles whose vertices and stored normal are finite: ray origins and targets are drawn from these only (the
+    others stay in the scene the probe uploads)."""
+    ok = np.ones(len(tris), bool)
+    for part in _verts(tris):
+        ok &= np.isfinite(part).all(1)
+    return tris[ok]
+
+
 def _rays(tris, n, rng):
+    tris = _finite(tris)
     gens = (_bounce_like_rays, _aimed_rays, _grazing_rays, _self_rays, _free_rays)
-    parts = [g(tris, n, rng) for g in gens]
+    with np.errstate(invalid="ignore", divide="ignore"):  # (a zero-area triangle aimed at from itself: a NaN ray, never culled)
+        parts = [g(tris, n, rng) for g in gens]
     r = np.zeros(len(gens) * n, RAY_DT)
     pos = np.concatenate([p for p, _ in parts]).astype(np.float32)
     d = np.concatenate([d for _, d in parts]).astype(np.float32)
@@ -120,11 +132,21 @@ def _scaled(tris, s):
 
 @pytest.mark.parametrize("name,scale", [("ultracomplex", 1.0), ("complex", 1.0), ("cube", 1.0),
                                         ("ultracomplex", 40.0), ("ultracomplex", 0.02), ("fsuzane", 1.0),
-                                        ("4geoms", 1.0), ("default", 1.0), ("suzannes", 1.0), ("suzannes", 25.0)])
+                                        ("4geoms", 1.0), ("default", 1.0), ("suzannes", 1.0), ("suzannes", 25.0),
+                                        ("adv:slivers", 1.0), ("adv:far_offset_1e3", 1.0), ("adv:far_offset_1e5", 1.0),
+                                        ("adv:mixed_scale", 1.0), ("adv:bad_normals", 1.0), ("adv:nonfinite", 1.0),
+                                        ("adv:chunks", 1.0)])
 def test_cluster_culling_is_sound(name, scale, gpu_available):
-    """suzannes.obj (5,208 triangles, 21 chunks) also checks the chunk balls of rtc_render_chain's first level."""
-    tris, _ = load_tris(name)
-    tris = _scaled(tris, scale)
+    """suzannes.obj (5,208 triangles, 21 chunks) also checks the chunk balls of rtc_render_chain's first level.  The adv:
+    scenes are tests/adversarial_scenes.py's: records ball_of never culls (edges beyond its edRatio switch, radii beyond
+    1e18, non-finite vertices) in clusters and chunks with ordinary ones, and stored normals aligned_normal must refuse."""
+    covered = True  # every record is one the cluster and reach proofs cover
+    if name.startswith("adv:"):
+        tris, _, note = ADVERSARIAL[name[4:]]
+        covered = not any(k in note for k in ("oversized", "misaligned", "degenerate"))
+    else:
+        tris, _ = load_tris(name)
+        tris = _scaled(tris, scale)
     rng = np.random.default_rng(1234 + int(scale * 100))
     rays = _rays(tris, 250_000 if len(tris) <= 256 else 40_000, rng)
     r = rt.cluster_bound_probe(tris, rays)
@@ -132,6 +154,8 @@ def test_cluster_culling_is_sound(name, scale, gpu_available):
     assert r["violations"] == 0, r
     assert r["reach_violations"] == 0, r
     assert r["hits"] > 1_000
+    if not covered:
+        return
     if scale <= 1.0:  # aligned_normal's margin is absolute (EPSILON): large triangles are never "aligned"
         assert r["unreachable"] > 0
     if len(tris) > 16 and scale == 1.0:

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import load_tris
+from primary_rays import launch_rows as _launch_rows, primary_dirs as _primary_dirs
 from sphere_scenes import open5
 
 import oracle.binding as orc
@@ -29,30 +30,6 @@ CAM_ARGS = ((-4.0, -1.9, -5.2), (0.6, -1.0, 1.3), 1.1)
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _launch_rows(cfg):
-    """Image row of every launch row (rtc.h: y = rowStart + k*rowStride, or bands of rowBand rows)."""
-    B = max(cfg.row_band, 1)
-    r = np.arange(cfg.rows())
-    return cfg.row_start + (r // B) * cfg.row_stride * B + r % B
-
-
-def _primary_dirs(cam, cfg, x, y):
-    """main.c:88-93 for the pixels (x, y), float32 operation by operation: integer halves, int -> float, f32 divides,
-    plus(plus(times(ex, dx), times(ey, dy)), times(ez, fov)), then normalized (moremath.c:7-17: the f32 sum of squares left
-    to right, sqrt and 1./length in double, each rounded to float, three f32 products)."""
-    f = np.float32
-    v = lambda a: np.array([a.x, a.y, a.z], f)  # noqa: E731
-    W, H = cfg.width, cfg.height
-    dx = ((x - W // 2).astype(f) / f(H // 2))[:, None]
-    dy = ((y - H // 2).astype(f) / f(H // 2))[:, None]
-    d = (((v(cam.ex) * dx).astype(f) + (v(cam.ey) * dy).astype(f)).astype(f) + (v(cam.ez) * f(cam.fov)).astype(f)).astype(f)
-    sq = (d * d).astype(f)
-    ss = ((sq[:, 0] + sq[:, 1]).astype(f) + sq[:, 2]).astype(f)
-    length = np.sqrt(ss.astype(np.float64)).astype(f)
-    inv = (1.0 / length.astype(np.float64)).astype(f)
-    return (d * inv[:, None]).astype(f)
 
 
 def _check_records(tris, spheres, cam, cfg, expect_wide=False, min_x=0):
