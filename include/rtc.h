@@ -243,6 +243,28 @@ int rtc_scene_sphere_split(const RtcDeviceScene *s);
 int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
                           const RtcRenderDesc *d, void *dColors, float *dAccum,
                           unsigned long long *dSegments, void *stream);
+/* Progressive rendering: a frame's samples in resumable passes (main.c:95-100 with the accumulationCount loop cut into
+ * ranges).  The launch evaluates samples range->first .. range->first + range->count - 1 of every selected pixel, in order;
+ * d->spp stays the frame's accumulationCount and every sample is weighted (float)(1. / d->spp) (main.c:99).  A pixel's
+ * whole resume state is 16 bytes, both buffers required, read and written: dAccum (as rtc_render_rows_async's) and
+ * dRngState, one unsigned per pixel at launchRow * width + x (compact in launch-row order like dAccum).  With first == 0
+ * neither is read: the pixel starts from the seed x + y * width and +0.  With first > 0 it starts from the stored state
+ * and sum.  After the launch dAccum is the reference's accumulatedColor after first + count iterations of main.c:98-99,
+ * dRngState its rngState at that point (a pixel whose primary ray misses draws nothing: its state stays the seed, which
+ * the first pass writes), dColors vec3ToColor of that sum -- a partial frame is darker by done / spp; scaling a preview
+ * is the caller's business.  Passes [0, a), [a, b), .., [z, spp) leave the sum, the Color and the state of one launch of
+ * spp samples, bit for bit, and dSegments counter [0] adds up to that launch's ([1], the queries traced, counts one primary
+ * trace per pass with RTC_F_HOIST_PRIMARY).  The caller keeps the scene, the camera, d and the three buffers the same
+ * across the passes of a frame and orders the passes on one stream (each pass is complete at `stream`, like a launch
+ * without RTC_F_OVERLAP; other launches on the scene may come between them).  RTC_EINVAL, with nothing enqueued: a null
+ * range, dAccum or dRngState; first < 0, count <= 0 or first + count > d->spp; RTC_F_OVERLAP (an unjoined sky pass would
+ * race the next pass's read of the accumulator; pipelining passes is not offered).  rtc_render, rtc_render_multi,
+ * rtc_frame_loop and the CLI render whole frames only. */
+typedef struct RtcSampleRange { int first, count; } RtcSampleRange;   /* samples [first, first+count) of d->spp */
+int rtc_render_samples_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                             const RtcRenderDesc *d, const RtcSampleRange *range,
+                             void *dColors, float *dAccum, unsigned int *dRngState,
+                             unsigned long long *dSegments, void *stream);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */
@@ -294,6 +316,10 @@ int rtc_plan_sim_launch(RtcPlanSim *sim, const RtcRenderDesc *d, unsigned long l
 /* The simulated scene's spheres (0 by default) and whether its upload gate would allow the split launch for them; a
  * launch with d->trianglesOnly renders none. */
 int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
+/* Makes the next rtc_plan_sim_launch (only) a pass of rtc_render_samples_async: samples [first, first + count) of its
+ * d->spp, the RNG-state buffer's identity (footprint resource 8).  That launch returns RTC_EINVAL where the entry point
+ * would (a bad range, RTC_F_OVERLAP, no accumulator or state buffer). */
+int rtc_plan_sim_set_sample_range(RtcPlanSim *sim, int first, int count, unsigned long long rngBuffer);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the

@@ -48,6 +48,7 @@ from ._abi import (  # noqa: F401
     RtcError,
     RtcLoopStats,
     RtcRenderDesc,
+    RtcSampleRange,
     RtcStats,
     Scene,
     Vec3,
@@ -60,7 +61,7 @@ __all__ = [
     "loadOBJTriangles", "parseTriangleFile", "default_spheres", "default_scene", "camera_basis", "RenderConfig",
     "render", "render_multi", "DeviceScene", "vec3ToColor", "write_bmp", "rayTriangle", "raySphere",
     "getEnvironmentLight", "random_sequences", "device_count", "lib", "TRIANGLE_DT", "SPHERE_DT", "RAY_DT",
-    "SCENE_DT", "RtcError",
+    "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -246,6 +247,56 @@ class DeviceScene:
                                           C.c_void_p(segments_ptr) if segments_ptr else None,
                                           C.c_void_p(stream) if stream else None), "rtc_render_rows_async")
 
+    def render_samples_async(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, first: int, count: int,
+                             colors_ptr: int, accum_ptr: int, rng_ptr: int, segments_ptr: int | None = None,
+                             stream: int | None = None):
+        """rtc_render_samples_async: samples [first, first + count) of cfg.spp for every selected pixel, from and into the
+        accumulator (float32 [rows, W, 3]) and the RNG states (uint32 [rows, W]) -- a pass of a progressive frame.  Both
+        are required; with first == 0 neither is read.  After passes covering [0, spp) in order the buffers and the Color
+        frame are those of one launch of spp samples, bit for bit.  Scene, camera, cfg and buffers stay the same across a
+        frame's passes, which are ordered on one stream; cfg.overlap is refused."""
+        d = cfg.desc()
+        rg = RtcSampleRange(int(first), int(count))
+        check(lib().rtc_render_samples_async(self._h, C.byref(scene), C.byref(cam), C.byref(d), C.byref(rg),
+                                             C.c_void_p(colors_ptr) if colors_ptr else None,
+                                             C.c_void_p(accum_ptr) if accum_ptr else None,
+                                             C.c_void_p(rng_ptr) if rng_ptr else None,
+                                             C.c_void_p(segments_ptr) if segments_ptr else None,
+                                             C.c_void_p(stream) if stream else None), "rtc_render_samples_async")
+
+    def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
+        """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with
+        `state` -- a frame saved earlier, load_progress -- to the samples it still lacks).  It owns the three device
+        buffers (torch tensors on the current device) and after each pass yields (samples_done, colors uint8 [rows, W, 3],
+        accum float32 [rows, W, 3]) as host arrays: the reference's frame after samples_done iterations of main.c:98-99,
+        darker than the finished one by samples_done / spp.  self.progress is then the frame's ProgressState (for
+        save_progress).  Stop iterating to cancel."""
+        import torch
+
+        passes = [int(c) for c in passes]
+        done = state.samples_done if state is not None else 0
+        if state is not None:
+            state.check(cfg)
+        if any(c <= 0 for c in passes) or done + sum(passes) != cfg.spp:
+            raise ValueError(f"render_progressive: passes {passes} after {done} samples do not sum to spp = {cfg.spp}")
+        rows = cfg.rows()
+        colors = torch.zeros((rows, cfg.width, 3), dtype=torch.uint8, device="cuda")
+        if state is not None:
+            accum = torch.from_numpy(np.ascontiguousarray(state.accum, np.float32)).cuda()
+            rng = torch.from_numpy(np.ascontiguousarray(state.rng, np.uint32).view(np.int32)).cuda()
+        else:
+            accum = torch.zeros((rows, cfg.width, 3), dtype=torch.float32, device="cuda")
+            rng = torch.zeros((rows, cfg.width), dtype=torch.int32, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+        for count in passes:
+            self.render_samples_async(scene, cam, cfg, done, count, colors.data_ptr(), accum.data_ptr(), rng.data_ptr(),
+                                      None, st)
+            done += count
+            torch.cuda.synchronize()
+            host_accum = accum.cpu().numpy()
+            self.progress = ProgressState(host_accum, rng.cpu().numpy().view(np.uint32), done, ProgressState.fields_of(cfg))
+            yield done, colors.cpu().numpy(), host_accum
+
     @property
     def chain_wgs(self) -> int:
         """rtc_render_chain's workgroups per CU for whole frames, chosen at upload (rtc_scene_chain_wgs)."""
@@ -319,6 +370,47 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class ProgressState:
+    """A progressive frame between two passes (DeviceScene.render_progressive): per pixel the float accumulator and the RNG
+    state -- 16 bytes, all a pass needs to go on --, the samples done, and the RenderConfig fields that decide the
+    pixels' values (a frame is continued with the same ones; the scene and the camera are the caller's to keep)."""
+    accum: np.ndarray  # float32 [rows, W, 3]
+    rng: np.ndarray  # uint32 [rows, W]
+    samples_done: int
+    cfg: dict
+
+    FIELDS = ("width", "height", "spp", "max_bounce", "triangles_only", "row_start", "row_stride", "row_band",
+              "debug_bounces")
+
+    @staticmethod
+    def fields_of(cfg: RenderConfig) -> dict:
+        return {k: int(getattr(cfg, k)) for k in ProgressState.FIELDS}
+
+    def check(self, cfg: RenderConfig) -> None:
+        if self.cfg != ProgressState.fields_of(cfg):
+            raise ValueError(f"the saved frame was rendered with {self.cfg}, not {ProgressState.fields_of(cfg)}")
+        if self.accum.shape != (cfg.rows(), cfg.width, 3) or self.rng.shape != (cfg.rows(), cfg.width):
+            raise ValueError("the saved frame's buffers do not have the launch's shape")
+        if not 0 < self.samples_done <= cfg.spp:
+            raise ValueError(f"the saved frame has {self.samples_done} of {cfg.spp} samples")
+
+
+def save_progress(path: str, state: ProgressState) -> None:
+    """Write a progressive frame's state as an .npz on the host (np.savez: `path` gets the suffix when it lacks it), so
+    that a later process can finish the frame (load_progress, render_progressive(..., state=...)) bit-identically."""
+    np.savez(path, accum=np.ascontiguousarray(state.accum, np.float32), rng=np.ascontiguousarray(state.rng, np.uint32),
+             samples_done=np.int64(state.samples_done), cfg_keys=np.array(list(state.cfg)),
+             cfg_values=np.array([state.cfg[k] for k in state.cfg], np.int64))
+
+
+def load_progress(path: str) -> ProgressState:
+    """The ProgressState save_progress wrote."""
+    with np.load(path) as z:
+        cfg = {str(k): int(v) for k, v in zip(z["cfg_keys"], z["cfg_values"])}
+        return ProgressState(z["accum"].astype(np.float32), z["rng"].astype(np.uint32), int(z["samples_done"]), cfg)
 
 
 def copy_async(dst_ptr: int, src_ptr: int, nbytes: int, blocks: int = 32, stream: int | None = None) -> None:

@@ -65,6 +65,10 @@ class RtcRenderDesc(C.Structure):
     ]
 
 
+class RtcSampleRange(C.Structure):  # samples [first, first + count) of RtcRenderDesc.spp (rtc_render_samples_async)
+    _fields_ = [("first", C.c_int), ("count", C.c_int)]
+
+
 class RtcStats(C.Structure):
     _fields_ = [
         ("renderMs", C.c_double),
@@ -138,7 +142,7 @@ EXPORTS = [
     "rtc_render", "rtc_render_multi", "rtc_last_multi_info",
     "rtc_scene_upload", "rtc_scene_release", "rtc_rows_selected", "rtc_render_rows_async", "rtc_scene_set_timing", "rtc_scene_kernel_times",
     "rtc_bounce_hit_share", "rtc_scene_chain_wgs", "rtc_bounce_hit_share_all", "rtc_scene_sphere_split",
-    "rtc_plan_sim_set_spheres", "rtc_plan_sim_regions",
+    "rtc_plan_sim_set_spheres", "rtc_plan_sim_regions", "rtc_render_samples_async", "rtc_plan_sim_set_sample_range",
     "rtc_scene_set_geometry_event", "rtc_scene_set_frame_event",
     "rtc_deinterleave_async", "rtc_deinterleave_bands_async", "rtc_copy_async", "rtc_copy_d2h_dma", "rtc_copy_rows_d2h_dma", "rtc_host_register",
     "rtc_host_unregister", "rtc_plan_sim_create", "rtc_plan_sim_launch", "rtc_plan_sim_release", "rtc_frame_loop", "rtc_frame_loop_cameras", "rtc_dma_pending", "rtc_dma_debug_inflight",
@@ -222,6 +226,10 @@ def lib() -> C.CDLL:
     L.rtc_rows_selected.argtypes = [C.POINTER(RtcRenderDesc)]
     L.rtc_render_rows_async.argtypes = [vp, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc), vp, vp,
                                         vp, vp]
+    if hasattr(L, "rtc_render_samples_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_render_samples_async.argtypes = [vp, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
+                                               C.POINTER(RtcSampleRange), vp, vp, vp, vp, vp]
+        L.rtc_plan_sim_set_sample_range.argtypes = [vp, ip, ip, C.c_ulonglong]
     L.rtc_deinterleave_async.argtypes = [vp, ip, ip, ip, ip, vp, vp]
     if hasattr(L, "rtc_deinterleave_bands_async"):  # (absent from round-4 libraries loaded for A/B timing)
         L.rtc_deinterleave_bands_async.argtypes = [vp, ip, ip, ip, ip, ip, vp, vp]

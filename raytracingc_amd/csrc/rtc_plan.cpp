@@ -94,6 +94,15 @@ Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uin
     return r;
 }
 
+void set_sample_range(Request &r, int first, int count, uint64_t rngState)
+{
+    r.resume = true;
+    r.sampleFirst = first;
+    r.sampleCount = count;
+    r.rngState = rngState;
+    r.flags &= ~RTC_F_OVERLAP; /* (the entry point refuses it) */
+}
+
 void plan_launch(const State &s, const Request &r, Plan &p)
 {
     memset(&p, 0, sizeof p);
@@ -108,6 +117,8 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     }
     const size_t px = (size_t)r.width * (size_t)r.rows;
     p.debug = (r.flags & RTC_F_DEBUG_BOUNCES) != 0;
+    p.resume = r.resume;
+    p.resumeRead = r.resume && r.sampleFirst > 0;
     /* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB) */
     p.cull = !(r.flags & RTC_F_NO_TILE_CULL) && r.maskWords <= 6144;
     /* the split launch (rtc_render_chain + the sky pass): every triangle-only scene, and the sphere scenes sphere_split
@@ -126,7 +137,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     p.wideItems = r.width > kItemCoordMax || r.rows > kItemCoordMax;
     /* RTC_F_OVERLAP: the sky pass is not joined into the caller's stream (a launch that counts segments joins: the
      * reduction reads the sky pass's counters) */
-    p.overlap = (r.flags & RTC_F_OVERLAP) && p.fused && !r.segments;
+    p.overlap = (r.flags & RTC_F_OVERLAP) && p.fused && !r.segments && !r.resume;
     p.half = p.overlap ? s.flip : 0;
     /* small shares (row stride > 1, <= kInlineSumPixels) sum in-kernel and, pipelined, prepare, cull and run their
      * geometry kernel on one of the two cull streams by slot parity; so do whole pipelined frames of more pixels
@@ -187,7 +198,8 @@ void plan_launch(const State &s, const Request &r, Plan &p)
         p.cullPrio = p.smallShare && px > 400000;
         /* deferred accumulation slots (joined whole frames; small shares and the alternating streams sum in-kernel) */
         if (r.spp > 0 && !(r.flags & RTC_F_CHAIN_INLINE) && !p.smallShare && !p.chainOnCs) {
-            const size_t per = (size_t)r.spp * kSampleSlotBytes + sizeof(int);
+            /* (a pass: slots for its own samples, [item][sampleCount]) */
+            const size_t per = (size_t)(r.resume ? r.sampleCount : r.spp) * kSampleSlotBytes + sizeof(int);
             const size_t cap = std::min<size_t>(px, kSampleBufBudget / per);
             p.samplesNeed = cap * per + 256;
             p.samplesGrow = p.samplesNeed > s.samplesCap;
@@ -207,6 +219,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     bind(p.sampleCap > 0, {kBufSamples});
     bind(r.key.accum != 0, {kBufAccum});
     bind(r.segments, {kBufSegSlots, kBufCallerSegments});
+    bind(r.resume, {kBufRngState});
 
     if (p.cs != kStCaller) {
         /* the cull stream runs this launch's first kernels: after everything the caller enqueued before the launch and
@@ -272,6 +285,18 @@ void plan_launch(const State &s, const Request &r, Plan &p)
                 n.flip = (s.flip + 1) % kSlots;
                 return;
             }
+            if (p.resume) {
+                /* a pass: every pixel kernel on the caller's stream, the sky pass first (set_sample_range) */
+                E.kernel(kStCaller, kKSky);
+                E.kernel(kStCaller, kKChain);
+                if (p.sampleCap > 0)
+                    E.kernel(kStCaller, kKAccum);
+                E.record(kStCaller, kEvGeometry);
+                if (r.segments)
+                    E.kernel(kStCaller, kKReduce);
+                E.record(kStCaller, kEvFrame);
+                return;
+            }
             E.wait(kStSide, kEvFork);
             E.kernel(kStSide, kKSky);
             E.record(kStSide, kEvJoin);
@@ -312,7 +337,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
 
 namespace {
 /* Every access of every kernel: a row counts when the launch binds its buffer and its predicate holds */
-enum When : int { kAlways, kIfMerge, kIfNotMerge, kIfPrepCounts };
+enum When : int { kAlways, kIfMerge, kIfNotMerge, kIfPrepCounts, kIfResumeRead };
 struct Touch {
     int kernel, buf, access, when;
 };
@@ -340,6 +365,15 @@ const Touch kTouches[] = {
     {kKRender, kBufOrder, kRead, kAlways},        {kKRender, kBufColors, kKeyedWrite, kAlways},
     {kKRender, kBufAccum, kKeyedWrite, kAlways},  {kKRender, kBufSegSlots, kAtomic, kAlways},
     {kKReduce, kBufSegSlots, kWrite, kAlways},    {kKReduce, kBufCallerSegments, kWrite, kAlways},
+    /* a pass (the state buffer is bound in a pass only): every pixel kernel is declared to write the states
+     * and, past the frame's first pass, to read them and the accumulator -- a superset (the accumulate pass touches no
+     * state, the sky pass writes it in the first pass only) */
+    {kKSky, kBufRngState, kKeyedWrite, kAlways},   {kKChain, kBufRngState, kKeyedWrite, kAlways},
+    {kKAccum, kBufRngState, kKeyedWrite, kAlways}, {kKRender, kBufRngState, kKeyedWrite, kAlways},
+    {kKSky, kBufRngState, kRead, kIfResumeRead},   {kKChain, kBufRngState, kRead, kIfResumeRead},
+    {kKAccum, kBufRngState, kRead, kIfResumeRead}, {kKRender, kBufRngState, kRead, kIfResumeRead},
+    {kKSky, kBufAccum, kRead, kIfResumeRead},      {kKChain, kBufAccum, kRead, kIfResumeRead},
+    {kKAccum, kBufAccum, kRead, kIfResumeRead},    {kKRender, kBufAccum, kRead, kIfResumeRead},
 };
 } // namespace
 
@@ -348,10 +382,13 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
     /* the resources outside the slot, in Buf order: their kind and identity, one unit each */
     const struct { int res; unsigned long long id; } outside[kBufs - kScratchRegions] = {
         {kResPrim, (unsigned long long)p.half}, {kResGeoSet, p.geoSet}, {kResGeoSet, p.geoSetNext}, {kResSamples, 0},
-        {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0}};
+        {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0},
+        {kResRngState, r.rngState}};
     int k = 0;
     for (const Touch &t : kTouches) {
-        const bool when = t.when == kAlways || (t.when == kIfPrepCounts ? p.prepCounts : p.merge == (t.when == kIfMerge));
+        const bool when = t.when == kAlways || (t.when == kIfResumeRead ? p.resumeRead
+                                                : t.when == kIfPrepCounts ? p.prepCounts
+                                                                          : p.merge == (t.when == kIfMerge));
         if (t.kernel != kernel || !p.binds(t.buf) || !when)
             continue;
         if (k < max && t.buf < kScratchRegions)
@@ -372,6 +409,9 @@ struct RtcPlanSim {
     rtcplan::SceneShape shape; /* rtc_plan_sim_set_spheres: 0 spheres by default */
     int legacy;
     rtcplan::Plan last; /* rtc_plan_sim_regions */
+    bool ranged;        /* rtc_plan_sim_set_sample_range: the next launch is a pass */
+    int first, count;
+    unsigned long long rngBuffer;
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -396,6 +436,15 @@ extern "C" int rtc_plan_sim_set_spheres(RtcPlanSim *s, int sphereCount, int gate
     return 0;
 }
 
+extern "C" int rtc_plan_sim_set_sample_range(RtcPlanSim *s, int first, int count, unsigned long long rngBuffer)
+{
+    if (!s)
+        return RTC_EINVAL;
+    s->ranged = true;
+    s->first = first, s->count = count, s->rngBuffer = rngBuffer;
+    return 0;
+}
+
 extern "C" int rtc_plan_sim_release(RtcPlanSim *s)
 {
     delete s;
@@ -411,6 +460,13 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
     rtcplan::Request r = rtcplan::make_request(*d, rtc_rows_selected(d), s->shape, stream, colors, accum, segments != 0,
                                                cam, env);
     r.legacySlotLayout = s->legacy != 0;
+    if (s->ranged) { /* a pass, refused as rtc_render_samples_async refuses it; the range is consumed either way */
+        s->ranged = false;
+        if (s->first < 0 || s->count <= 0 || s->first > d->spp - s->count || (d->flags & RTC_F_OVERLAP) || !accum ||
+            !s->rngBuffer)
+            return RTC_EINVAL;
+        rtcplan::set_sample_range(r, s->first, s->count, s->rngBuffer);
+    }
     rtcplan::Plan &p = s->last;
     rtcplan::plan_launch(s->st, r, p);
     s->st = p.after;
@@ -422,9 +478,9 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
         ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
         if (o.kind != rtcplan::kOpKernel)
             continue;
-        rtcplan::Footprint f[16];
-        const int k = rtcplan::kernel_footprint(p, r, o.kernel, f, 16);
-        for (int j = 0; j < k && j < 16; ++j, ++nf)
+        rtcplan::Footprint f[24];
+        const int k = rtcplan::kernel_footprint(p, r, o.kernel, f, 24);
+        for (int j = 0; j < k && j < 24; ++j, ++nf)
             if (fp && nf < maxFp) {
                 unsigned long long *q = fp + 6 * (size_t)nf;
                 q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;

@@ -111,6 +111,11 @@ struct Request {
     float origin[3];
     bool legacySlotLayout; /* test hook: round 5's broken layout (slot h at h x this launch's slot size) */
     bool noMerge;          /* the sky pass beside the geometry kernel even where it could follow it (A/B) */
+    /* a pass of rtc_render_samples_async (set_sample_range): samples [sampleFirst, sampleFirst + sampleCount)
+     * of the frame's spp, from and into the caller's accumulator and RNG-state buffer */
+    bool resume;
+    int sampleFirst, sampleCount;
+    uint64_t rngState;
 };
 
 /* the scene's shape as the planner needs it (RtcDeviceScene; rtc_plan_sim_create / _set_spheres) */
@@ -123,6 +128,12 @@ struct SceneShape {
  * nine dims of the launch; legacySlotLayout and noMerge are left clear */
 Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uint64_t stream, uint64_t colors,
                      uint64_t accum, bool segments, const float cam[13], const float env[14]);
+
+/* Makes r a pass: samples [first, first + count) of r.spp (the caller has checked the range), the RNG-state buffer's
+ * identity.  A pass is never overlapped: its sky pass is joined, and runs on the caller's stream before the geometry
+ * kernel -- both read and rewrite the accumulator (disjoint pixels, which the footprints do not tell apart) -- and it
+ * never takes the alternating cull streams. */
+void set_sample_range(Request &r, int first, int count, uint64_t rngState);
 
 /* The launch-scoped buffers: the regions of one scratch slot, in slot order, then the resources outside it */
 enum Buf : int {
@@ -140,6 +151,7 @@ enum Buf : int {
     kBufSamples,                /* the deferred sample slots */
     kBufSegSlots,
     kBufColors, kBufAccum, kBufCallerSegments, /* the caller's */
+    kBufRngState,               /* the caller's per-pixel RNG states (a pass, Request::resume) */
     kBufs
 };
 struct Region {
@@ -149,6 +161,8 @@ struct Region {
 struct Plan {
     bool empty;          /* no rows: only the caller's hooks are recorded */
     bool cull, fused, chain, overlap, smallShare, chainOnCs, superCull, debug;
+    bool resume;         /* a pass (Request::resume): joined, one stream, the sky pass before the geometry kernel */
+    bool resumeRead;     /* ... that starts from the stored accumulator and states (sampleFirst > 0) */
     bool merge;          /* the sky pass follows the geometry kernel and writes every pixel's Color in whole lines */
     int half;            /* the scratch slot */
     int cs, gs;          /* the culls' stream and the geometry kernel's (Stream) */
@@ -182,7 +196,7 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 
 /* The memory one kernel of a plan touches, for the ordering test: resource kinds and byte ranges */
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
-                 kResAccum = 6, kResCallerSegments = 7 };
+                 kResAccum = 6, kResCallerSegments = 7, kResRngState = 8 };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;

@@ -107,6 +107,11 @@ struct RenderParams {
     const DevCluster *__restrict__ chunks;
     int chunkCount;
     int clusterCount, clusterCull;
+    /* rtc_render_samples_async: the first sample of the pass; > 0: the pixel kernels start from rngState and
+     * accum.  (In the 4 bytes of padding the struct had here: no other field moves, so every kernel of the launches without
+     * a sample range reads its arguments where it did.)  A pass carries spp = its sample count and invSpp = 1 / the
+     * frame's accumulationCount. */
+    int sampleFirst;
     const unsigned long long *__restrict__ tileMask; /* null: primary segments test every triangle */
     const unsigned long long *__restrict__ pixMask;  /* per 8x8 tile: pixels with a primary candidate (bit i =
                                                        pixel i, row-major); the others see only the sky */
@@ -130,7 +135,13 @@ struct RenderParams {
      * + bit]), rtc_render_chain each item's Color bytes (geoColor[item], bytes 0-2), and the sky pass -- after it -- every
      * pixel's Color in whole lines */
     unsigned *__restrict__ pixItem;
-    unsigned *__restrict__ geoColor;
+    /* rngState (passes only, the RESUME instantiations): one state per pixel at launch row * width + x.  It shares
+     * geoColor's place -- a pass never merges its sky pass (rtcplan), and only RESUME kernels, which have no merged path,
+     * run in it -- so that the struct keeps its size and layout. */
+    union {
+        unsigned *__restrict__ geoColor;
+        unsigned *__restrict__ rngState;
+    };
     SampleSlot *__restrict__ sampleBuf; /* rtc_render_chain, deferred accumulation: [item][spp] radiance * (1/spp) */
     int *__restrict__ itemPix;      /* [item] the pixel's offset in the launch's Color rows */
     int sampleCap;                  /* items with a slot in sampleBuf; items beyond it accumulate in-kernel */
@@ -211,6 +222,10 @@ template <typename PT, typename T> __device__ __forceinline__ T karg_field(size_
     return karg_at<T>(off);
 }
 #define KARG(field) karg_field<decltype(P), decltype(RenderParams::field)>(offsetof(RenderParams, field))
+
+static_assert(offsetof(RenderParams, tileMask) == 80 && offsetof(RenderParams, sampleFirst) == 76 &&
+                  offsetof(RenderParams, env) == 344 && sizeof(RenderParams) == 432,
+              "RenderParams keeps the layout the kernels of ordinary launches were compiled against");
 
 constexpr int kTileW = 16, kTileH = 16, kBlock = 256;
 
@@ -1009,7 +1024,9 @@ __global__ __launch_bounds__(kSegSlots) void rtc_reduce_segments(unsigned long l
 }
 
 
-template <bool SPHERES, bool DEBUG>
+/* RESUME (a pass of rtc_render_samples_async): the lane's RNG state and accumulator are loaded before the
+ * sample loop when the pass is not the frame's first, and stored after it; P.spp is the pass's sample count. */
+template <bool SPHERES, bool DEBUG, bool RESUME = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) void rtc_render_kernel(
     RenderParams P)
 {
@@ -1051,6 +1068,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
     }
 
     V3 acc{0.f, 0.f, 0.f};
+    if constexpr (RESUME) {
+        if (valid && P.sampleFirst > 0) { /* the reference's rngState and accumulatedColor after sampleFirst samples */
+            const size_t o = (size_t)r * (size_t)P.width + (size_t)x;
+            rng = P.rngState[o];
+            acc = V3{P.accum[3 * o], P.accum[3 * o + 1], P.accum[3 * o + 2]};
+        }
+    }
     bool alive = valid && P.spp > 0 && P.maxBounce > 0;
     if (DEBUG && valid && !(P.maxBounce > 0)) {
         /* calcDebugColor with no bounce loop returns lerp(BLACK, WHITE, 0 / (float)maxBounce) */
@@ -1195,6 +1219,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) voi
             P.accum[3 * o + 1] = acc.y;
             P.accum[3 * o + 2] = acc.z;
         }
+        if constexpr (RESUME)
+            P.rngState[o] = rng; /* a pixel without a hit drew nothing: its seed */
     }
 #ifdef RTC_DIAG
     if (g_rtc_diag && lane == 0) {
@@ -1235,7 +1261,13 @@ __device__ __forceinline__ void wave_lds_sync()
  * the 1/4 share took 3.5 % longer with them, profiles/r04_zd_ab_sky_wg.log). */
 /* GENERAL (round 6): the launch may merge (P.geoColor), hoist, write the accumulator or count segments; the pipelined
  * faithful whole frames run an instantiation without that code (56 VGPRs and no SGPR spill instead of 59 and 8). */
-template <int kSkyWaves, bool GENERAL>
+/* RESUME (a pass of rtc_render_samples_async; GENERAL): the sum starts from the stored accumulator when the
+ * pass is not the frame's first; the first pass writes the pixel's state, its seed x + y * width (a sky pixel draws
+ * nothing, so later passes leave it).  The shortcuts and a sum that does not start at +0: the sun-term skip (sun_vanishes)
+ * concerns e + sv alone, whatever it is added to; environment_miss_term needs a sum that is not -0, and the stored sum is
+ * +0 plus such terms, which in round-to-nearest is never -0; the hoisted term is one value added P.spp times either way.
+ * A pass never merges (geoColor's place holds rngState). */
+template <int kSkyWaves, bool GENERAL, bool RESUME = false>
 __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(RTC_SKY_WAVES))) void rtc_render_sky_rows(
     RenderParams P)
 {
@@ -1260,7 +1292,7 @@ __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(
     const bool valid = inFrame && !geo; /* a sky pixel: this kernel renders it */
     /* merged (P.geoColor): the geometry kernel has finished; its pixels' bytes are written here too, so every strip is
      * whole lines.  Their words are requested now and used after the sky loop. */
-    const bool merged = GENERAL && P.geoColor != nullptr; /* (uniform) */
+    const bool merged = GENERAL && !RESUME && P.geoColor != nullptr; /* (uniform) */
     const bool writes = merged ? inFrame : valid;
     const unsigned long long mine = __ballot(writes);
     if (mine == 0ull)
@@ -1285,6 +1317,12 @@ __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(
     const int y = launch_row_y(P, r);
     const V3 dir = primary_dir(P, x, y);
     V3 acc{0.f, 0.f, 0.f};
+    if constexpr (RESUME) {
+        if (valid && P.sampleFirst > 0) {
+            const size_t o = 3 * ((size_t)r * (size_t)P.width + (size_t)x);
+            acc = V3{P.accum[o], P.accum[o + 1], P.accum[o + 2]};
+        }
+    }
     if (valid && P.spp > 0 && P.maxBounce > 0) {
         /* hoisted mode evaluates the primary ray's miss once (a function of the pixel, like its closest hit), faithful
          * mode every sample */
@@ -1334,6 +1372,10 @@ __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(
         P.accum[o] = acc.x;
         P.accum[o + 1] = acc.y;
         P.accum[o + 2] = acc.z;
+    }
+    if constexpr (RESUME) {
+        if (valid && P.sampleFirst == 0)
+            P.rngState[(size_t)r * (size_t)P.width + (size_t)x] = (unsigned)(x + y * P.width); /* main.c:95 */
     }
     if (GENERAL)
         flush_counters(P, segCalls, segTraced, 0ull, lane);
@@ -1880,7 +1922,13 @@ __device__ __forceinline__ ChainStage chain_stage(const RenderParams &P, unsigne
  * sphere's normal and material at a sphere hit); a hit draws the same 7 values on a sphere as on a triangle
  * (RandomDiretion and the roulette), so the state-indexed chain, the draw table and the walk are unchanged.  Without it
  * none of that code is in the kernel. */
-template <bool MULTI, bool COUNT, bool HITS, bool GENERAL, bool SPHERES = false>
+/* RESUME (GENERAL launches only; DESIGN §3.8, a pass of rtc_render_samples_async): P.spp is the pass's sample count.  When the
+ * pass is not the frame's first, the item's seed is the pixel's stored state -- the reference's rngState after the samples
+ * so far, so the chain S_j of the remaining samples is indexed from it exactly as the whole frame's is from x + y * width --
+ * and an item that sums in-kernel starts from the stored accumulator (a deferred item's sum: rtc_accumulate_samples_resume).
+ * At the item's end one lane stores the state 7 jn draws on: jn is the chain's position after the pass's last sample, the
+ * hits so far (a primary miss or maxBounce == 0 leaves jn = 0, the state where it was). */
+template <bool MULTI, bool COUNT, bool HITS, bool GENERAL, bool SPHERES = false, bool RESUME = false>
 __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC_CHAIN_WAVES))) void rtc_render_chain(
     RenderParams P)
 {
@@ -2034,7 +2082,13 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
         if (counting)
             for (int w = 0; w < P.maskWords; ++w)
                 L += (unsigned)__popcll(mask[w]);
-        const unsigned seed = (unsigned)(x + y * KARG(width)); /* main.c:95 */
+        unsigned seedOf = (unsigned)(x + y * KARG(width)); /* main.c:95 */
+        if constexpr (RESUME) {
+            if (KARG(sampleFirst) > 0) /* (uniform; every lane loads the pixel's dword) */
+                seedOf = (unsigned)__builtin_amdgcn_readfirstlane(
+                    (int)gload(KARG(rngState), (size_t)r * (size_t)KARG(width) + (size_t)x));
+        }
+        const unsigned seed = seedOf;
         const bool deferred = GENERAL && it < P.sampleCap; /* wave-uniform */
         Closest prim{999999.f, -1};
         if (GENERAL && P.hoist && P.spp > 0 && P.maxBounce > 0) {
@@ -2049,6 +2103,10 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
         DMARK(dcur, 15); /* item setup */
         /* in-kernel sums (items without a deferred slot): the pixel's accumulator (main.c:97), component c in lane c */
         float acc = 0.f;
+        if constexpr (RESUME) {
+            if (KARG(sampleFirst) > 0 && !deferred && lane < 3)
+                acc = __uint_as_float(gload(KARG(accum), 3 * ((size_t)r * (size_t)KARG(width) + (size_t)x) + (size_t)lane));
+        }
         int k = 0;       /* samples accumulated */
         unsigned jn = 0; /* state index (in units of 7 draws) of sample k */
         while (k < P.spp && P.maxBounce > 0) {
@@ -2318,10 +2376,14 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
             }
             DMARK(dcur, 7); /* walk and sums */
         }
+        if constexpr (RESUME) {
+            if (lane == 0)
+                P.rngState[(size_t)r * (size_t)KARG(width) + (size_t)x] = rng_advance(seed, 7u * jn);
+        }
         if (deferred) {
             if (lane == 0)
                 P.itemPix[it] = r * KARG(width) + x;
-        } else if (P.geoColor) { /* merged sky pass: the pixel's three bytes as one word of its item */
+        } else if (!RESUME && P.geoColor) { /* merged sky pass: the pixel's three bytes as one word of its item */
             const unsigned b = float_to_u8(acc);
             const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)b, 0) |
                                (unsigned)__builtin_amdgcn_readlane((int)b, 1) << 8 |
@@ -2408,6 +2470,13 @@ static hipError_t launch_sphere_cull(dim3 grid, size_t sh, hipStream_t st, hipEv
                                      unsigned long long *mask, unsigned *weight, unsigned long long *pixMask);
 static hipError_t launch_sphere_chain(bool multi, bool count, dim3 grid, dim3 block, size_t sh, hipStream_t st,
                                       hipEvent_t stop, const RenderParams &P);
+/* The kernels of a pass (rtc_render_samples_async, DESIGN §3.8: the RESUME instantiations and
+ * rtc_accumulate_samples_resume), launched from the end of this file for the same reason */
+static hipError_t launch_resume_sky(bool wide, dim3 grid, hipStream_t st, const RenderParams &P);
+static hipError_t launch_resume_chain(bool multi, bool count, bool spheres, dim3 grid, dim3 block, size_t sh,
+                                      hipStream_t st, hipEvent_t stop, const RenderParams &P);
+static hipError_t launch_resume_accumulate(dim3 grid, hipStream_t st, hipEvent_t stop, const RenderParams &P);
+static hipError_t launch_resume_render(bool spheres, bool debug, dim3 grid, hipStream_t st, const RenderParams &P);
 
 #ifdef RTC_AB_NO_SLOTS
 constexpr bool kAbNoSlots = true; /* timing experiment only (RTC_EXPERIMENT): deferred samples neither stored nor summed */
@@ -2421,6 +2490,7 @@ struct Launch {
     RenderParams P;
     int wgsPerCu;    /* the geometry kernel's workgroups per CU */
     size_t chainDyn; /* and its dynamic LDS */
+    bool resume;     /* a pass (rtc_render_samples_async): the RESUME kernels */
     dim3 grid() const { return dim3(pl.gridX, pl.gridY); } /* one 16x16 workgroup block each */
     /* every pointer into the scratch: a region the plan binds (rtcplan::Buf), in the launch's slot; unbound: null */
     template <typename T> T *region(int buf) const
@@ -2448,7 +2518,7 @@ static int check_arguments(const Scene *scene, const RtcCamera *cam, const RtcRe
 /* what the kernels read of the scene, the launch's shape and the camera (the plan's buffers: bind_plan) */
 static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, const RtcCamera &cam,
                                   const RtcRenderDesc &d, int rows, void *dColors, float *dAccum,
-                                  unsigned long long *dSegments)
+                                  unsigned long long *dSegments, const RtcSampleRange *range)
 {
     RenderParams P;
     memset(&P, 0, sizeof P);
@@ -2462,7 +2532,9 @@ static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, c
     P.width = d.width, P.height = d.height;
     P.rows = rows, P.rowStart = d.rowStart, P.rowStride = d.rowStride;
     P.rowBandShift = d.rowBand > 1 ? __builtin_ctz((unsigned)d.rowBand) : 0;
-    P.spp = d.spp, P.maxBounce = d.maxBounce;
+    /* a pass renders range->count samples, each weighted by the frame's (float)(1. / accumulationCount) */
+    P.spp = range ? range->count : d.spp, P.maxBounce = d.maxBounce;
+    P.sampleFirst = range ? range->first : 0;
     P.hoist = (d.flags & RTC_F_HOIST_PRIMARY) ? 1 : 0;
     P.invSpp = d.spp > 0 ? (float)(1. / (double)d.spp) : 0.f;
     P.origin = v3(cam.origin), P.ex = v3(cam.ex), P.ey = v3(cam.ey), P.ez = v3(cam.ez), P.fov = cam.fov;
@@ -2522,7 +2594,7 @@ static void bind_plan(Launch &L, int flags)
         P.wideItems = pl.wideItems;
         P.cullPrio = pl.cullPrio;
     }
-    if (pl.binds(rtcplan::kBufSamples)) {
+    if (pl.binds(rtcplan::kBufSamples)) { /* (a pass: P.spp is its sample count, as the planner sized the slots) */
         P.sampleBuf = (SampleSlot *)s->samples;
         P.itemPix = (int *)(s->samples + (size_t)pl.sampleCap * (size_t)P.spp * sizeof(SampleSlot));
         P.sampleCap = pl.sampleCap;
@@ -2584,7 +2656,10 @@ static int run_sky(const Launch &L, hipStream_t os, hipEvent_t)
     if (L.s->timing)
         HIP_TRY(hipEventRecord(L.s->evSky0, os));
     const dim3 grid((P.width + 63) / 64, wide ? (P.rows + 3) / 4 : P.rows);
-    HIP_TRY(launch_stop(kSky[!wide][!general], grid, dim3(wide ? 256 : 64), 0, os, nullptr, P));
+    if (L.resume)
+        HIP_TRY(launch_resume_sky(wide, grid, os, P));
+    else
+        HIP_TRY(launch_stop(kSky[!wide][!general], grid, dim3(wide ? 256 : 64), 0, os, nullptr, P));
     if (L.s->timing)
         HIP_TRY(hipEventRecord(L.s->evSky1, os));
     return 0;
@@ -2606,7 +2681,9 @@ static int run_chain(const Launch &L, hipStream_t os, hipEvent_t ev)
     const int variant = multi ? !count : count ? 2 : defer ? 3 : hits ? 4 : 5;
     if (s->timing)
         HIP_TRY(hipEventRecord(s->evHeavy0, os));
-    if (P.sphereCount > 0) /* the sphere split: GENERAL, for MULTI x COUNT */
+    if (L.resume) /* a pass: GENERAL, for MULTI x COUNT x SPHERES */
+        HIP_TRY(launch_resume_chain(multi, count, P.sphereCount > 0, cg, cb, L.chainDyn, os, ev, P));
+    else if (P.sphereCount > 0) /* the sphere split: GENERAL, for MULTI x COUNT */
         HIP_TRY(launch_sphere_chain(multi, count, cg, cb, L.chainDyn, os, ev, P));
     else
         HIP_TRY(launch_stop(kChain[variant], cg, cb, L.chainDyn, os, ev, P));
@@ -2618,7 +2695,9 @@ static int run_chain(const Launch &L, hipStream_t os, hipEvent_t ev)
 static int run_accumulate(const Launch &L, hipStream_t os, hipEvent_t ev)
 {
     const unsigned g = (unsigned)std::min<size_t>(((size_t)L.P.sampleCap + 255) / 256, 1024);
-    if (!kAbNoSlots)
+    if (L.resume)
+        HIP_TRY(launch_resume_accumulate(dim3(g), os, ev, L.P));
+    else if (!kAbNoSlots)
         HIP_TRY(launch_stop(rtc_accumulate_samples, dim3(g), dim3(256), 0, os, ev, L.P));
     else if (ev)
         HIP_TRY(hipEventRecord(ev, os));
@@ -2636,7 +2715,10 @@ static int run_render(const Launch &L, hipStream_t os, hipEvent_t)
 {
     static void (*const kRender[2][2])(RenderParams) = {{rtc_render_kernel<true, true>, rtc_render_kernel<true, false>},
                                                         {rtc_render_kernel<false, true>, rtc_render_kernel<false, false>}};
-    HIP_TRY(launch_stop(kRender[L.P.sphereCount <= 0][!L.pl.debug], L.grid(), dim3(kBlock), 0, os, nullptr, L.P));
+    if (L.resume)
+        HIP_TRY(launch_resume_render(L.P.sphereCount > 0, L.pl.debug, L.grid(), os, L.P));
+    else
+        HIP_TRY(launch_stop(kRender[L.P.sphereCount <= 0][!L.pl.debug], L.grid(), dim3(kBlock), 0, os, nullptr, L.P));
     return 0;
 }
 
@@ -2654,7 +2736,8 @@ static_assert(sizeof kPlanned / sizeof kPlanned[0] == rtcplan::kKReduce + 1, "on
  * tile cull are not enqueued (the plan's events are, so the ordering state stays true: a launch whose render kernels did
  * nothing), and `items` gets the launch's counter set and list regions */
 static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
-                       void *dColors, float *dAccum, unsigned long long *dSegments, void *stream, RtcCullItems *items)
+                       void *dColors, float *dAccum, unsigned long long *dSegments, void *stream, RtcCullItems *items,
+                       const RtcSampleRange *range = nullptr, unsigned *dRngState = nullptr)
 {
     if (!s)
         return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null scene");
@@ -2666,6 +2749,16 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
     ms->geoEvent = ms->frameEvent = nullptr;
     if (const int rc = check_arguments(scene, cam, d, dColors))
         return rc;
+    if (range) { /* rtc_render_samples_async: nothing is enqueued for a pass that is refused */
+        if (!dAccum || !dRngState)
+            return rtc_fail(RTC_EINVAL, "rtc_render_samples_async: the accumulator and the RNG-state buffer are required");
+        if (range->first < 0 || range->count <= 0 || range->first > d->spp - range->count)
+            return rtc_fail(RTC_EINVAL, "rtc_render_samples_async: samples [%d, %d + %d) are not within the frame's %d",
+                            range->first, range->first, range->count, d->spp);
+        if (d->flags & RTC_F_OVERLAP)
+            return rtc_fail(RTC_EINVAL, "rtc_render_samples_async: RTC_F_OVERLAP (an unjoined sky pass would race the next "
+                                        "pass's read of the accumulator)");
+    }
     const int rows = rtc_rows_selected(d);
     /* the scene's buffers, scratch and kernels live on s->device; the caller's current device is restored */
     RtcDeviceGuard guard(s->device);
@@ -2679,7 +2772,7 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         return 0;
     }
     static thread_local rtcplan::Plan pl;
-    Launch L{s, pl, render_params(s, *scene, *cam, *d, rows, dColors, dAccum, dSegments), 0, 0};
+    Launch L{s, pl, render_params(s, *scene, *cam, *d, rows, dColors, dAccum, dSegments, range), 0, 0, range != nullptr};
     /* every ordering decision -- slot, streams, events, which kernels, which buffers -- comes from the planner
      * (rtc_plan.h); this function executes its operations */
     const RenderParams &P = L.P;
@@ -2693,6 +2786,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         (uint64_t)(uintptr_t)st, (uint64_t)(uintptr_t)dColors, (uint64_t)(uintptr_t)dAccum, dSegments != nullptr, camKey,
         envKey);
     rq.noMerge = !RTC_SKY_MERGE;
+    if (range)
+        rtcplan::set_sample_range(rq, range->first, range->count, (uint64_t)(uintptr_t)dRngState);
     rtcplan::plan_launch(s->plan, rq, pl);
     /* the saved state claims only what has been enqueued: until every operation below is, a later launch sees none of
      * this launch's primary records or counter zeroing (it re-runs rtc_prep_primary) */
@@ -2701,6 +2796,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
     if (const int rc = grow_capacity(ms, pl))
         return rc;
     bind_plan(L, d->flags);
+    if (range) /* (after bind_plan: the state pointer lies where an ordinary launch keeps geoColor, unbound in a pass) */
+        L.P.rngState = dRngState;
     size_chain_lds(L);
     const hipStream_t streams[rtcplan::kStreams] = {st, s->cst, ms->cst2, s->side};
     hipEvent_t events[rtcplan::kEvents] = {}; /* (the caller's hooks may be unarmed: null) */
@@ -2742,6 +2839,16 @@ extern "C" int rtc_render_rows_async(const RtcDeviceScene *s, const Scene *scene
                                      unsigned long long *dSegments, void *stream)
 {
     return render_rows(s, scene, cam, d, dColors, dAccum, dSegments, stream, nullptr);
+}
+
+extern "C" int rtc_render_samples_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                                        const RtcRenderDesc *d, const RtcSampleRange *range, void *dColors,
+                                        float *dAccum, unsigned int *dRngState, unsigned long long *dSegments,
+                                        void *stream)
+{
+    if (!range)
+        return rtc_fail(RTC_EINVAL, "rtc_render_samples_async: null sample range");
+    return render_rows(s, scene, cam, d, dColors, dAccum, dSegments, stream, nullptr, range, dRngState);
 }
 
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
@@ -2857,4 +2964,74 @@ static hipError_t launch_sphere_chain(bool multi, bool count, dim3 grid, dim3 bl
     if (count)
         return launch_stop(rtc_render_chain<false, true, false, true, true>, grid, block, sh, st, stop, P);
     return launch_stop(rtc_render_chain<false, false, false, true, true>, grid, block, sh, st, stop, P);
+}
+
+/* ---- the kernels of a pass (rtc_render_samples_async; see launch_resume_sky's declaration) -------------------- */
+/* rtc_accumulate_samples for a pass: the pixel's sum goes on from the stored accumulator when the pass is not the frame's
+ * first (main.c:97-100 after sampleFirst iterations), over the pass's P.spp deferred samples in sample order.  A template
+ * (like rtc_tile_cull_sph) only so that its code is emitted here, after every kernel of the ordinary launches, and not
+ * among the non-template kernels before them */
+template <bool RESUME>
+__global__ __launch_bounds__(256) void rtc_accumulate_samples_resume(RenderParams P)
+{
+    int items = 0;
+    for (int l = 0; l < kGeoLists; ++l)
+        items += min(P.geoCount[l * kGeoCountStride], P.geoCap);
+    items = min(items, P.sampleCap);
+    for (int it = blockIdx.x * 256 + threadIdx.x; it < items; it += gridDim.x * 256) {
+        const SampleSlot *slot = P.sampleBuf + (size_t)it * (size_t)P.spp;
+        const size_t o = (size_t)P.itemPix[it];
+        f2 accxy{0.f, 0.f};
+        float accz = 0.f;
+        if (RESUME && P.sampleFirst > 0) {
+            accxy = f2{P.accum[3 * o], P.accum[3 * o + 1]};
+            accz = P.accum[3 * o + 2];
+        }
+        if (P.maxBounce > 0) {
+#pragma unroll 8
+            for (int k = 0; k < P.spp; ++k) {
+                const SampleSlot v = slot[k];
+                accxy = accxy + f2{v.x, v.y};
+                accz = accz + v.z;
+            }
+        }
+        P.colors[3 * o] = float_to_u8(accxy.x);
+        P.colors[3 * o + 1] = float_to_u8(accxy.y);
+        P.colors[3 * o + 2] = float_to_u8(accz);
+        P.accum[3 * o] = accxy.x;
+        P.accum[3 * o + 1] = accxy.y;
+        P.accum[3 * o + 2] = accz;
+    }
+}
+
+static hipError_t launch_resume_sky(bool wide, dim3 grid, hipStream_t st, const RenderParams &P)
+{
+    if (wide)
+        return launch_stop(rtc_render_sky_rows<4, true, true>, grid, dim3(256), 0, st, nullptr, P);
+    return launch_stop(rtc_render_sky_rows<1, true, true>, grid, dim3(64), 0, st, nullptr, P);
+}
+
+static hipError_t launch_resume_chain(bool multi, bool count, bool spheres, dim3 grid, dim3 block, size_t sh,
+                                      hipStream_t st, hipEvent_t stop, const RenderParams &P)
+{
+    /* <MULTI, COUNT, HITS, GENERAL, SPHERES, RESUME> */
+    static void (*const kChain[2][2][2])(RenderParams) = {
+        {{rtc_render_chain<false, false, false, true, false, true>, rtc_render_chain<false, false, false, true, true, true>},
+         {rtc_render_chain<false, true, false, true, false, true>, rtc_render_chain<false, true, false, true, true, true>}},
+        {{rtc_render_chain<true, false, false, true, false, true>, rtc_render_chain<true, false, false, true, true, true>},
+         {rtc_render_chain<true, true, false, true, false, true>, rtc_render_chain<true, true, false, true, true, true>}}};
+    return launch_stop(kChain[multi][count][spheres], grid, block, sh, st, stop, P);
+}
+
+static hipError_t launch_resume_accumulate(dim3 grid, hipStream_t st, hipEvent_t stop, const RenderParams &P)
+{
+    return launch_stop(rtc_accumulate_samples_resume<true>, grid, dim3(256), 0, st, stop, P);
+}
+
+static hipError_t launch_resume_render(bool spheres, bool debug, dim3 grid, hipStream_t st, const RenderParams &P)
+{
+    static void (*const kRender[2][2])(RenderParams) = {
+        {rtc_render_kernel<false, false, true>, rtc_render_kernel<false, true, true>},
+        {rtc_render_kernel<true, false, true>, rtc_render_kernel<true, true, true>}};
+    return launch_stop(kRender[spheres][debug], grid, dim3(kBlock), 0, st, nullptr, P);
 }
