@@ -186,6 +186,33 @@ typedef struct RtcDeviceScene RtcDeviceScene;
 int rtc_scene_upload(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
                      int device, RtcDeviceScene **out);
 int rtc_scene_release(RtcDeviceScene *s);
+/* Replace the resident scene's triangles and / or spheres (positions, normals, materials) without a new upload: one short
+ * kernel on `stream` (a refit), no host work, no synchronisation (no reference counterpart: main.c:229-243 builds its
+ * arrays once).  dTris / dSpheres are DEVICE pointers on the scene's device in the reference's own layouts (68 / 36 bytes
+ * per primitive); a null pointer leaves that kind unchanged, and its count is then 0; a count given equals the upload's --
+ * the number of primitives and the grouping of the triangles into clusters are fixed at upload.  The kernel rewrites what
+ * the upload derived from the primitives: the packed triangles (A, AB = B - A, AC = C - A in f32, the normal), the
+ * materials, the spheres, the triangles in cluster order with their aligned-normal flags, and every cluster's and chunk's
+ * bounding ball and cull margins, byte for byte what an upload of the new primitives with the old grouping would hold.
+ * The culling is exact for any ball that contains its vertices and carries its margins, so the frames are the new
+ * geometry's bit for bit, however far it moved; geometry that drifts far from the upload's clusters is only culled worse
+ * (larger, overlapping balls) and is a reason to upload again -- an update never regroups.
+ * Ordering: asynchronous on `stream`, under rtc_render_rows_async's contract (a scene serves one stream at a time; a
+ * caller that changes streams orders them).  Every launch enqueued on the scene after the call renders the new geometry,
+ * every launch enqueued before it the old one, overlapped launches (RTC_F_OVERLAP) whose kernels or sky pass are still in
+ * flight included: the scene keeps two generations of its records, the update writes the one no launch in flight reads
+ * (it waits only for launches from before the previous update) and later launches read that one.  The source buffers
+ * may be reused once `stream` has passed the call.
+ * The scheduling hints of the upload (rtc_scene_chain_wgs, the sphere split's gate rtc_scene_sphere_split) keep their
+ * values: they never change a frame.  An animation that turns an open sphere scene into a closed one keeps the route the
+ * upload chose; RTC_F_SPLIT_SPHERES and RTC_F_NO_COOP select a route per launch as before.
+ * RTC_EINVAL, with nothing enqueued: a null scene; both pointers null; a count that differs from the upload's (or is not
+ * 0 beside a null pointer); a pointer for a kind the scene was uploaded without.
+ * rtc_scene_update takes HOST arrays: it stages them on the device, waits for the device, runs the update, waits for it
+ * and restores the caller's current device (synchronous; the same refusals). */
+int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
+                           int sphereCount, void *stream);
+int rtc_scene_update(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount);
 /* Number of rows d selects (ceil((height - rowStart) / rowStride) for single rows; with bands, the full bands' rows
  * plus the last band's rows inside the frame), 0 if none. */
 int rtc_rows_selected(const RtcRenderDesc *d);
@@ -320,6 +347,15 @@ int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
  * d->spp, the RNG-state buffer's identity (footprint resource 8).  That launch returns RTC_EINVAL where the entry point
  * would (a bad range, RTC_F_OVERLAP, no accumulator or state buffer). */
 int rtc_plan_sim_set_sample_range(RtcPlanSim *sim, int first, int count, unsigned long long rngBuffer);
+/* Plans one rtc_scene_update_async on the caller's stream `stream`, in rtc_plan_sim_launch's encodings: the waits, then the
+ * refit kernel (kernel 9) with two footprint records -- it writes one generation of the scene records (resource 9, id = the
+ * generation) and may read the other -- then one u64 record (~0, 0, the generation written, 0, 0, 0).  Launches planned
+ * afterwards read that generation (their kernels' footprints name it).  rtc_plan_sim_set_update_fault breaks later updates
+ * on purpose, for the test that must catch it: mode 1 drops the update's waits, 2 keeps the slots' primary records valid,
+ * 3 writes the generation the launches in flight read; 0 mends it. */
+int rtc_plan_sim_update(RtcPlanSim *sim, unsigned long long stream, int *ops, int maxOps, unsigned long long *footprint,
+                        int maxFootprint);
+int rtc_plan_sim_set_update_fault(RtcPlanSim *sim, int mode);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the
@@ -412,6 +448,21 @@ int rtc_probe_primary_cull(const Triangle *tris, int triCount, const Scene *scen
                            const RtcRenderDesc *d, unsigned char *kept, size_t maxKept, unsigned long long *tileBits,
                            size_t maxWords, unsigned long long *pixMask, size_t maxTiles, int info[4], float *primF,
                            double *cones, unsigned char *pruned);
+/* The scene records (no reference counterpart; main.c:229-243 builds the arrays they replace), for the tests of
+ * rtc_scene_update_async.  Both write up to six arrays -- triangles (64 B each, reference order), materials (32 B), spheres
+ * (48 B), the triangles in cluster order (64 B; dword 12 = the reference index, -1 for padding, dword 13 = the
+ * aligned-normal flag), the cluster balls and the chunk balls (32 B: centre, radius, alpha, beta, gamma E, E) -- into the
+ * buffers given (null: not wanted); bytes[6] holds each buffer's capacity on entry and each array's size on return
+ * (RTC_EINVAL when a buffer is too small; call with null buffers first for the sizes).
+ * rtc_scene_records_host runs without a GPU: it clusters `tris` as rtc_scene_upload does and returns the upload's records,
+ * or with newTris (triCount of them) the records a refit of that membership to newTris must produce -- the host statement
+ * the device kernel is compared with byte for byte.  rtc_probe_scene_records synchronises the device and copies back the
+ * records a launch enqueued now would read (the current generation). */
+int rtc_scene_records_host(const Triangle *tris, int triCount, const Triangle *newTris, const Sphere *spheres,
+                           int sphereCount, void *outTris, void *outMats, void *outSpheres, void *outClTris,
+                           void *outClusters, void *outChunks, size_t bytes[6]);
+int rtc_probe_scene_records(const RtcDeviceScene *s, void *outTris, void *outMats, void *outSpheres, void *outClTris,
+                            void *outClusters, void *outChunks, size_t bytes[6]);
 
 #ifdef __cplusplus
 }

@@ -61,7 +61,7 @@ __all__ = [
     "loadOBJTriangles", "parseTriangleFile", "default_spheres", "default_scene", "camera_basis", "RenderConfig",
     "render", "render_multi", "DeviceScene", "vec3ToColor", "write_bmp", "rayTriangle", "raySphere",
     "getEnvironmentLight", "random_sequences", "device_count", "lib", "TRIANGLE_DT", "SPHERE_DT", "RAY_DT",
-    "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress",
+    "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress", "scene_records_host", "RECORD_ARRAYS",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -184,6 +184,35 @@ def _stats(st: RtcStats) -> dict:
     return {"render_ms": st.renderMs, "frame_ms": st.frameMs, "total_ms": st.totalMs, "segments": st.segments,
             "samples": st.samples, "tri_tests": st.triTests, "cluster_tests": st.clusterTests,
             "discarded_tests": st.discardedTests}
+
+
+RECORD_ARRAYS = ("tris", "mats", "spheres", "clTris", "clusters", "chunks")  # 64, 32, 48, 64, 32, 32 bytes per record
+_RECORD_WORDS = (16, 8, 12, 16, 8, 8)
+
+
+def _records(call, where: str) -> dict:
+    """The six record arrays of rtc_scene_records_host / rtc_probe_scene_records as uint32 [records, dwords]: first the
+    sizes (null buffers), then the bytes."""
+    sizes = (C.c_size_t * 6)()
+    check(call([None] * 6, sizes), where)
+    out = [np.zeros((sizes[k] // (4 * w), w), np.uint32) for k, w in enumerate(_RECORD_WORDS)]
+    check(call([_ptr(a) for a in out], sizes), where)
+    return dict(zip(RECORD_ARRAYS, out))
+
+
+def scene_records_host(tris, new_tris=None, spheres=None) -> dict:
+    """The scene records on the host, no GPU (rtc_scene_records_host): `tris` clustered as an upload clusters them and,
+    with new_tris (as many), that grouping refitted to them -- what DeviceScene(tris, spheres) followed by
+    update(new_tris) must hold, byte for byte.  Arrays of uint32 dwords by name (RECORD_ARRAYS): in clTris dword 12 is
+    the reference index (int32, -1 for padding) and dword 13 the aligned-normal flag; a ball is centre, radius, alpha,
+    beta, gamma E, E (float32 bits)."""
+    t, nt = _arr(tris, TRIANGLE_DT)
+    s, ns = _arr(spheres, SPHERE_DT)
+    n, nn = _arr(new_tris, TRIANGLE_DT)
+    if n is not None and nn != nt:
+        raise ValueError("scene_records_host: new_tris must hold as many triangles as tris")
+    return _records(lambda bufs, sizes: lib().rtc_scene_records_host(_ptr(t), nt, _ptr(n), _ptr(s), ns, *bufs, sizes),
+                    "rtc_scene_records_host")
 
 
 def render(tris, spheres, scene: Scene, cam: RtcCamera, cfg: RenderConfig, device: int = -1,
@@ -359,6 +388,49 @@ class DeviceScene:
         out = (C.c_float * 2)()
         check(lib().rtc_scene_kernel_times(self._h, out), "rtc_scene_kernel_times")
         return None if out[0] < 0 else (float(out[0]), float(out[1]))
+
+    def update(self, tris=None, spheres=None, stream: int | None = None):
+        """Replace the resident triangles and / or spheres in place (rtc_scene_update / rtc_scene_update_async): the
+        counts are the upload's, None leaves that kind unchanged.  Numpy arrays of TRIANGLE_DT / SPHERE_DT take the
+        synchronous host path.  Torch tensors on the scene's device (any dtype, count x 68 / 36 bytes, contiguous) take
+        the asynchronous path on `stream` (a hipStream_t; None: torch's current stream): every launch enqueued on the
+        scene afterwards renders the new geometry, every earlier one the old, and the tensors may be reused once the
+        stream has passed the call.  The upload's scheduling hints stay; the frames are the new geometry's bit for bit."""
+        if not self._h:
+            raise RuntimeError("DeviceScene.update: the scene has been released")
+        if tris is None and spheres is None:
+            raise ValueError("DeviceScene.update: neither triangles nor spheres")
+        on_device = [hasattr(a, "data_ptr") for a in (tris, spheres) if a is not None]
+        if not any(on_device):
+            t, nt = _arr(tris, TRIANGLE_DT)
+            s, ns = _arr(spheres, SPHERE_DT)
+            check(lib().rtc_scene_update(self._h, _ptr(t), nt, _ptr(s), ns), "rtc_scene_update")
+            return
+        if not all(on_device):
+            raise TypeError("DeviceScene.update: triangles and spheres both on the host or both on the device")
+        import torch
+
+        def dev(a, item, what):
+            if a is None:
+                return None, 0
+            nbytes = a.numel() * a.element_size()
+            if not a.is_cuda or not a.is_contiguous() or nbytes % item:
+                raise ValueError(f"DeviceScene.update: {what} must be a contiguous device tensor of whole {item}-byte records")
+            return C.c_void_p(a.data_ptr()), nbytes // item
+
+        pt, nt = dev(tris, TRIANGLE_DT.itemsize, "tris")
+        ps, ns = dev(spheres, SPHERE_DT.itemsize, "spheres")
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        check(lib().rtc_scene_update_async(self._h, pt, nt, ps, ns, C.c_void_p(stream) if stream else None),
+              "rtc_scene_update_async")
+
+    def records(self) -> dict:
+        """The records a launch enqueued now would read, copied back after a device synchronisation
+        (rtc_probe_scene_records): the arrays of scene_records_host, for the tests of update()."""
+        if not self._h:
+            raise RuntimeError("DeviceScene.records: the scene has been released")
+        return _records(lambda bufs, sizes: lib().rtc_probe_scene_records(self._h, *bufs, sizes), "rtc_probe_scene_records")
 
     def close(self):
         if self._h:

@@ -149,6 +149,8 @@ EXPORTS = [
     "rtc_probe_ray_triangle", "rtc_probe_ray_sphere", "rtc_probe_environment", "rtc_probe_random",
     "rtc_probe_cluster_bound", "rtc_probe_sun_vanish", "rtc_env_vanish_limit", "rtc_probe_item_records",
     "rtc_probe_primary_cull",
+    "rtc_scene_update_async", "rtc_scene_update", "rtc_plan_sim_update", "rtc_plan_sim_set_update_fault",
+    "rtc_scene_records_host", "rtc_probe_scene_records",
 ]
 
 _lib = None
@@ -247,6 +249,13 @@ def lib() -> C.CDLL:
     if hasattr(L, "rtc_probe_primary_cull"):  # (absent from libraries of earlier rounds loaded for A/B timing)
         L.rtc_probe_primary_cull.argtypes = [vp, ip, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
                                              vp, sz, vp, sz, vp, sz, vp, vp, vp, vp]
+    if hasattr(L, "rtc_scene_update_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_update_async.argtypes = [vp, vp, ip, vp, ip, vp]
+        L.rtc_scene_update.argtypes = [vp, vp, ip, vp, ip]
+        L.rtc_plan_sim_update.argtypes = [vp, C.c_ulonglong, vp, ip, vp, ip]
+        L.rtc_plan_sim_set_update_fault.argtypes = [vp, ip]
+        L.rtc_scene_records_host.argtypes = [vp, ip, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
+        L.rtc_probe_scene_records.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

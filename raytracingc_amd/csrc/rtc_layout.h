@@ -249,18 +249,29 @@ static_assert(kGeoSetInts >= kGeoLists * kGeoCountStride, "a counter set holds e
 static_assert(kSkySlots == rtcplan::kSlots && kGeoRing == rtcplan::kGeoRing && kGeoLists == rtcplan::kGeoLists &&
                   kGeoCountStride == rtcplan::kGeoCountStride && kItemRecDwords * 4 == rtcplan::kItemRecordBytes,
               "the planner's slot and counter-set layout is the device's");
+/* One generation of the scene records: everything a launch reads of the scene's geometry.  A scene keeps two
+ * (DESIGN §3.9): launches read the current one, rtc_scene_update_async writes the other and makes it current. */
+struct SceneRecords {
+    DevTri *tris;       /* triPadded + 8 records in reference order (the padding records stay zero) */
+    DevMat *mats;
+    DevSphere *spheres;
+    DevTri *clTris;     /* clusterCount * kClusterSize records in cluster order, pad0 = reference index (int) */
+    DevCluster *clusters;
+    DevCluster *chunks; /* chunkCount balls over kChunkClusters consecutive clusters */
+};
 struct RtcDeviceScene {
     int device;
     int cuCount; /* compute units of the device (the persistent chain kernel's workgroups are a multiple of it) */
     int triCount, triPadded, sphereCount; /* triPadded: multiple of kUnroll, zero (never-hit) records */
     int clusterCount;   /* ceil(triCount / kClusterSize) */
-    DevTri *clTris;     /* clusterCount * kClusterSize records in cluster order, pad0 = reference index (int) */
-    DevCluster *clusters;
-    DevCluster *chunks; /* chunkCount balls over kChunkClusters consecutive clusters */
     int chunkCount;
-    DevTri *tris;
-    DevMat *mats;
-    DevSphere *spheres;
+    SceneRecords gen[2]; /* by generation; a launch binds gen[Plan::gen] */
+    /* the generation a launch enqueued now would read (probes, rtc_cull_items) */
+    const SceneRecords &current() const { return gen[plan.gen]; }
+    /* clustered record -> reference index (-1: padding), clusterCount * kClusterSize ints: the cluster membership, fixed
+     * at upload (rtc_refit reads it) */
+    int *clIndex;
+    size_t recBytes[6]; /* bytes of tris, mats, spheres, clTris, clusters, chunks (each generation) */
     /* per-launch primary records, one copy per scratch slot (primStride records each), written by rtc_prep_primary:
      * an overlapped launch's preparation (on the cull stream) may run while the previous frame's geometry kernel still
      * reads its own copy */

@@ -139,6 +139,9 @@ void plan_launch(const State &s, const Request &r, Plan &p)
      * reduction reads the sky pass's counters) */
     p.overlap = (r.flags & RTC_F_OVERLAP) && p.fused && !r.segments && !r.resume;
     p.half = p.overlap ? s.flip : 0;
+    p.gen = s.gen;
+    if (p.overlap) /* (every return below adopts n: an overlapped launch always ends with its slot's sky-done record) */
+        n.slotGens[p.half] |= (unsigned char)(1u << s.gen);
     /* small shares (row stride > 1, <= kInlineSumPixels) sum in-kernel and, pipelined, prepare, cull and run their
      * geometry kernel on one of the two cull streams by slot parity; so do whole pipelined frames of more pixels
      * (DESIGN §3); smaller whole frames keep the caller's stream (C1 256x256x1: cross-stream hops would be its period) */
@@ -210,7 +213,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     }
     /* what the launch binds: the executor hands its kernels these buffers and no other, and only these have footprints */
     const auto bind = [&p](bool on, std::initializer_list<int> bufs) { for (int b : bufs) p.bound |= (unsigned)on << b; };
-    bind(true, {kBufPrim, kBufColors});
+    bind(true, {kBufPrim, kBufColors, kBufSceneGen});
     bind(p.cull, {kBufMask, kBufPixMask, kBufWeight});
     bind(p.cull && !p.fused, {kBufOrder});
     bind(p.superCull, {kBufSuperMask});
@@ -374,6 +377,12 @@ const Touch kTouches[] = {
     {kKAccum, kBufRngState, kRead, kIfResumeRead}, {kKRender, kBufRngState, kRead, kIfResumeRead},
     {kKSky, kBufAccum, kRead, kIfResumeRead},      {kKChain, kBufAccum, kRead, kIfResumeRead},
     {kKAccum, kBufAccum, kRead, kIfResumeRead},    {kKRender, kBufAccum, kRead, kIfResumeRead},
+    /* the scene records of the bound generation (triangles, materials, spheres, clustered records, balls): every kernel
+     * that gets them (a superset: the culls read the spheres of a sphere launch only, and today's sky pass, whose
+     * pixels' primary rays hit nothing, reads none) */
+    {kKPrep, kBufSceneGen, kRead, kAlways},        {kKSuperCull, kBufSceneGen, kRead, kAlways},
+    {kKTileCull, kBufSceneGen, kRead, kAlways},    {kKSky, kBufSceneGen, kRead, kAlways},
+    {kKChain, kBufSceneGen, kRead, kAlways},       {kKRender, kBufSceneGen, kRead, kAlways},
 };
 } // namespace
 
@@ -383,7 +392,7 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
     const struct { int res; unsigned long long id; } outside[kBufs - kScratchRegions] = {
         {kResPrim, (unsigned long long)p.half}, {kResGeoSet, p.geoSet}, {kResGeoSet, p.geoSetNext}, {kResSamples, 0},
         {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0},
-        {kResRngState, r.rngState}};
+        {kResRngState, r.rngState}, {kResSceneGen, (unsigned long long)p.gen}};
     int k = 0;
     for (const Touch &t : kTouches) {
         const bool when = t.when == kAlways || (t.when == kIfResumeRead ? p.resumeRead
@@ -401,6 +410,36 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
     return k;
 }
 
+void plan_update(const State &s, int fault, UpdatePlan &u)
+{
+    memset(&u, 0, sizeof u);
+    u.after = s;
+    State &n = u.after;
+    const int other = s.gen ^ 1;
+    u.reads = s.gen;
+    u.writes = fault == 3 ? s.gen : other;
+    for (int h = 0; h < kSlots; ++h)
+        if (s.slotGens[h] >> other & 1) {
+            if (fault != 1)
+                u.ops[u.nOps++] = Op{kOpWait, kStCaller, kEvSkyDone0 + h, -1};
+            n.slotGens[h] = 0; /* the caller's stream is now past every launch of the slot */
+        }
+    u.ops[u.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKRefit};
+    n.gen = u.writes;
+    if (fault != 2)
+        for (int h = 0; h < kSlots; ++h)
+            n.prepValid[h] = false;
+}
+
+int update_footprint(const UpdatePlan &u, Footprint *out, int max)
+{
+    const Footprint f[2] = {{kResSceneGen, kWrite, (unsigned long long)u.writes, 0, 1},
+                            {kResSceneGen, kRead, (unsigned long long)u.reads, 0, 1}};
+    for (int k = 0; k < 2 && k < max; ++k)
+        out[k] = f[k];
+    return 2;
+}
+
 } // namespace rtcplan
 
 /* ---- the CPU test hook (include/rtc.h rtc_plan_sim_*) ---------------------------------------------------------- */
@@ -412,6 +451,7 @@ struct RtcPlanSim {
     bool ranged;        /* rtc_plan_sim_set_sample_range: the next launch is a pass */
     int first, count;
     unsigned long long rngBuffer;
+    int updateFault; /* rtc_plan_sim_set_update_fault */
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -494,6 +534,45 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
         q[4] = p.overlap, q[5] = p.slotOffset;
     }
     return p.nOps | ((nf + 1) << 8);
+}
+
+extern "C" int rtc_plan_sim_set_update_fault(RtcPlanSim *s, int mode)
+{
+    if (!s || mode < 0 || mode > 3)
+        return RTC_EINVAL;
+    s->updateFault = mode;
+    return 0;
+}
+
+extern "C" int rtc_plan_sim_update(RtcPlanSim *s, unsigned long long stream, int *ops, int maxOps, unsigned long long *fp,
+                                   int maxFp)
+{
+    if (!s || !ops)
+        return RTC_EINVAL;
+    (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
+    rtcplan::UpdatePlan u;
+    rtcplan::plan_update(s->st, s->updateFault, u);
+    s->st = u.after;
+    int nf = 0;
+    for (int i = 0; i < u.nOps && i < maxOps; ++i) {
+        const rtcplan::Op &o = u.ops[i];
+        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
+        if (o.kind != rtcplan::kOpKernel)
+            continue;
+        rtcplan::Footprint f[2];
+        const int k = rtcplan::update_footprint(u, f, 2);
+        for (int j = 0; j < k; ++j, ++nf)
+            if (fp && nf < maxFp) {
+                unsigned long long *q = fp + 6 * (size_t)nf;
+                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
+                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
+            }
+    }
+    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation written, -, -, -) */
+        unsigned long long *q = fp + 6 * (size_t)nf;
+        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)u.writes, q[3] = q[4] = q[5] = 0;
+    }
+    return u.nOps | ((nf + 1) << 8);
 }
 
 extern "C" int rtc_plan_sim_regions(const RtcPlanSim *s, unsigned long long *out, int maxRows)

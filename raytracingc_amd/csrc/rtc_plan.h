@@ -59,7 +59,8 @@ enum Event : int {
     kEvGeometry = 4 + 2 * kSlots, /* the caller's geometry event */
     kEvents = 5 + 2 * kSlots
 };
-enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce };
+enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce,
+                    kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */ };
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
     int kind;   /* OpKind */
@@ -94,6 +95,13 @@ struct State {
     float prepOrigin[kSlots][3];
     size_t scratchCap, samplesCap;    /* bytes allocated (kSlots slots of scratch; the deferred sample slots) */
     bool cst2;                        /* the second cull stream exists */
+    /* the scene records' two generations: launches bind generation `gen`; rtc_scene_update_async writes the
+     * other one and makes it current.  slotGens[h] bit g: an overlapped launch of slot h read generation g, and no update
+     * has waited for the slot's sky-done event since (that event covers every earlier launch of the slot: each one starts
+     * after its predecessor ended).  Joined launches need no entry: they are complete at the caller's stream, which an
+     * update follows -- the scene serves one stream at a time, and a caller that changes streams orders them (rtc.h). */
+    int gen;
+    unsigned char slotGens[kSlots];
 };
 void init(State &s);
 
@@ -152,6 +160,7 @@ enum Buf : int {
     kBufSegSlots,
     kBufColors, kBufAccum, kBufCallerSegments, /* the caller's */
     kBufRngState,               /* the caller's per-pixel RNG states (a pass, Request::resume) */
+    kBufSceneGen,               /* the scene records of the bound generation (Plan::gen) */
     kBufs
 };
 struct Region {
@@ -165,6 +174,7 @@ struct Plan {
     bool resumeRead;     /* ... that starts from the stored accumulator and states (sampleFirst > 0) */
     bool merge;          /* the sky pass follows the geometry kernel and writes every pixel's Color in whole lines */
     int half;            /* the scratch slot */
+    int gen;             /* the generation of scene records the launch's kernels read */
     int cs, gs;          /* the culls' stream and the geometry kernel's (Stream) */
     unsigned gridX, gridY, superX, superY;
     size_t blocks, tiles;
@@ -196,7 +206,7 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 
 /* The memory one kernel of a plan touches, for the ordering test: resource kinds and byte ranges */
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
-                 kResAccum = 6, kResCallerSegments = 7, kResRngState = 8 };
+                 kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -204,5 +214,22 @@ struct Footprint {
     unsigned long long lo, hi; /* byte range (scratch) or [0, 1) */
 };
 int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out, int max);
+
+/* One rtc_scene_update_async: the refit kernel on the caller's stream writes the generation no launch
+ * binds, after a wait for the sky-done event of every slot whose overlapped launches read that generation (the event
+ * covers the slot's geometry kernel too); the written generation becomes current and every slot's primary records become
+ * stale (they are derived from the triangles, not only from the camera origin).  Launches planned afterwards follow the
+ * update: those on the caller's stream by stream order, those on a cull stream through kEvCullSync.
+ * `fault`, a test hook like Request::legacySlotLayout (0: none): 1 drops the waits, 2 keeps the primary records valid,
+ * 3 writes the current generation. */
+struct UpdatePlan {
+    int reads, writes; /* generations: the one a partial update copies from, the one the kernel writes */
+    int nOps;
+    Op ops[kSlots + 1];
+    State after;
+};
+void plan_update(const State &s, int fault, UpdatePlan &u);
+/* the refit kernel's footprint: the generation it writes and the one it may copy from */
+int update_footprint(const UpdatePlan &u, Footprint *out, int max);
 
 } // namespace rtcplan

@@ -348,11 +348,12 @@ extern "C" int rtc_probe_cluster_bound(const Triangle *tris, int triCount, const
         e = hipMemset(dc, 0, 7 * sizeof(unsigned long long));
     if (e == hipSuccess) {
         /* the clusters, then the chunks (balls over kChunkClusters clusters, rtc_render_chain's first level) */
-        hipLaunchKernelGGL(probe_cluster_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, s->clTris, s->clusters,
+        const SceneRecords &g = s->current();
+        hipLaunchKernelGGL(probe_cluster_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, g.clTris, g.clusters,
                            s->clusterCount, kClusterSize, s->clusterCount * kClusterSize, true, dr, n, dc);
         e = hipGetLastError();
         if (e == hipSuccess && s->chunkCount > 1) {
-            hipLaunchKernelGGL(probe_cluster_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, s->clTris, s->chunks,
+            hipLaunchKernelGGL(probe_cluster_kernel, dim3(probe_blocks(n)), dim3(256), 0, nullptr, g.clTris, g.chunks,
                                s->chunkCount, kClusterSize * kChunkClusters, s->clusterCount * kClusterSize, false, dr, n,
                                dc);
             e = hipGetLastError();

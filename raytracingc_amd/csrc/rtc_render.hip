@@ -2515,18 +2515,18 @@ static int check_arguments(const Scene *scene, const RtcCamera *cam, const RtcRe
     return 0;
 }
 
-/* what the kernels read of the scene, the launch's shape and the camera (the plan's buffers: bind_plan) */
+/* what the kernels read of the scene's shape, the launch's shape and the camera (the plan's buffers, the scene records
+ * among them: bind_plan) */
 static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, const RtcCamera &cam,
                                   const RtcRenderDesc &d, int rows, void *dColors, float *dAccum,
                                   unsigned long long *dSegments, const RtcSampleRange *range)
 {
     RenderParams P;
     memset(&P, 0, sizeof P);
-    P.tris = s->tris, P.mats = s->mats, P.spheres = s->spheres;
     P.triCount = s->triCount, P.triPadded = s->triPadded, P.maskWords = s->maskWords;
     P.sphereCount = d.trianglesOnly ? 0 : s->sphereCount;
-    P.clTris = s->clTris, P.clusters = s->clusters, P.clusterCount = s->clusterCount;
-    P.chunks = s->chunks, P.chunkCount = s->chunkCount, P.clusterCull = !(d.flags & RTC_F_NO_CLUSTER_CULL);
+    P.clusterCount = s->clusterCount;
+    P.chunkCount = s->chunkCount, P.clusterCull = !(d.flags & RTC_F_NO_CLUSTER_CULL);
     P.colors = (unsigned char *)dColors, P.accum = dAccum;
     P.segments = dSegments, P.segSlots = s->segSlots;
     P.width = d.width, P.height = d.height;
@@ -2574,6 +2574,9 @@ static void bind_plan(Launch &L, int flags)
     const RtcDeviceScene *s = L.s;
     const rtcplan::Plan &pl = L.pl;
     RenderParams &P = L.P;
+    const SceneRecords &g = s->gen[pl.gen]; /* the scene records of the generation the plan binds (kBufSceneGen) */
+    P.tris = g.tris, P.mats = g.mats, P.spheres = g.spheres;
+    P.clTris = g.clTris, P.clusters = g.clusters, P.chunks = g.chunks;
     P.primF = s->primF + (size_t)pl.half * s->primStride;
     P.primX = s->primX + (size_t)pl.half * s->primStride;
     P.blocksX = (int)pl.gridX;
@@ -2620,7 +2623,7 @@ static void size_chain_lds(Launch &L)
 static int run_prep(const Launch &L, hipStream_t os, hipEvent_t)
 {
     const int n = L.s->triPadded;
-    HIP_TRY(launch_stop(rtc_prep_primary, dim3((n + 8 + 63) / 64), dim3(64), 0, os, nullptr, L.s->tris,
+    HIP_TRY(launch_stop(rtc_prep_primary, dim3((n + 8 + 63) / 64), dim3(64), 0, os, nullptr, L.P.tris,
                         const_cast<DevPrimF *>(L.P.primF), const_cast<DevPrimX *>(L.P.primX), n > 0 ? n + 8 : 0,
                         L.P.origin, L.pl.prepCounts ? L.P.geoCount : nullptr));
     return 0;

@@ -2,7 +2,8 @@
  * rtc_scene.hip -- the scene on the device (rtc_scene_upload / rtc_scene_release, include/rtc.h): the reference's
  * Triangle[] (objloader.c / main.c:229-243) packed into the HBM records of rtc_layout.h, grouped into clusters and chunks
  * for the bounce rays' culling, the scheduling hint bounce_hit_share, the scene's streams and ordering events, and the
- * per-scene hooks (frame / geometry events, kernel timing).
+ * per-scene hooks (frame / geometry events, kernel timing); and the same records rewritten in place for new primitives
+ * by a kernel (rtc_scene_update_async, rtc_refit).
  */
 #include <hip/hip_runtime.h>
 
@@ -315,17 +316,23 @@ static bool aligned_normal(const DevTri &r)
     return std::isfinite(K) && 2.0 * kClusterRhoMax * K < 0.001;
 }
 
-/* ct: the records in cluster order (pad0 = reference index, -1 for padding), cl: one ball per cluster of
- * kClusterSize, ch: one ball per chunk of kChunkClusters consecutive clusters (a subtree of the median split:
- * the chain kernel's first culling level for scenes of more than one chunk) */
-static void rtc_build_clusters(const std::vector<DevTri> &dt, int triCount, std::vector<DevTri> &ct,
-                               std::vector<DevCluster> &cl, std::vector<DevCluster> &ch)
+/* The cluster membership: idx[k] = the reference index of clustered record k (idx holds triCount entries; the last
+ * cluster's missing records are padding).  Decided once, at upload; an update keeps it (rtc_scene_update_async). */
+static void rtc_cluster_membership(const std::vector<DevTri> &dt, int triCount, std::vector<int> &idx)
 {
-    const int nc = (triCount + kClusterSize - 1) / kClusterSize;
-    std::vector<int> idx(triCount);
+    idx.resize(triCount > 0 ? triCount : 0);
     for (int i = 0; i < triCount; ++i)
         idx[i] = i;
     split_clusters(dt, idx, 0, (size_t)triCount);
+}
+
+/* The one host statement of the clustered records for a membership `idx` (rtc_cluster_membership): upload builds them
+ * from the membership it has just decided, a refit (rtc_scene_records_host with new triangles; on the device rtc_refit,
+ * operation for operation) from the upload's membership and the new packed records dt. */
+static void rtc_cluster_records(const std::vector<DevTri> &dt, int triCount, const std::vector<int> &idx,
+                                std::vector<DevTri> &ct, std::vector<DevCluster> &cl, std::vector<DevCluster> &ch)
+{
+    const int nc = (triCount + kClusterSize - 1) / kClusterSize;
     ct.assign((size_t)nc * kClusterSize, DevTri{});
     cl.assign((size_t)(nc > 0 ? nc : 1), DevCluster{});
     for (int c = 0; c < nc; ++c) {
@@ -350,6 +357,272 @@ static void rtc_build_clusters(const std::vector<DevTri> &dt, int triCount, std:
     for (int h = 0; h < nch; ++h) {
         const size_t c0 = (size_t)h * kChunkClusters, c1 = std::min<size_t>((size_t)nc, c0 + kChunkClusters);
         ch[h] = ball_of(ct, c0 * kClusterSize, (c1 - c0) * kClusterSize);
+    }
+}
+
+/* Every record of a scene on the host: dt / dm / ds in reference order (pack_scene); ct: the records in cluster order
+ * (pad0 = reference index, -1 for padding), cl: one ball per cluster of kClusterSize, ch: one ball per chunk of
+ * kChunkClusters consecutive clusters (a subtree of the median split: the chain kernel's first culling level for scenes
+ * of more than one chunk); idx: the membership.  With `refit` the membership in R.idx is kept (an update) and only the
+ * records are rebuilt; without it the membership is decided from these triangles (an upload). */
+struct HostRecords {
+    std::vector<DevTri> dt, ct;
+    std::vector<DevMat> dm;
+    std::vector<DevSphere> ds;
+    std::vector<DevCluster> cl, ch;
+    std::vector<int> idx;
+};
+static void host_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, bool refit,
+                         HostRecords &R)
+{
+    pack_scene(tris, triCount, spheres, sphereCount, R.dt, R.dm, R.ds);
+    if (!refit)
+        rtc_cluster_membership(R.dt, triCount, R.idx);
+    rtc_cluster_records(R.dt, triCount, R.idx, R.ct, R.cl, R.ch);
+    if (R.ct.empty())
+        R.ct.assign(1, DevTri{});
+}
+
+/* ---- the refit on the device (rtc_scene_update_async) ---------------------------------------------------------------
+ * rtc_refit writes one generation of scene records from the caller's Triangle[] / Sphere[] in device memory: what
+ * pack_scene and rtc_cluster_records produce for the upload's membership (clIndex), byte for byte.  One workgroup per
+ * chunk, one lane per clustered record: the lane packs its triangle (tris / mats in reference order, clTris in cluster
+ * order with the aligned-normal flag), its cluster's ball comes from reductions over the aligned group of 8 lanes, the
+ * chunk's from those through LDS.  ball_of and aligned_normal are restated operation for operation in double
+ * (-ffp-contract=off; IEEE divide; __dsqrt_rn; nextafter towards +inf of a non-negative float is a bit increment); the
+ * min / max reductions are exact and skip NaN exactly as std::min / std::max with the accumulator first do, so their
+ * order does not matter.  A kind of primitive the caller leaves out is copied from the current generation. */
+struct RefitArgs {
+    const Triangle *srcTris;  /* null: copy the triangles' records of `from` */
+    const Sphere *srcSpheres; /* null: copy from's spheres */
+    SceneRecords from, to;
+    const int *clIndex;
+    int clusterCount, sphereCount;
+    size_t n16[6]; /* 16-byte words of tris, mats, spheres, clTris, clusters, chunks */
+};
+
+struct BallAcc {
+    double lo[3], hi[3], E;
+    int finite, n;
+};
+
+__device__ __forceinline__ void acc_init(BallAcc &b)
+{
+    for (int a = 0; a < 3; ++a)
+        b.lo[a] = 1e300, b.hi[a] = -1e300;
+    b.E = 0.0;
+    b.finite = 1;
+    b.n = 0;
+}
+
+/* ball_of's first loop for one real record */
+__device__ __forceinline__ void acc_record(BallAcc &b, const DevTri &r)
+{
+    ++b.n;
+    const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
+    for (int a = 0; a < 3; ++a) {
+        const double v[3] = {A[a], A[a] + B[a], A[a] + C[a]};
+        for (int w = 0; w < 3; ++w) {
+            const double x = v[w];
+            b.finite = b.finite && isfinite(x);
+            b.lo[a] = x < b.lo[a] ? x : b.lo[a];
+            b.hi[a] = b.hi[a] < x ? x : b.hi[a];
+        }
+    }
+    const double sb = __dsqrt_rn(B[0] * B[0] + B[1] * B[1] + B[2] * B[2]);
+    const double sc = __dsqrt_rn(C[0] * C[0] + C[1] * C[1] + C[2] * C[2]);
+    const double m = sb < sc ? sc : sb; /* std::max(sb, sc) */
+    b.E = b.E < m ? m : b.E;
+}
+
+/* two partial results of that loop (neither holds a NaN: the loop never stores one) */
+__device__ __forceinline__ void acc_merge(BallAcc &b, const BallAcc &o)
+{
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] = o.lo[a] < b.lo[a] ? o.lo[a] : b.lo[a];
+        b.hi[a] = b.hi[a] < o.hi[a] ? o.hi[a] : b.hi[a];
+    }
+    b.E = b.E < o.E ? o.E : b.E;
+    b.finite = b.finite && o.finite;
+    b.n += o.n;
+}
+
+__device__ __forceinline__ BallAcc acc_shfl_xor(const BallAcc &b, int mask)
+{
+    BallAcc o;
+    for (int a = 0; a < 3; ++a) {
+        o.lo[a] = __shfl_xor(b.lo[a], mask, kClusterSize);
+        o.hi[a] = __shfl_xor(b.hi[a], mask, kClusterSize);
+    }
+    o.E = __shfl_xor(b.E, mask, kClusterSize);
+    o.finite = __shfl_xor(b.finite, mask, kClusterSize);
+    o.n = __shfl_xor(b.n, mask, kClusterSize);
+    return o;
+}
+
+__device__ __forceinline__ void ball_centre(const BallAcc &b, float c[3])
+{
+    for (int a = 0; a < 3; ++a)
+        c[a] = b.n ? (float)((b.lo[a] + b.hi[a]) / 2) : 0.f;
+}
+
+/* ball_of's second loop for one real record: the largest distance of its vertices from the (float) centre */
+__device__ __forceinline__ double rec_radius(const DevTri &r, const float c[3])
+{
+    const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
+    const double K[3] = {c[0], c[1], c[2]};
+    double R = 0.0;
+    for (int w = 0; w < 3; ++w) {
+        double d2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double x = A[a] + (w == 1 ? B[a] : w == 2 ? C[a] : 0.0) - K[a];
+            d2 += x * x;
+        }
+        const double s = __dsqrt_rn(d2);
+        R = R < s ? s : R;
+    }
+    return R;
+}
+
+__device__ __forceinline__ float next_up(float x) /* nextafter(x, +inf) for x >= 0, +inf or NaN */
+{
+    if (!(x < INFINITY))
+        return x;
+    return __uint_as_float(x == 0.f ? 1u : __float_as_uint(x) + 1u);
+}
+
+/* ball_of's last part: the record from the reduced extent, the centre and the radius about it */
+__device__ __forceinline__ DevCluster ball_finish(const BallAcc &b, const float c[3], double R)
+{
+    const double u = 0x1p-24, eps = 0.001, E = b.E;
+    DevCluster k{};
+    k.cx = c[0], k.cy = c[1], k.cz = c[2];
+    const double F = 4.0, edRatio = 8.0 * u * E * E * kClusterRhoMax / eps;
+    k.r = next_up((float)(R * (1.0 + 1e-9)));
+    k.e = (float)E;
+    if (!b.finite || b.n == 0 || !(edRatio < 0.5) || !(k.r < 1e18f)) {
+        k.alpha = INFINITY; /* never culled */
+        k.beta = k.gammaE = 0.f;
+        return k;
+    }
+    const double kk = 1.0 / (1.0 - edRatio);
+    k.alpha = next_up((float)(F * kk * 32.0 * u * E * E * E / eps));
+    k.beta = next_up((float)(F * kk * 45.0 * u * E * E / eps));
+    k.gammaE = next_up((float)(kClusterGamma * E));
+    return k;
+}
+
+__device__ __forceinline__ bool aligned_normal_dev(const DevTri &r) /* aligned_normal */
+{
+    const double u = 0x1p-24;
+    const double AB[3] = {r.abx, r.aby, r.abz}, AC[3] = {r.acx, r.acy, r.acz}, N[3] = {r.nx, r.ny, r.nz};
+    const double G[3] = {AB[1] * AC[2] - AB[2] * AC[1], AB[2] * AC[0] - AB[0] * AC[2], AB[0] * AC[1] - AB[1] * AC[0]};
+    const double g = __dsqrt_rn(G[0] * G[0] + G[1] * G[1] + G[2] * G[2]);
+    if (!(g > 0.0) || !isfinite(g))
+        return false;
+    const double a = (N[0] * G[0] + N[1] * G[1] + N[2] * G[2]) / g;
+    if (!(a > 0.0))
+        return false;
+    const double e[3] = {N[0] - a * G[0] / g, N[1] - a * G[1] / g, N[2] - a * G[2] / g};
+    const double en = __dsqrt_rn(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + 1e-12 * (fabs(N[0]) + fabs(N[1]) + fabs(N[2]));
+    const double m12 = fabs(N[1]) < fabs(N[2]) ? fabs(N[2]) : fabs(N[1]);
+    const double ninf = fabs(N[0]) < m12 ? m12 : fabs(N[0]);
+    const double n1 = fabs(AB[0]) + fabs(AB[1]) + fabs(AB[2]), c1 = fabs(AC[0]) + fabs(AC[1]) + fabs(AC[2]);
+    const double K = g * (3.01 * u * ninf + en) / a + 5.1 * u * n1 * c1;
+    return isfinite(K) && 2.0 * kClusterRhoMax * K < 0.001;
+}
+
+__device__ __forceinline__ void copy16(void *dst, const void *src, size_t n16, size_t first, size_t stride)
+{
+    for (size_t k = first; k < n16; k += stride)
+        ((uint4 *)dst)[k] = ((const uint4 *)src)[k];
+}
+
+constexpr int kRefitBlock = kChunkClusters * kClusterSize; /* one lane per clustered record of a chunk */
+static_assert(kRefitBlock == 256 && kClusterSize == 8, "rtc_refit: a workgroup per chunk, 8-lane cluster reductions");
+
+__global__ __launch_bounds__(kRefitBlock) void rtc_refit(RefitArgs a)
+{
+    const int tid = (int)threadIdx.x, h = (int)blockIdx.x;
+    const size_t gt = (size_t)h * kRefitBlock + tid, gstride = (size_t)gridDim.x * kRefitBlock;
+    if (a.srcSpheres) { /* pack_scene's sphere loop */
+        for (size_t i = gt; i < (size_t)a.sphereCount; i += gstride) {
+            const float *p = reinterpret_cast<const float *>(a.srcSpheres) + 9 * i; /* pos, r, color, emission, smoothness */
+            a.to.spheres[i] = DevSphere{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], 0.f, 0.f, 0.f};
+        }
+    } else {
+        copy16(a.to.spheres, a.from.spheres, a.n16[2], gt, gstride);
+    }
+    if (!a.srcTris) { /* (the same for every lane of the grid) */
+        copy16(a.to.tris, a.from.tris, a.n16[0], gt, gstride);
+        copy16(a.to.mats, a.from.mats, a.n16[1], gt, gstride);
+        copy16(a.to.clTris, a.from.clTris, a.n16[3], gt, gstride);
+        copy16(a.to.clusters, a.from.clusters, a.n16[4], gt, gstride);
+        copy16(a.to.chunks, a.from.chunks, a.n16[5], gt, gstride);
+        return;
+    }
+    __shared__ BallAcc sAcc[kChunkClusters];
+    __shared__ double sR[kChunkClusters];
+    const size_t slot = gt, slots = (size_t)a.clusterCount * kClusterSize;
+    const bool valid = slot < slots;
+    const int i = valid ? a.clIndex[slot] : -1;
+    DevTri r{};
+    if (i >= 0) {
+        const float *p = reinterpret_cast<const float *>(a.srcTris) + 17 * (size_t)i; /* posA, posB, posC, normal, mat */
+        r.ax = p[0], r.ay = p[1], r.az = p[2];
+        /* raytracing.c:191-192 minus(posB, posA), minus(posC, posA): same f32 ops */
+        r.abx = p[3] - p[0], r.aby = p[4] - p[1], r.abz = p[5] - p[2];
+        r.acx = p[6] - p[0], r.acy = p[7] - p[1], r.acz = p[8] - p[2];
+        r.nx = p[9], r.ny = p[10], r.nz = p[11];
+        a.to.tris[i] = r;
+        a.to.mats[i] = DevMat{p[12], p[13], p[14], p[15], p[16], 0.f, 0.f, 0.f};
+        r.pad0 = __int_as_float(i);
+        r.pad1 = __int_as_float(aligned_normal_dev(r) ? 1 : 0);
+    } else {
+        r.pad0 = __int_as_float(-1); /* zero record: never hit */
+    }
+    if (valid)
+        a.to.clTris[slot] = r;
+    /* the cluster: the aligned group of 8 lanes */
+    BallAcc b;
+    acc_init(b);
+    if (i >= 0)
+        acc_record(b, r);
+    for (int m = 1; m < kClusterSize; m <<= 1)
+        acc_merge(b, acc_shfl_xor(b, m));
+    float c[3];
+    ball_centre(b, c);
+    double R = i >= 0 ? rec_radius(r, c) : 0.0;
+    for (int m = 1; m < kClusterSize; m <<= 1) {
+        const double o = __shfl_xor(R, m, kClusterSize);
+        R = R < o ? o : R;
+    }
+    const int cl = tid / kClusterSize;
+    if (tid % kClusterSize == 0) {
+        if (slot < slots)
+            a.to.clusters[slot / kClusterSize] = ball_finish(b, c, R);
+        sAcc[cl] = b;
+    }
+    __syncthreads();
+    /* the chunk: its clusters' extents (a cluster past the scene's last one is empty), then the radius about its centre */
+    BallAcc cb = sAcc[0];
+#pragma unroll 1 /* (unrolled, the 32 extents are all loaded first: 500 registers) */
+    for (int k = 1; k < kChunkClusters; ++k)
+        acc_merge(cb, sAcc[k]);
+    float cc[3];
+    ball_centre(cb, cc);
+    double Rc = i >= 0 ? rec_radius(r, cc) : 0.0;
+    for (int m = 1; m < kClusterSize; m <<= 1) {
+        const double o = __shfl_xor(Rc, m, kClusterSize);
+        Rc = Rc < o ? o : Rc;
+    }
+    if (tid % kClusterSize == 0)
+        sR[cl] = Rc;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < kChunkClusters; ++k)
+            Rc = Rc < sR[k] ? sR[k] : Rc;
+        a.to.chunks[h] = ball_finish(cb, cc, Rc);
     }
 }
 
@@ -427,15 +700,9 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
     RtcDeviceGuard guard(device);
     if (!guard.ok())
         return rtc_fail(RTC_ENODEV, "rtc_scene_upload: cannot select device %d", device);
-    std::vector<DevTri> dt;
-    std::vector<DevMat> dm;
-    std::vector<DevSphere> ds;
-    pack_scene(tris, triCount, spheres, sphereCount, dt, dm, ds);
-    std::vector<DevTri> ct;
-    std::vector<DevCluster> cl, ch;
-    rtc_build_clusters(dt, triCount, ct, cl, ch);
-    if (ct.empty())
-        ct.assign(1, DevTri{});
+    HostRecords R;
+    host_records(tris, triCount, spheres, sphereCount, false, R);
+    const std::vector<DevTri> &dt = R.dt;
     RtcDeviceScene *s = new RtcDeviceScene();
     s->device = device;
     int cus = 0;
@@ -463,23 +730,31 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
      * 3.06 vs 2.74 ms per 1080p x64 frame) */
     s->sphereSplitGate = sphereCount > 0 && sphereCount <= rtcplan::kSplitSpheresMax && triCount > 0 &&
                          s->hitShareAll <= rtcplan::kSplitMaxHitShare;
-    hipError_t e = hipMalloc(&s->tris, dt.size() * sizeof(DevTri));
+    /* two generations of the records (rtc_scene_update_async writes the one no launch binds); the upload's are
+     * generation 0, generation 1 starts zeroed (its padding records stay zero: an update writes the real ones) */
+    const void *const host[6] = {R.dt.data(), R.dm.data(), R.ds.data(), R.ct.data(), R.cl.data(), R.ch.data()};
+    const size_t bytes[6] = {R.dt.size() * sizeof(DevTri),     R.dm.size() * sizeof(DevMat),
+                             R.ds.size() * sizeof(DevSphere),  R.ct.size() * sizeof(DevTri),
+                             R.cl.size() * sizeof(DevCluster), R.ch.size() * sizeof(DevCluster)};
+    hipError_t e = hipSuccess;
+    for (int g = 0; g < 2; ++g) {
+        void **const dev[6] = {(void **)&s->gen[g].tris,   (void **)&s->gen[g].mats,     (void **)&s->gen[g].spheres,
+                               (void **)&s->gen[g].clTris, (void **)&s->gen[g].clusters, (void **)&s->gen[g].chunks};
+        for (int k = 0; k < 6; ++k) {
+            s->recBytes[k] = bytes[k];
+            if (e == hipSuccess)
+                e = hipMalloc(dev[k], bytes[k]);
+            if (e == hipSuccess)
+                e = g == 0 ? hipMemcpy(*dev[k], host[k], bytes[k], hipMemcpyHostToDevice) : hipMemset(*dev[k], 0, bytes[k]);
+        }
+    }
+    /* the membership, one int per clustered record (-1: the last cluster's padding) */
+    std::vector<int> clIndex(R.ct.size(), -1);
+    std::copy(R.idx.begin(), R.idx.end(), clIndex.begin());
     if (e == hipSuccess)
-        e = hipMalloc(&s->clTris, ct.size() * sizeof(DevTri));
+        e = hipMalloc(&s->clIndex, clIndex.size() * sizeof(int));
     if (e == hipSuccess)
-        e = hipMalloc(&s->clusters, cl.size() * sizeof(DevCluster));
-    if (e == hipSuccess)
-        e = hipMemcpy(s->clTris, ct.data(), ct.size() * sizeof(DevTri), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(s->clusters, cl.data(), cl.size() * sizeof(DevCluster), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc(&s->chunks, ch.size() * sizeof(DevCluster));
-    if (e == hipSuccess)
-        e = hipMemcpy(s->chunks, ch.data(), ch.size() * sizeof(DevCluster), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc(&s->mats, dm.size() * sizeof(DevMat));
-    if (e == hipSuccess)
-        e = hipMalloc(&s->spheres, ds.size() * sizeof(DevSphere));
+        e = hipMemcpy(s->clIndex, clIndex.data(), clIndex.size() * sizeof(int), hipMemcpyHostToDevice);
     s->primStride = dt.size();
     if (e == hipSuccess)
         e = hipMalloc(&s->primF, kSkySlots * dt.size() * sizeof(DevPrimF));
@@ -493,12 +768,6 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
         e = hipMalloc(&s->geoCounts, kGeoRing * kGeoSetInts * sizeof(int));
     if (e == hipSuccess)
         e = hipMemset(s->geoCounts, 0, kGeoRing * kGeoSetInts * sizeof(int));
-    if (e == hipSuccess)
-        e = hipMemcpy(s->tris, dt.data(), dt.size() * sizeof(DevTri), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(s->mats, dm.data(), dm.size() * sizeof(DevMat), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(s->spheres, ds.data(), ds.size() * sizeof(DevSphere), hipMemcpyHostToDevice);
     int leastPrio = 0, greatestPrio = 0;
     if (e == hipSuccess)
         e = hipDeviceGetStreamPriorityRange(&leastPrio, &greatestPrio);
@@ -542,18 +811,13 @@ extern "C" int rtc_scene_release(RtcDeviceScene *s)
         (void)hipStreamSynchronize(s->cst);
     if (s->cst2)
         (void)hipStreamSynchronize(s->cst2);
-    if (s->tris)
-        (void)hipFree(s->tris);
-    if (s->clTris)
-        (void)hipFree(s->clTris);
-    if (s->clusters)
-        (void)hipFree(s->clusters);
-    if (s->chunks)
-        (void)hipFree(s->chunks);
-    if (s->mats)
-        (void)hipFree(s->mats);
-    if (s->spheres)
-        (void)hipFree(s->spheres);
+    for (const SceneRecords &g : s->gen)
+        for (void *p : {(void *)g.tris, (void *)g.mats, (void *)g.spheres, (void *)g.clTris, (void *)g.clusters,
+                        (void *)g.chunks})
+            if (p)
+                (void)hipFree(p);
+    if (s->clIndex)
+        (void)hipFree(s->clIndex);
     if (s->primF)
         (void)hipFree(s->primF);
     if (s->primX)
@@ -589,6 +853,137 @@ extern "C" int rtc_scene_release(RtcDeviceScene *s)
         (void)hipSetDevice(cur);
     delete s;
     return 0;
+}
+
+extern "C" int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
+                                      int sphereCount, void *stream)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: null scene");
+    if (!dTris && !dSpheres)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: neither triangles nor spheres");
+    if (triCount != (dTris ? s->triCount : 0) || sphereCount != (dSpheres ? s->sphereCount : 0))
+        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: %d triangles / %d spheres for a scene uploaded with %d / %d "
+                                    "(a kind left out: a null pointer and 0)",
+                        triCount, sphereCount, s->triCount, s->sphereCount);
+    if ((dTris && s->triCount == 0) || (dSpheres && s->sphereCount == 0))
+        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: the scene was uploaded without that kind of primitive");
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_scene_update_async: cannot select the scene's device %d", s->device);
+    /* the planner decides which launches the kernel waits for and which generation it writes (rtc_plan.h plan_update);
+     * this function executes its operations */
+    rtcplan::UpdatePlan up;
+    rtcplan::plan_update(s->plan, 0, up);
+    const hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < up.nOps; ++i) {
+        const rtcplan::Op &op = up.ops[i];
+        if (op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: an operation off the caller's stream");
+        const int slot = op.event - rtcplan::kEvSkyDone0;
+        if (op.kind == rtcplan::kOpWait && slot >= 0 && slot < kSkySlots) {
+            HIP_TRY(hipStreamWaitEvent(st, s->evSkyDone[slot], 0));
+        } else if (op.kind == rtcplan::kOpKernel && op.kernel == rtcplan::kKRefit) {
+            RefitArgs a{};
+            a.srcTris = dTris, a.srcSpheres = dSpheres;
+            a.from = s->gen[up.reads], a.to = s->gen[up.writes];
+            a.clIndex = s->clIndex;
+            a.clusterCount = s->clusterCount, a.sphereCount = s->sphereCount;
+            for (int k = 0; k < 6; ++k)
+                a.n16[k] = s->recBytes[k] / 16;
+            hipLaunchKernelGGL(rtc_refit, dim3((unsigned)std::max(s->chunkCount, 1)), dim3(kRefitBlock), 0, st, a);
+            HIP_TRY(hipGetLastError());
+        } else {
+            return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: unknown planned operation %d", op.kind);
+        }
+    }
+    s->plan = up.after; /* every operation is enqueued */
+    return 0;
+}
+
+extern "C" int rtc_scene_update(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres,
+                                int sphereCount)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_update: null scene");
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_scene_update: cannot select the scene's device %d", s->device);
+    /* staged through two device buffers on the null stream; the arguments are checked by the asynchronous call */
+    Triangle *dT = nullptr;
+    Sphere *dS = nullptr;
+    hipError_t e = hipSuccess;
+    if (tris && triCount > 0) {
+        e = hipMalloc(&dT, (size_t)triCount * sizeof(Triangle));
+        if (e == hipSuccess)
+            e = hipMemcpy(dT, tris, (size_t)triCount * sizeof(Triangle), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && spheres && sphereCount > 0) {
+        e = hipMalloc(&dS, (size_t)sphereCount * sizeof(Sphere));
+        if (e == hipSuccess)
+            e = hipMemcpy(dS, spheres, (size_t)sphereCount * sizeof(Sphere), hipMemcpyHostToDevice);
+    }
+    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the update */
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    int rc = e == hipSuccess ? rtc_scene_update_async(s, tris ? dT : nullptr, triCount, spheres ? dS : nullptr,
+                                                      sphereCount, nullptr)
+                             : rtc_fail(-(int)e, "rtc_scene_update: staging failed: %s", hipGetErrorString(e));
+    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+        rc = rtc_fail(-(int)e, "rtc_scene_update: %s", hipGetErrorString(e));
+    if (dT)
+        (void)hipFree(dT);
+    if (dS)
+        (void)hipFree(dS);
+    return rc;
+}
+
+/* copies `bytes` of `src` (host or device) into out when the caller gave a buffer, and reports the size */
+static int give_records(void *const out[6], size_t cap[6], const void *const src[6], const size_t bytes[6], bool device)
+{
+    for (int k = 0; k < 6; ++k) {
+        if (out[k] && cap[k] < bytes[k])
+            return rtc_fail(RTC_EINVAL, "scene records: buffer %d holds %zu bytes of %zu", k, cap[k], bytes[k]);
+        if (out[k] && device)
+            HIP_TRY(hipMemcpy(out[k], src[k], bytes[k], hipMemcpyDeviceToHost));
+        else if (out[k])
+            memcpy(out[k], src[k], bytes[k]);
+        cap[k] = bytes[k];
+    }
+    return 0;
+}
+
+extern "C" int rtc_scene_records_host(const Triangle *tris, int triCount, const Triangle *newTris, const Sphere *spheres,
+                                      int sphereCount, void *outTris, void *outMats, void *outSpheres, void *outClTris,
+                                      void *outClusters, void *outChunks, size_t bytes[6])
+{
+    if (!bytes || triCount < 0 || sphereCount < 0 || (triCount > 0 && !tris) || (sphereCount > 0 && !spheres))
+        return rtc_fail(RTC_EINVAL, "rtc_scene_records_host: bad argument");
+    HostRecords R;
+    host_records(tris, triCount, spheres, sphereCount, false, R);
+    if (newTris)
+        host_records(newTris, triCount, spheres, sphereCount, true, R);
+    void *const out[6] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
+    const void *const src[6] = {R.dt.data(), R.dm.data(), R.ds.data(), R.ct.data(), R.cl.data(), R.ch.data()};
+    const size_t have[6] = {R.dt.size() * sizeof(DevTri),     R.dm.size() * sizeof(DevMat),
+                            R.ds.size() * sizeof(DevSphere),  R.ct.size() * sizeof(DevTri),
+                            R.cl.size() * sizeof(DevCluster), R.ch.size() * sizeof(DevCluster)};
+    return give_records(out, bytes, src, have, false);
+}
+
+extern "C" int rtc_probe_scene_records(const RtcDeviceScene *s, void *outTris, void *outMats, void *outSpheres,
+                                       void *outClTris, void *outClusters, void *outChunks, size_t bytes[6])
+{
+    if (!s || !bytes)
+        return rtc_fail(RTC_EINVAL, "rtc_probe_scene_records: null argument");
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_probe_scene_records: cannot select the scene's device %d", s->device);
+    HIP_TRY(hipDeviceSynchronize()); /* the scene's streams and the caller's: every update enqueued so far has run */
+    const SceneRecords &g = s->current();
+    void *const out[6] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
+    const void *const src[6] = {g.tris, g.mats, g.spheres, g.clTris, g.clusters, g.chunks};
+    return give_records(out, bytes, src, s->recBytes, true);
 }
 
 extern "C" int rtc_rows_selected(const RtcRenderDesc *d)
