@@ -89,7 +89,7 @@ __device__ __forceinline__ bool prim_pass(V3 dir, const DevPrimF &F)
     return (dt >= F.c) & (fminf(fminf(ut, vt), wt) >= F.negm);
 }
 
-/* The tile prefilter (its derivation: rtc_render.hip, "Tile prefilter"): the cone of a pixel rectangle and the test that no
+/* The tile prefilter (its derivation: rtc_cull.h, "Tile prefilter"): the cone of a pixel rectangle and the test that no
  * pixel of it can pass the filter for a record.  P: as for primary_dir, with the launch's `rows`. */
 struct TileCone {
     double c[4][3];
@@ -243,7 +243,7 @@ constexpr double kWgsHitShare = 0.15;
 /* rtc_render_chain's geometry-pixel sub-lists: kGeoLists counters, kGeoCountStride ints (one 128-B line) apart; a ring
  * of kGeoRing counter sets of kGeoSetInts ints (see RtcDeviceScene::geoCounts) */
 constexpr int kGeoLists = 16, kGeoCountStride = 32;
-constexpr int kItemRecDwords = 4; /* a geometry pixel's item record (item_record, rtc_render.hip) */
+constexpr int kItemRecDwords = 4; /* a geometry pixel's item record (item_record, rtc_params.h) */
 constexpr int kGeoRing = 16, kGeoSetInts = kGeoLists * kGeoCountStride;
 static_assert(kGeoSetInts >= kGeoLists * kGeoCountStride, "a counter set holds every sub-list counter");
 static_assert(kSkySlots == rtcplan::kSlots && kGeoRing == rtcplan::kGeoRing && kGeoLists == rtcplan::kGeoLists &&

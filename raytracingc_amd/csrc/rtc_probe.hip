@@ -367,7 +367,7 @@ extern "C" int rtc_probe_cluster_bound(const Triangle *tris, int triCount, const
     return rc;
 }
 
-/* The split launch's item records (rtc_render.hip item_record): uploads the scene, runs the preparation and culls of the
+/* The split launch's item records (rtc_params.h item_record): uploads the scene, runs the preparation and culls of the
  * launch `d` (rtc_cull_items) and copies back the sub-lists' counts, the records (the sub-lists one after the other) and
  * the tiles' pixel masks */
 extern "C" int rtc_probe_item_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,

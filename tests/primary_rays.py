@@ -81,7 +81,7 @@ def _round_dir(x, up):
 
 
 def prep_records(tris, origin):
-    """rtc_prep_primary restated (rtc_render.hip): per triangle the float32 AB, AC, s0 = origin - A,
+    """rtc_prep_primary restated (rtc_closest.h): per triangle the float32 AB, AC, s0 = origin - A,
     q0 = s0 x AB and dAC0 = dot(AC, q0) as the kernel forms them, its error terms in double with the proof's constants
     (9.006 u, 6.002 u, 2.0002 u, 4.8e-7, the factor 4, 2^-60) and its two escape hatches: `sane` (ed < 2.5e-4, products below
     1e30) and `never` (dAC0 is 0 or NaN).  Returns a dict with sane, never, ed and rec float32 [n, 16], the DevPrimF

@@ -169,4 +169,6 @@ def geometry(name):
         return load_tris("ultracomplex")[0], open5(), scene, cam, 0
     if name == "chunks":
         return SCENES["chunks"][0], None, scene, SCENES["chunks"][1], 1
+    if name == "chunks_open5":  # (not in SCENE_NAMES: two chunks AND spheres, for the sphere split's passes alone)
+        return SCENES["chunks"][0], open5(), scene, SCENES["chunks"][1], 0
     raise KeyError(name)

@@ -40,6 +40,8 @@ SPHERE_SCENES = ("default", "open5")
 CASES = [(n, r, s) for n in pr.SCENE_NAMES for r in ROUTES for s in ("5_1_6", "3_64_3")
          if r != "split_spheres" or n in SPHERE_SCENES]
 CASES += [(n, "default", s) for n in pr.SCENE_NAMES for s in ("12", "1x12")]
+# several chunks and spheres in one pass (rtc_render_chain<MULTI, COUNT or not, ..., SPHERES, RESUME>: no scene above is both)
+CASES += [("chunks_open5", "split_spheres", "5_1_6")]
 
 
 def _bits(a):

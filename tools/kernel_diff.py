@@ -9,8 +9,10 @@ Each tree's raytracingc_amd/csrc/rtc_render.hip is compiled for gfx950 with the 
 its .Lfunc_end; local labels (.LBB<function>_<block>) are renumbered by the function's own order, so a kernel that moved
 in the file still compares equal.  A template parameter added at the END of a kernel template's list with the default
 `false` changes the mangled names of the existing instantiations and nothing else: such names of NEW are matched with
-OLD's by dropping trailing `Lb0E` arguments.  Exit status 1 when a kernel of OLD is missing from NEW or differs.
-Needs only hipcc (no GPU)."""
+OLD's by dropping trailing `Lb0E` arguments.  The order of emission is compared too: NEW must emit OLD's kernels first,
+in OLD's order (the non-template kernels in source order, then the templates' instantiations in the order of the explicit
+instantiation list at the end of rtc_render.hip, where new ones are appended).  Exit status 1 when a kernel of OLD is
+missing from NEW or differs, or when that order changed.  Needs only hipcc (no GPU)."""
 from __future__ import annotations
 
 import re
