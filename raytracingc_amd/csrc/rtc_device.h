@@ -366,6 +366,63 @@ __device__ __forceinline__ V3 environment_miss_term(V3 dir, const EnvParams &s, 
     return environment_t<true>(dir, s, sunVanish);
 }
 
+/* environment_miss_term for a caller whose direction, environment and live lanes stay the same from call to call (the sky
+ * pass: a pixel's samples, round 11): every test by which environment_t picks its path -- the wave-wide ones on the sky
+ * argument and on the sun term, pow_ref's on the launch's focus -- depends on those alone, so env_classify makes them
+ * once, under the exec mask the calls will run with, and environment_miss_body<SKY, SUN> is the path they pick, with no
+ * test left in it: the same operations on the same operands as environment_miss_term(dir, s, sunVanish) runs. */
+constexpr int kSkyPowUnit = 0, kSkyPowPos = 1, kSkyPowNone = 2; /* powf_sky_unit; powf_glibc_pos; every lane's argument +0 */
+constexpr int kSunNone = 0, kSunPow = 1, kSunPowOdd = 2, kSunSpecial = 3; /* known for the wave; pow_ref's three cases */
+constexpr int kEnvSkyPaths = 3, kEnvSunPaths = 4;
+struct EnvPath {
+    int sky, sun; /* (wave-uniform) */
+};
+__device__ __forceinline__ EnvPath env_classify(V3 dir, const EnvParams &s, bool sunVanish)
+{
+    const unsigned sa = __float_as_uint(smoothstep_k<kSkyStep>(-dir.y));
+    const float sunArg = fmax0_ref(dot(dir, s.sun));
+    const float sunMask = dir.y < 0.f ? 1.f : 0.f;
+    const unsigned iy = rtcmath::f2u(s.focus);
+    /* (environment_t's own tests, restated here and not shared with it: its callers' code stays as it was compiled) */
+    const bool sunKnown = (s.sunSkip && __float_as_uint(sunArg) != 0x80000000u && /* powf(-0, odd) = -0 */
+                           (sunArg == 0.f || (sunMask == 0.f && sunArg <= 1.f))) ||
+                          sunVanish;
+    EnvPath p;
+    p.sky = __all(sa - 0x00800000u <= 0x3f800000u - 0x00800000u) ? kSkyPowUnit : (__any(sa != 0u) ? kSkyPowPos : kSkyPowNone);
+    p.sun = !__any(!sunKnown)
+                ? kSunNone
+                : (rtcmath::powf_zeroinfnan(iy) ? kSunSpecial : (rtcmath::powf_checkint(iy) == 1 ? kSunPowOdd : kSunPow));
+    return p;
+}
+template <int SKY, int SUN> __device__ __forceinline__ V3 environment_miss_body(V3 dir, const EnvParams &s)
+{
+    const float skyArg = smoothstep_k<kSkyStep>(-dir.y);
+    float skyGradientT = 0.f;
+    if (SKY == kSkyPowUnit)
+        skyGradientT = rtcmath::powf_sky_unit(skyArg, s.log2tab, s.exp2tab);
+    else if (SKY == kSkyPowPos)
+        skyGradientT = rtcmath::powf_glibc_pos<true>(skyArg, 0.35f, s.log2tab, s.exp2tab);
+    else /* no powf: the +0 is made opaque, so that the lerps below stay where the call is (in a loop: every iteration, as
+          * they do behind a powf) instead of folding into a constant of the caller */
+        asm volatile("" : "+v"(skyGradientT));
+    const V3 skyGradient = lerp(s.horizon, s.zenith, skyGradientT);
+    const float sunArg = fmax0_ref(dot(dir, s.sun));
+    const float groundToSkyT = smoothstep_k<kGroundStep>(-dir.y);
+    const V3 x = lerp(s.ground, skyGradient, groundToSkyT);
+    if (SUN == kSunNone)
+        return x; /* sv is a zero: see environment_miss_term */
+    const float sunMask = dir.y < 0.f ? 1.f : 0.f;
+    float p; /* pow_ref(sunArg, s.focus, s) */
+    if (SUN == kSunSpecial) {
+        p = rtcmath::powf_special_y(sunArg, s.focus);
+    } else {
+        const float r = rtcmath::powf_glibc_pos<true>(__builtin_fabsf(sunArg), s.focus, s.log2tab, s.exp2tab);
+        p = (SUN == kSunPowOdd && rtcmath::f2u(sunArg) == 0x80000000u) ? -r : r;
+    }
+    const float sv = (p * s.intensity) * sunMask;
+    return add(V3{0.f, 0.f, 0.f}, add(x, V3{sv, sv, sv}));
+}
+
 /* EPSILON is the double 0.001 (scene.h:37); for any float v, v < 0.001 <=> v < 0.001f and
  * -0.001 < v <=> -0.001f < v, so the float compares below are exact restatements. */
 constexpr float kEps = 0.001f;

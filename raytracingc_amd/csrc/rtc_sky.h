@@ -28,13 +28,56 @@ __device__ __forceinline__ void wave_lds_sync()
  * the co-resident chain workgroups leave free at a finer grain -- whole frames -1 %, the 1080p 1/8 share -2 % -- but
  * the 1/4 share took 3.5 % longer with them, profiles/r04_zd_ab_sky_wg.log). */
 /* GENERAL (round 6): the launch may merge (P.geoColor), hoist, write the accumulator or count segments; the pipelined
- * faithful whole frames run an instantiation without that code (56 VGPRs and no SGPR spill instead of 59 and 8). */
+ * faithful whole frames run an instantiation without that code (56 VGPRs and no SGPR spill instead of 59 and 8; since
+ * round 11's specialised sample loops 62 and none instead of 59 and 28). */
 /* RESUME (a pass of rtc_render_samples_async; GENERAL): the sum starts from the stored accumulator when the
  * pass is not the frame's first; the first pass writes the pixel's state, its seed x + y * width (a sky pixel draws
  * nothing, so later passes leave it).  The shortcuts and a sum that does not start at +0: the sun-term skip (sun_vanishes)
  * concerns e + sv alone, whatever it is added to; environment_miss_term needs a sum that is not -0, and the stored sum is
  * +0 plus such terms, which in round-to-nearest is never -0; the hoisted term is one value added P.spp times either way.
  * A pass never merges (geoColor's place holds rngState). */
+/* The faithful sample loop with its path decided once per strip (round 11, RTC_SKY_PATHS; 0 builds the loop that calls
+ * environment_miss_term, which decides every sample): a pixel's direction, the launch's environment and the strip's live
+ * lanes are the same in every sample, so env_classify's wave-wide tests are made once before the loop, under its exec
+ * mask, and the loop is one of environment_miss_body's instantiations behind one wave-uniform switch -- no ballot and no
+ * choice of path per sample, and the unrolled copies interleave (RTC_SKY_UNROLL samples per iteration: DESIGN §3.3).  Every sample still runs the reference's arithmetic (both powf
+ * cores from the tables, the lerps, the adds by zero beside a computed sun term, the sequential sum): sky_keep_per_sample
+ * keeps the table reads, and with them all that follows from them, inside the loop now that no branch does, and the
+ * path without a sky powf keeps its lerps there by an opaque +0 (environment_miss_body). */
+#ifndef RTC_SKY_PATHS
+#define RTC_SKY_PATHS 1
+#endif
+#ifndef RTC_SKY_UNROLL
+#define RTC_SKY_UNROLL 2
+#endif
+/* a fence against the lane itself (no instruction): loads after it are not moved before it, so a loop's loads stay in it
+ * (not an empty asm statement: device asm is convergent, and a loop with a convergent call is not unrolled) */
+__device__ __forceinline__ void sky_keep_per_sample() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "singlethread"); }
+
+template <int SKY, int SUN, int UNROLL>
+__device__ __forceinline__ V3 sky_samples(V3 acc, V3 dir, const EnvParams &env, int spp, float invSpp)
+{
+#pragma unroll UNROLL
+    for (int s = 0; s < spp; ++s) {
+        sky_keep_per_sample();
+        /* raytracing.c:291 with rayColor (1, 1, 1): 0 + environment (environment_miss_term: acc starts at +0) */
+        const V3 l = environment_miss_body<SKY, SUN>(dir, env);
+        acc = add(acc, mul(l, invSpp)); /* main.c:99 */
+    }
+    return acc;
+}
+template <int UNROLL, int I = 0>
+__device__ __forceinline__ V3 sky_samples_on(EnvPath p, V3 acc, V3 dir, const EnvParams &env, int spp, float invSpp)
+{
+    if constexpr (I + 1 < kEnvSkyPaths * kEnvSunPaths) {
+        if (p.sky * kEnvSunPaths + p.sun != I) /* (wave-uniform) */
+            return sky_samples_on<UNROLL, I + 1>(p, acc, dir, env, spp, invSpp);
+    }
+    /* (the path without a sky powf holds an asm statement, and a loop with one is not unrolled; its body is short) */
+    return sky_samples<I / kEnvSunPaths, I % kEnvSunPaths, I / kEnvSunPaths == kSkyPowNone ? 1 : UNROLL>(acc, dir, env, spp,
+                                                                                                        invSpp);
+}
+
 template <int kSkyWaves, bool GENERAL, bool RESUME = false>
 __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(RTC_SKY_WAVES))) void rtc_render_sky_rows(
     RenderParams P)
@@ -102,6 +145,11 @@ __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(
             /* the sun term provably below half an ulp of every colour component for this pixel (sun_vanishes, a
              * function of the pixel's direction and the launch's environment) */
             const bool vanish = sun_vanishes(dir, P.env);
+#if RTC_SKY_PATHS && !defined(RTC_AB_CHEAP_ENV_SKY)
+            /* (the GENERAL kernels one sample per iteration: two took them to scratch) */
+            acc = sky_samples_on<GENERAL ? 1 : RTC_SKY_UNROLL>(env_classify(dir, P.env, vanish), acc, dir, P.env, P.spp,
+                                                               P.invSpp);
+#else
 #pragma unroll 2
             for (int s = 0; s < P.spp; ++s) {
 #if defined(RTC_AB_CHEAP_ENV_SKY) && defined(RTC_EXPERIMENT) /* timing experiment only (the environment's cost) */
@@ -112,6 +160,7 @@ __global__ __launch_bounds__(kSkyWaves * 64) __attribute__((amdgpu_waves_per_eu(
 #endif
                 acc = add(acc, mul(l, P.invSpp)); /* main.c:99 */
             }
+#endif
         }
         segCalls = (unsigned)P.spp;
         segTraced = P.hoist ? 1u : (unsigned)P.spp;
