@@ -252,6 +252,21 @@ int rtc_scene_kernel_times(const RtcDeviceScene *s, float out[2]);
  * scene got from it (4 above 0.15, else 3; small row shares run 3). */
 int rtc_bounce_hit_share(const Triangle *tris, int triCount, float *share);
 int rtc_scene_chain_wgs(const RtcDeviceScene *s);
+/* What the scene's last geometry-kernel launch (rtc_render_chain, the split launch's kernel for the pixels that see
+ * geometry) chose, recorded on the host when the launch was enqueued -- read-only, no device work, no reference
+ * counterpart: every choice renders the same frame, so only this report tells a test which code path a launch ran.
+ * multi .. resume: the kernel's template flags (MULTI: more than one chunk of 32 clusters; COUNT: segment counters; HITS: the
+ * hit-heavy scenes' instantiation; GENERAL: deferred slots, hoisted primaries or unstaged primary filter records, and every
+ * MULTI / COUNT / SPHERES / RESUME launch; SPHERES; RESUME: a pass).  chainPrimF: the primary filter records are staged in
+ * LDS.  wgsPerCu: the launch's workgroups per CU (rtc_scene_chain_wgs for whole frames, 3 for small row shares).
+ * chainDyn: its dynamic LDS in bytes.  clusterCount, chunkCount: the scene's.  launches: how many geometry-kernel launches
+ * the scene has enqueued so far (0: none yet, every other field 0; a launch without the split launch leaves the report as
+ * it was). */
+typedef struct RtcChainReport {
+    int multi, count, hits, general, spheres, resume;
+    int chainPrimF, wgsPerCu, chainDyn, clusterCount, chunkCount, launches;
+} RtcChainReport;
+int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *out);
 /* Sphere scenes (calculateRayCollision's sphere loop, raytracing.c:219-228).  A launch that renders spheres takes the split
  * launch -- the pixels whose primary ray hits nothing go to the sky pass, the others to rtc_render_chain, which tests the
  * spheres first and lets a triangle win only when strictly closer -- when all of these hold: at most 32 spheres; the

@@ -45,6 +45,7 @@ from ._abi import (  # noqa: F401
     EXPORTS,
     Ray,
     RtcCamera,
+    RtcChainReport,
     RtcError,
     RtcLoopStats,
     RtcRenderDesc,
@@ -330,6 +331,18 @@ class DeviceScene:
     def chain_wgs(self) -> int:
         """rtc_render_chain's workgroups per CU for whole frames, chosen at upload (rtc_scene_chain_wgs)."""
         return lib().rtc_scene_chain_wgs(self._h)
+
+    def chain_report(self) -> dict:
+        """What the scene's last geometry-kernel launch chose (rtc_scene_chain_report; host state, no device work): the
+        kernel's template flags multi, count, hits, general, spheres, resume and chain_prim_f (the primary filter records
+        staged in LDS) as bools; wgs_per_cu, chain_dyn (bytes of dynamic LDS), cluster_count, chunk_count and launches
+        (the geometry-kernel launches enqueued so far; 0: no launch yet) as ints."""
+        r = RtcChainReport()
+        check(lib().rtc_scene_chain_report(self._h, C.byref(r)), "rtc_scene_chain_report")
+        out = {k: bool(getattr(r, k)) for k in ("multi", "count", "hits", "general", "spheres", "resume")}
+        out.update(chain_prim_f=bool(r.chainPrimF), wgs_per_cu=r.wgsPerCu, chain_dyn=r.chainDyn,
+                   cluster_count=r.clusterCount, chunk_count=r.chunkCount, launches=r.launches)
+        return out
 
     @property
     def sphere_split(self) -> bool:

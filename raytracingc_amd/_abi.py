@@ -69,6 +69,11 @@ class RtcSampleRange(C.Structure):  # samples [first, first + count) of RtcRende
     _fields_ = [("first", C.c_int), ("count", C.c_int)]
 
 
+class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geometry-kernel launch chose (include/rtc.h)
+    _fields_ = [(k, C.c_int) for k in ("multi", "count", "hits", "general", "spheres", "resume", "chainPrimF", "wgsPerCu",
+                                       "chainDyn", "clusterCount", "chunkCount", "launches")]
+
+
 class RtcStats(C.Structure):
     _fields_ = [
         ("renderMs", C.c_double),
@@ -151,6 +156,7 @@ EXPORTS = [
     "rtc_probe_primary_cull",
     "rtc_scene_update_async", "rtc_scene_update", "rtc_plan_sim_update", "rtc_plan_sim_set_update_fault",
     "rtc_scene_records_host", "rtc_probe_scene_records",
+    "rtc_scene_chain_report",
 ]
 
 _lib = None
@@ -256,6 +262,8 @@ def lib() -> C.CDLL:
         L.rtc_plan_sim_set_update_fault.argtypes = [vp, ip]
         L.rtc_scene_records_host.argtypes = [vp, ip, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
         L.rtc_probe_scene_records.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "rtc_scene_chain_report"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_chain_report.argtypes = [vp, C.POINTER(RtcChainReport)]
     _lib = L
     return L
 

@@ -315,6 +315,7 @@ struct RtcDeviceScene {
     hipEvent_t evHeavy0, evHeavy1, evSky0, evSky1;
     bool timing; /* record them (rtc_scene_set_timing; off by default: each record costs the launch a few us) */
     bool timed;  /* the last launch was a split launch that recorded them */
+    RtcChainReport chainReport; /* what the last geometry-kernel launch chose (run_chain; rtc_scene_chain_report) */
 };
 
 /* A split launch's geometry-pixel lists once its culls have run, for rtc_probe_item_records: the launch's preparation,

@@ -127,8 +127,9 @@ struct ChainFlags {
 /* The launch's properties -> the flags.  `defer`: the launch may give items deferred sample slots, hoists the primary
  * segments or reads the primary filter records from global memory.  `hits`: the scene's bounces often hit again.  Only a
  * launch that is none of multi-chunk, counting, deferring, with spheres or a pass runs a kernel without the GENERAL code,
- * and only there does `hits` choose: both choices render the same frame, so nothing but the static_asserts below
- * notices a wrong one. */
+ * and only there does `hits` choose: both choices render the same frame, so only the static_asserts below and the
+ * launch's report (rtc_scene_chain_report, which tests/test_gpu_chain_paths.py holds to the launch meant) notice a
+ * wrong one. */
 constexpr ChainFlags chain_flags(bool multi, bool count, bool defer, bool hits, bool spheres, bool resume)
 {
     const bool general = multi || count || defer || spheres || resume;
@@ -386,6 +387,12 @@ static int run_chain(const Launch &L, hipStream_t os, hipEvent_t ev)
     static_assert(every_chain_launch([](int, ChainFlags f) { return chain_variant(kChain, f) < kVariants; }),
                   "every launch selects an instantiated kernel");
     const int variant = chain_variant(kChain, chain_flags(multi, count, defer, hits, P.sphereCount > 0, L.resume));
+    { /* rtc_scene_chain_report: the row taken and size_chain_lds' choices (host stores only) */
+        const ChainFlags &f = kChain[variant].flags;
+        RtcChainReport &r = const_cast<RtcDeviceScene *>(s)->chainReport;
+        r = RtcChainReport{f.multi,      f.count,    f.hits,          f.general,       f.spheres,     f.resume,
+                           P.chainPrimF, L.wgsPerCu, (int)L.chainDyn, s->clusterCount, s->chunkCount, r.launches + 1};
+    }
     if (s->timing)
         HIP_TRY(hipEventRecord(s->evHeavy0, os));
     HIP_TRY(launch_stop(kChain[variant].kernel, cg, cb, L.chainDyn, os, ev, P));

@@ -657,6 +657,14 @@ extern "C" int rtc_scene_chain_wgs(const RtcDeviceScene *s)
     return s->chainWgsFull;
 }
 
+extern "C" int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *out)
+{
+    if (!s || !out)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_chain_report: null argument");
+    *out = s->chainReport;
+    return 0;
+}
+
 extern "C" int rtc_scene_upload(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, int device,
                                 RtcDeviceScene **out)
 {

@@ -9,6 +9,9 @@ World: the camera basis of main.c:252-255 has up = (0, -1, 0), so +y is down in 
 y > 0 with the normal (0, -1, 0).  rayTriangle (raytracing.c:186-214) is two-sided in the winding and one-sided in the
 stored normal, so every triangle built here takes a stored normal that faces the camera unless the scene says otherwise.
 
+The counts_* scenes stop at 65 triangles (9 clusters) and `chunks` has 36 clusters: the cluster-count classes between them
+(16, 17, 32, 33 clusters) and the trace's other path switches are tests/chain_path_scenes.py's.
+
 Materials differ between all triangles of a scene (colour, emission and smoothness from the index), so that a wrong
 winner changes the pixel."""
 from __future__ import annotations

@@ -69,6 +69,20 @@ def test_bad_arguments_rejected():
     assert b"rtc_" in L.rtc_last_error() or len(L.rtc_last_error()) > 0
 
 
+def test_chain_report_mirror_and_argument_errors():
+    """rtc_scene_chain_report: the ctypes mirror has the header's fields in the header's order (all int), and null
+    arguments are refused without a device."""
+    txt = open(os.path.join(REPO, "include", "rtc.h")).read()
+    body = re.search(r"typedef struct RtcChainReport \{(.*?)\} RtcChainReport;", txt, flags=re.S).group(1)
+    fields = [f.strip() for decl in re.findall(r"\bint\s+([^;]+);", body) for f in decl.split(",")]
+    assert fields == [n for n, _ in _abi.RtcChainReport._fields_] and len(fields) == 12
+    assert all(t is C.c_int for _, t in _abi.RtcChainReport._fields_) and C.sizeof(_abi.RtcChainReport) == 48
+    L = rt.lib()
+    assert L.rtc_scene_chain_report(None, C.byref(_abi.RtcChainReport())) == _abi.RTC_EINVAL
+    assert b"rtc_scene_chain_report" in L.rtc_last_error()
+    assert "rtc_scene_chain_report" in _abi.EXPORTS and hasattr(rt.DeviceScene, "chain_report")
+
+
 def test_flag_constants_match_header():
     """Every RTC_F_* / RTC_E* / RTC_SEGMENT_COUNTERS value in include/rtc.h equals the ctypes mirror's."""
     import re
