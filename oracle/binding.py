@@ -40,6 +40,8 @@ def lib() -> C.CDLL:
         L.oracle_random.restype = None
         L.oracle_calc_color.argtypes = [vp, ip, vp, ip, C.POINTER(Scene), ip, vp, vp, vp, sz, vp, vp, ip]
         L.oracle_calc_color.restype = None
+        L.oracle_calc_path.argtypes = [vp, ip, vp, ip, C.POINTER(Scene), ip, vp, vp, vp, sz, vp, vp, vp, vp, ip]
+        L.oracle_calc_path.restype = None
         _lib = L
     return _lib
 
@@ -120,3 +122,28 @@ def calc_color(tris, spheres, scene: Scene, triangles_only: int, rays, seeds, ma
     lib().oracle_calc_color(_p(t), nt, _p(s), ns, C.byref(scene), triangles_only, _p(r), _p(sd), _p(mb), n, _p(out),
                             _p(after), int(debug))
     return out, after
+
+
+# oracle_calc_path's record of one calculateRayCollision call (rtc_oracle.c OracleCall)
+CALL_DT = np.dtype([("pos", "<f4", 3), ("dir", "<f4", 3), ("winner", "<i4"), ("dst", "<f4"), ("p", "<f4"), ("draw", "<f4"),
+                    ("rayColor", "<f4", 3)])
+
+
+def calc_path(tris, spheres, scene: Scene, triangles_only: int, rays, seeds, max_bounce):
+    """calc_color call by call: (colour, seed after, calls CALL_DT [n, max(max_bounce)], number of calls [n]).  Per
+    calculateRayCollision call the ray traced (pos, dir), the winner (triangle index, -2 - i for sphere i, -1 for a miss),
+    its dst and, on a hit, the roulette's p and draw and the rayColor whose maximum p is; entries past a record's calls are zero."""
+    t, nt = _arr(tris, TRIANGLE_DT)
+    s, ns = _arr(spheres, SPHERE_DT)
+    r = np.ascontiguousarray(rays, RAY_DT)
+    sd = np.ascontiguousarray(seeds, np.uint32)
+    mb = np.ascontiguousarray(max_bounce, np.int32)
+    n = len(r)
+    stride = max(int(mb.max(initial=0)), 1)
+    out = np.zeros((n, 3), np.float32)
+    after = np.zeros(n, np.uint32)
+    calls = np.zeros((n, stride), CALL_DT)
+    ncalls = np.zeros(n, np.int32)
+    lib().oracle_calc_path(_p(t), nt, _p(s), ns, C.byref(scene), triangles_only, _p(r), _p(sd), _p(mb), n, _p(out),
+                           _p(after), _p(calls), _p(ncalls), stride)
+    return out, after, calls, ncalls

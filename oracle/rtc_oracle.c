@@ -101,7 +101,7 @@ static vec3 o_env(Ray ray, const Scene *s) /* :151-160 */
     return o_plus(o_lerp(s->groundColor, skyGradient, groundToSkyT), sunValue);
 }
 
-typedef struct { int didHit; float dst; vec3 hitPoint; vec3 normal; Material mat; } OHit;
+typedef struct { int didHit; float dst; vec3 hitPoint; vec3 normal; Material mat; int idx; } OHit; /* idx: o_collide's winner */
 
 static OHit o_ray_sphere(Ray ray, vec3 c, float radius) /* :162-184 */
 {
@@ -171,6 +171,7 @@ static OHit o_collide(Ray ray, const OCtx *c, unsigned long long *segments) /* :
     OHit closest;
     memset(&closest, 0, sizeof closest);
     closest.dst = 999999;
+    closest.idx = -1;
     (*segments)++;
     if (c->trianglesOnly == 0)
         for (int i = 0; i < c->sphCount; ++i) {
@@ -178,6 +179,7 @@ static OHit o_collide(Ray ray, const OCtx *c, unsigned long long *segments) /* :
             if (h.didHit && h.dst < closest.dst) {
                 closest = h;
                 closest.mat = c->sph[i].mat;
+                closest.idx = -2 - i;
             }
         }
     for (int i = 0; i < c->triCount; ++i) {
@@ -185,18 +187,34 @@ static OHit o_collide(Ray ray, const OCtx *c, unsigned long long *segments) /* :
         if (h.didHit && h.dst < closest.dst) {
             closest = h;
             closest.mat = c->tris[i].mat;
+            closest.idx = i;
         }
     }
     closest.hitPoint = o_plus(ray.pos, o_times(ray.dir, closest.dst));
     return closest;
 }
 
-static vec3 o_calc_color(Ray ray, const OCtx *c, unsigned int *rng, unsigned long long *segments) /* :262-296 */
+/* One calculateRayCollision call of a path, as oracle_calc_path reports it: the ray traced, the winner (triangle index,
+ * -2 - i for sphere i, -1 for a miss), its dst (999999 on a miss) and, on a hit, the roulette's p and draw and the
+ * rayColor p is the maximum of (after the hit's colour, before the division by p); all 0 on a miss */
+typedef struct { vec3 pos, dir; int winner; float dst, p, draw; vec3 rayColor; } OracleCall; /* 52 B */
+
+/* calcColor; with `rec` every call is written to rec[0 .. *nrec) as well (the same statements either way) */
+static inline vec3 o_path(Ray ray, const OCtx *c, unsigned int *rng, unsigned long long *segments, OracleCall *rec, int *nrec)
 {
     vec3 incomingLight = {0, 0, 0};
     vec3 rayColor = {1, 1, 1};
     for (int i = 0; i < c->maxBounce; ++i) {
         OHit hit = o_collide(ray, c, segments);
+        OracleCall *r = rec ? &rec[(*nrec)++] : NULL;
+        if (r) {
+            r->pos = ray.pos;
+            r->dir = ray.dir;
+            r->winner = hit.idx;
+            r->dst = hit.dst;
+            r->p = r->draw = 0;
+            r->rayColor = (vec3){0, 0, 0};
+        }
         if (hit.didHit) {
             vec3 diffuseDir = o_normalized(o_plus(hit.normal, o_random_direction(rng)));
             vec3 specularDir = o_reflect(ray.dir, hit.normal);
@@ -206,7 +224,13 @@ static vec3 o_calc_color(Ray ray, const OCtx *c, unsigned int *rng, unsigned lon
             incomingLight = o_plus(incomingLight, o_timesVec3(emittedLight, rayColor));
             rayColor = o_timesVec3(rayColor, hit.mat.color);
             float p = (float)fmax(fmax((double)rayColor.x, (double)rayColor.y), (double)rayColor.z);
-            if (p < o_random(rng))
+            float draw = o_random(rng);
+            if (r) {
+                r->p = p;
+                r->draw = draw;
+                r->rayColor = rayColor;
+            }
+            if (p < draw)
                 break;
             rayColor = o_times(rayColor, (float)(1.0 / (double)p));
         } else {
@@ -215,6 +239,11 @@ static vec3 o_calc_color(Ray ray, const OCtx *c, unsigned int *rng, unsigned lon
         }
     }
     return incomingLight;
+}
+
+static vec3 o_calc_color(Ray ray, const OCtx *c, unsigned int *rng, unsigned long long *segments) /* :262-296 */
+{
+    return o_path(ray, c, rng, segments, NULL, NULL);
 }
 
 /* calcDebugColor (raytracing.c:242-260): bounce count until the first miss, as grey */
@@ -388,6 +417,22 @@ void oracle_calc_color(const Triangle *tris, int triCount, const Sphere *spheres
         unsigned int s = seeds[i];
         unsigned long long seg = 0;
         out[i] = debug ? o_calc_debug_color(rays[i], &ctx, &s, &seg) : o_calc_color(rays[i], &ctx, &s, &seg);
+        seedAfter[i] = s;
+    }
+}
+
+/* oracle_calc_color's paths call by call (tests/test_material_scenes.py): record i's calls go to calls[i * stride ..), their
+ * number to ncalls[i]; stride >= every maxBounce */
+void oracle_calc_path(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, const Scene *scene,
+                      int trianglesOnly, const Ray *rays, const unsigned int *seeds, const int *maxBounce, size_t n,
+                      vec3 *out, unsigned int *seedAfter, OracleCall *calls, int *ncalls, int stride)
+{
+    for (size_t i = 0; i < n; ++i) {
+        OCtx ctx = {tris, triCount, spheres, sphereCount, scene, trianglesOnly, maxBounce[i]};
+        unsigned int s = seeds[i];
+        unsigned long long seg = 0;
+        ncalls[i] = 0;
+        out[i] = o_path(rays[i], &ctx, &s, &seg, calls + i * (size_t)stride, &ncalls[i]);
         seedAfter[i] = s;
     }
 }

@@ -13,7 +13,8 @@ The counts_* scenes stop at 65 triangles (9 clusters) and `chunks` has 36 cluste
 (16, 17, 32, 33 clusters) and the trace's other path switches are tests/chain_path_scenes.py's.
 
 Materials differ between all triangles of a scene (colour, emission and smoothness from the index), so that a wrong
-winner changes the pixel."""
+winner changes the pixel.  They stay ordinary here (smoothness and colours in [0, 1]); material edges live in
+tests/material_scenes.py."""
 from __future__ import annotations
 
 import math

@@ -14,6 +14,9 @@ the deterministic variant described in SURVEY.md F4 (oracle/ref_unity.c, oracle/
   kat_env_edge.npz       getEnvironmentLight at signed zeros, special sun intensities / focus values
   kat_calc_<scene>.npz   calcColor per (ray, seed, maxBounce)
   kat_debug_<scene>.npz  calcDebugColor (raytracing.c:242-260) per (ray, seed, maxBounce)
+  kat_calc_materials.npz calcColor on the finite scenes of tests/material_scenes.py (smoothness -1 .. 3e38, colours outside
+                         [0, 1], emission 3e38), each written out as a triangles.txt for the reference's own parser
+  loader/high_ns_obj.tris  loadOBJTriangles on an MTL with Ns 6250 and Ns 4000 (smoothness 2.5 and 2)
   render_golden.json     full renders (main.c render loop): sha256 of the pre-quantisation float
                          framebuffer and md5 of the BMP, per configuration
 
@@ -398,6 +401,11 @@ def gen_meta():
         "compiler": subprocess.run(["gcc", "--version"], capture_output=True, text=True).stdout.splitlines()[0],
         "ref_binary": "oracle/_ref/rtc_ref (make ref: gcc -O3 on /root/reference sources via oracle/ref_unity.c)",
     }
+    materials = os.path.join(HERE, "kat_calc_materials.npz")
+    if os.path.exists(materials):
+        with np.load(materials) as k:
+            meta["kat_calc_materials_keys"] = sorted(k.files)
+            meta["kat_calc_materials_scenes"] = [str(n) for n in k["names"]]
     with open(os.path.join(HERE, "golden_meta.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
 
@@ -448,12 +456,142 @@ def gen_kat_env_edge(work):
     np.savez_compressed(os.path.join(HERE, "kat_env_edge.npz"), rays=rays, scenes=scenes, out=out)
 
 
+def save_npz(path, **arrays):
+    """np.savez_compressed with fixed member dates: the same arrays give the same bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def exact_decimal(x) -> str:
+    """A float32's exact value as a plain decimal: cleanFile (raytracing.c:47-74) blanks every character but digits, signs,
+    dots and newlines, so an exponent would split the number."""
+    from decimal import Decimal
+
+    s = format(Decimal(float(np.float32(x))), "f")
+    assert set(s) <= set("0123456789.-")
+    return s
+
+
+def triangles_txt(tris) -> str:
+    """Triangle[] in the reference's text format (raytracing.c:19-25): the count, then per triangle A, B, C, colour,
+    emission, smoothness; the normal is recomputed by the parser."""
+    lines = [str(len(tris))]
+    for t in tris:
+        v = [t[k][c] for k in ("posA", "posB", "posC") for c in "xyz"] + [t["mat"]["color"][c] for c in "xyz"]
+        v += [t["mat"]["emissionStrength"], t["mat"]["smoothness"]]
+        lines.append(" ".join(exact_decimal(x) for x in v))
+    return "\n".join(lines) + "\n"
+
+
+# the reference's default mode keeps scene.h's sphere (centre (0, 1, 0), radius 2.5): the scenes and their cameras are
+# moved away from it, so that the records meet the triangles first
+KAT_MATERIALS_OFFSET = (0.0, -16.0, 0.0)
+KAT_MATERIALS_RECORDS = 200
+
+
+def gen_kat_calc_materials(work):
+    """calcColor of the reference on the finite scenes of tests/material_scenes.py: per scene 100 of the frame's own
+    primary rays with their seeds x + y * width and the same rays with the seeds advanced by 7 j draws, j = 1 .. 100."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import material_scenes as ms
+    import progressive_reference as pr
+    import raytracingc_amd as rt
+    import oracle.binding as orc
+    from primary_rays import hit_table, launch_rays
+
+    names = sorted(n for n in ms.SCENES if not n.endswith("_nonfinite"))
+    out = {k: [] for k in ("tris", "tri_scene", "rays", "seeds", "max_bounce", "color", "seed_after", "rec_scene")}
+    off = np.array(KAT_MATERIALS_OFFSET, np.float32)
+    for si, name in enumerate(names):
+        tris, cam, _ = ms.SCENES[name]
+        assert np.isfinite(np.stack([tris["mat"]["color"][c] for c in "xyz"] + [tris["mat"]["emissionStrength"],
+                                                                                tris["mat"]["smoothness"]])).all()
+        t = tris.copy()
+        for k in ("posA", "posB", "posC"):
+            for i, c in enumerate("xyz"):
+                t[k][c] = (t[k][c] + off[i]).astype(np.float32)
+        t = ms.recomputed_normals(t)
+        g = lambda a, k: np.stack([a[k][c] for c in "xyz"], 1).astype(np.float64)  # noqa: E731
+        wound = np.einsum("ij,ij->i", np.cross(g(t, "posB") - g(t, "posA"), g(t, "posC") - g(t, "posA")), g(tris, "normal"))
+        assert (wound > 0).all(), f"{name}: a winding against its stored normal"
+        d = os.path.join(work, "materials_" + name)
+        os.makedirs(d)
+        with open(os.path.join(d, "triangles.txt"), "w") as f:
+            f.write(triangles_txt(t))
+        dump = os.path.join(d, "dump.tris")
+        run_ref(["--dump-tris", "default", dump], d)
+        raw = open(dump, "rb").read()
+        assert int(np.frombuffer(raw[:4], np.int32)[0]) == len(t)
+        assert raw[8:8 + 68 * len(t)] == t.tobytes(), f"{name}: the reference's parser gives other bits"
+        _, W, H, spp, mb = ms.FRAMES[name]  # (every scene has a frame of its own name)
+        cfg = rt.RenderConfig(W, H, 1, mb, True)
+        half = KAT_MATERIALS_RECORDS // 2
+        # the pixels: spread evenly over those whose primary ray meets a triangle (the oracle's rayTriangle only chooses
+        # inputs here) and, in an open scene, a tenth of them over the sky
+        all_rays = launch_rays(cam, cfg)
+        rec, _ = hit_table(orc.ray_triangle, tris, all_rays)
+        geo, sky = np.flatnonzero(rec.any(1)), np.flatnonzero(~rec.any(1))
+        n_sky = half // 10 if len(sky) else 0
+        px = np.sort(np.concatenate([geo[np.arange(half - n_sky) * len(geo) // (half - n_sky)],
+                                     sky[np.arange(n_sky) * len(sky) // max(n_sky, 1)]])).astype(np.int64)
+        rays = all_rays[px]
+        for i, c in enumerate("xyz"):
+            rays["pos"][c] = (rays["pos"][c] + off[i]).astype(np.float32)
+        s0 = pr.seeds(cfg.desc())[px]
+        s1 = np.array([pr.advance(s0[k:k + 1], 7 * (k + 1))[0] for k in range(half)], np.uint32)
+        rays, seeds = np.concatenate([rays, rays]), np.concatenate([s0, s1])
+        kin = np.zeros(len(rays), np.dtype([("ray", RAY_DT), ("seed", "<u4"), ("mb", "<i4")]))
+        kin["ray"], kin["seed"], kin["mb"] = rays, seeds, mb
+        fi, fo = os.path.join(d, "calc.in"), os.path.join(d, "calc.out")
+        kin.tofile(fi)
+        run_ref(["--kat-calc", "default", fi, fo], d)
+        res = np.fromfile(fo, np.dtype([("color", "<f4", 3), ("seedAfter", "<u4")]))
+        assert len(res) == len(rays)
+        for k, v in (("tris", t), ("tri_scene", np.full(len(t), si, np.int16)), ("rays", rays), ("seeds", seeds),
+                     ("max_bounce", np.full(len(rays), mb, np.int32)), ("color", res["color"]),
+                     ("seed_after", res["seedAfter"]), ("rec_scene", np.full(len(rays), si, np.int16))):
+            out[k].append(v)
+    arrays = {k: np.concatenate(v) for k, v in out.items()}
+    arrays["names"] = np.array(names)
+    save_npz(os.path.join(HERE, "kat_calc_materials.npz"), **arrays)
+
+
+def gen_loader_high_ns(work):
+    """loadOBJTriangles (objloader.c: smoothness = sqrt(0.001 Ns), no clamp) on tests/test_scene_build.py's MTL with
+    Ns 6250 and Ns 4000."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_scene_build import HIGH_NS_MTL, HIGH_NS_OBJ
+
+    d = os.path.join(work, "high_ns")
+    os.makedirs(d)
+    for name, text in (("high_ns.mtl", HIGH_NS_MTL), ("high_ns.obj", HIGH_NS_OBJ)):
+        with open(os.path.join(d, name), "w") as f:
+            f.write(text)
+    os.makedirs(os.path.join(HERE, "loader"), exist_ok=True)
+    run_ref(["--dump-tris", os.path.join(d, "high_ns.obj"), os.path.join(HERE, "loader", "high_ns_obj.tris")], d)
+
+
 def main():
     if not os.path.exists(REF_BIN):
         sys.exit(f"{REF_BIN} missing: run `make ref` (needs {REF_DIR})")
     if sys.argv[1:] == ["--env-edge"]:  # the one fixture added later (its own seed; the others unchanged)
         with tempfile.TemporaryDirectory() as work:
             gen_kat_env_edge(work)
+        return
+    if sys.argv[1:] == ["--materials"]:  # the material fixtures alone (no random draws; the others unchanged)
+        with tempfile.TemporaryDirectory() as work:
+            gen_kat_calc_materials(work)
+            gen_loader_high_ns(work)
+            gen_meta()
         return
     rng = np.random.default_rng(20251003)
     with tempfile.TemporaryDirectory() as work:
@@ -470,6 +608,8 @@ def main():
             gen_kat_calc(work, rng, s, debug=True)
         gen_renders(work)
         gen_kat_env_edge(work)
+        gen_kat_calc_materials(work)
+        gen_loader_high_ns(work)
         gen_meta()
 
 

@@ -38,8 +38,8 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _hit_heavy(scene_name):
-    return "not hit-heavy" not in SCENES[scene_name][2]  # (tests/test_chain_path_scenes.py holds the notes to the probe)
+def _hit_heavy(scene_name, scenes=SCENES):
+    return "not hit-heavy" not in scenes[scene_name][2]  # (tests/test_chain_path_scenes.py holds the notes to the probe)
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,17 +58,18 @@ def _device_scene(scene_name):
     return rt.DeviceScene(SCENES[scene_name][0], None)
 
 
-def expected_report(scene_name, route, counters, resume=False, small_share=False):
-    """What run_chain / size_chain_lds choose for this launch (rtc_render.hip), from the scene's size and hit share."""
-    T = len(SCENES[scene_name][0])
+def expected_report(scene_name, route, counters, resume=False, small_share=False, scenes=SCENES):
+    """What run_chain / size_chain_lds choose for this launch (rtc_render.hip), from the scene's size and hit share;
+    `scenes`: another table of the same form (tests/material_scenes.py's)."""
+    T = len(scenes[scene_name][0])
     ncl = clusters_of(T)
     multi = ncl > CHUNK_CLUSTERS
-    wgs = 3 if small_share or not _hit_heavy(scene_name) else 4
+    wgs = 3 if small_share or not _hit_heavy(scene_name, scenes) else 4
     staged = prim_f_staged(T, wgs)
     in_kernel = route in IN_KERNEL_SUMS or small_share
     defer = not in_kernel or route == "hoisted" or not staged
     general = multi or counters or defer or resume
-    return dict(multi=multi, count=counters, hits=_hit_heavy(scene_name) and not general, general=general, spheres=False,
+    return dict(multi=multi, count=counters, hits=_hit_heavy(scene_name, scenes) and not general, general=general, spheres=False,
                 resume=resume, chain_prim_f=staged, wgs_per_cu=wgs, cluster_count=ncl,
                 chunk_count=(ncl + CHUNK_CLUSTERS - 1) // CHUNK_CLUSTERS)
 

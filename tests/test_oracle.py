@@ -66,6 +66,37 @@ def test_calc_color_kat(scene):
     assert np.array_equal(after, k["seed_after"])
 
 
+def test_calc_color_materials_kat():
+    """calcColor at materials outside [0, 1] (tests/material_scenes.py's finite scenes, each passed to the reference as
+    a triangles.txt in exact decimals): smoothness -1 .. 3e38, colours 0, -0, above 1 and negative, emission 3e38.  Bit-exact
+    on colour and seed; NaN colours compare by position.  This pins what the restatement reads into the source at these
+    values: fmax in double on signed zeros and NaN, (float)(1.0 / p) at p = 0 and inf, 1 - t in lerp."""
+    k = np.load(f"{GOLDEN}/kat_calc_materials.npz")
+    sc, _, _ = setup_from_flags({})
+    sph = scene_spheres("default")  # the reference's default mode keeps scene.h's sphere
+    seen = {"nan": 0, "inf": 0, "neg": 0}
+    for si, name in enumerate(k["names"]):
+        tris = k["tris"][k["tri_scene"] == si]
+        m = k["rec_scene"] == si
+        rays, seeds, mb = k["rays"][m], k["seeds"][m], k["max_bounce"][m]
+        assert len(rays) == 200 and len(tris) > 0
+        col, after, calls, _ = orc.calc_path(tris, sph, sc, 0, rays, seeds, mb)
+        want = k["color"][m]
+        nan = np.isnan(want)
+        assert np.array_equal(np.isnan(col), nan), name
+        assert np.array_equal(_bits(col)[~nan], _bits(want)[~nan]), name
+        assert np.array_equal(after, k["seed_after"][m]), name
+        col2, after2 = orc.calc_color(tris, sph, sc, 0, rays, seeds, mb)
+        assert np.array_equal(_bits(col2)[~nan], _bits(col)[~nan]) and np.array_equal(after2, after)
+        share = float((calls["winner"][:, 0] >= 0).mean())  # the records meet the triangles first, not the sphere
+        assert share > 0.5, f"{name}: only {share:.2f} of the records hit a triangle first"
+        seen["nan"] += int(nan.any(-1).sum())
+        seen["inf"] += int(np.isinf(want).any(-1).sum())
+        seen["neg"] += int((want < 0).any(-1).sum())
+    print(f"kat_calc_materials: {len(k['names'])} scenes; records with a NaN, inf, negative colour: {seen}")
+    assert len(k["names"]) == 27 and min(seen.values()) >= 10
+
+
 @pytest.mark.parametrize("scene", ["ultracomplex", "default"])
 def test_calc_debug_color_kat(scene):
     """calcDebugColor (raytracing.c:242-260), the bounce-count integrator (RTC_F_DEBUG_BOUNCES)."""

@@ -142,6 +142,52 @@ def test_triangle_file_parser_matches_reference(tmp_path):
     assert (tmp_path / "triangles.txt.parsed").exists()
 
 
+# objloader.c gives smoothness = sqrt(0.001 Ns) with no clamp: Ns above 1000 leaves [0, 1] (6250 -> 2.5, 4000 -> 2)
+HIGH_NS_MTL = """newmtl Over
+Ns 6250
+Kd 1.0 0.5 0.25
+Ke 0 0 0
+newmtl Two
+Ns 4000
+Kd 0.25 1.0 0.5
+Ke 0.5 0.5 0.5
+newmtl Edge
+Ns 1000.0001
+Kd 0.5 0.25 1.0
+"""
+
+HIGH_NS_OBJ = """mtllib high_ns.mtl
+o A
+v 0 0 0
+v 1 0 0
+v 0 1 0
+v 0 0 1
+vn 0 0 1
+vt 0 0
+usemtl Over
+f 1/1/1 2/1/1 3/1/1
+usemtl Two
+f 1/1/1 3/1/1 4/1/1
+usemtl Edge
+f 2/1/1 3/1/1 4/1/1
+usemtl Over
+f 1/1/1 4/1/1 2/1/1
+"""
+
+
+def test_obj_loader_keeps_smoothness_above_one(tmp_path):
+    """Ns 6250 and Ns 4000: the reference's loader stores smoothness 2.5 and 2, and so does scene_build.c, bit for bit
+    (tests/material_scenes.py renders what such values do)."""
+    (tmp_path / "high_ns.mtl").write_text(HIGH_NS_MTL)
+    (tmp_path / "high_ns.obj").write_text(HIGH_NS_OBJ)
+    want = _ref_tris("high_ns_obj", str(tmp_path / "high_ns.obj"), str(tmp_path))
+    got = rt.loadOBJTriangles(str(tmp_path / "high_ns.obj"))
+    assert len(got) == 4 and got.tobytes() == want.tobytes()
+    sm = want["mat"]["smoothness"]
+    assert sm[0] == np.float32(2.5) and sm[1] == np.float32(2.0) and sm[2] > 1 and sm[3] == sm[0]
+    assert np.array_equal(got["mat"]["smoothness"].view(np.uint32), sm.view(np.uint32))
+
+
 def test_default_triangles_golden_consistent():
     tris, tonly = load_tris("default")
     assert len(tris) == 14 and tonly == 0
