@@ -307,6 +307,36 @@ int rtc_render_samples_async(const RtcDeviceScene *s, const Scene *scene, const 
                              const RtcRenderDesc *d, const RtcSampleRange *range,
                              void *dColors, float *dAccum, unsigned int *dRngState,
                              unsigned long long *dSegments, void *stream);
+/* First-hit buffers: what every selected pixel's primary ray (main.c:88-94) sees, i.e. the result of
+ * calculateRayCollision(ray, d->trianglesOnly) (raytracing.c:216-240), for picking, depth compositing and denoiser guides.
+ * No Scene, no RNG, no samples: d->spp and d->maxBounce are ignored.  Each buffer is a DEVICE pointer on the scene's device
+ * or null (at least one is not); pixel (launch row r, x) lies at r * width + x, compact in launch-row order like dAccum,
+ * and the row selection (rowStart, rowStride, rowBand) means what it means for rtc_render_rows_async -- the values do not
+ * depend on the partition.
+ *   prim:   the winner: triangle index t >= 0, -2 - i for sphere i, -1 for a miss; ties keep the first in the reference's
+ *           order (spheres before triangles, ascending index, strict `<`)
+ *   depth:  closest.dst; 999999.f on a miss (the reference's initial value)
+ *   normal: a triangle's stored normal bit for bit; a sphere's normalized(hitPoint - centre), hitPoint = pos + dir * dst
+ *           (raytracing.c:181-182); +0, +0, +0 on a miss
+ *   albedo: closest.mat.color bit for bit; +0, +0, +0 on a miss
+ * Every value is the reference's bit for bit (the primary query of the render kernels: the tile cull's candidates, then the
+ * reference's arithmetic).  d->flags may carry RTC_F_NO_TILE_CULL (every record tested for every pixel; the same buffers,
+ * for A/B timing and tests).  Any number of spheres and a scene without triangles are accepted.
+ * Asynchronous on `stream` and complete at `stream` (joined, like a pass), under rtc_render_rows_async's rule that a scene
+ * serves one stream at a time.  It may come between pipelined RTC_F_OVERLAP launches, between the passes of a progressive
+ * frame and after rtc_scene_update_async (it reads the generation current when it is enqueued).  It neither records nor
+ * forgets the one-shot geometry and frame events, leaves rtc_scene_chain_report and rtc_scene_kernel_times as they were and
+ * restores the caller's current device.  rows_selected == 0: returns 0, nothing enqueued.
+ * RTC_EINVAL, with nothing enqueued: a null scene, camera, desc or `out`; all four pointers null; bad geometry (as
+ * rtc_render_rows_async); a flag other than RTC_F_NO_TILE_CULL. */
+typedef struct RtcHitBuffers {
+    int *prim;     /* 4 B / pixel */
+    float *depth;  /* 4 B / pixel */
+    float *normal; /* 12 B / pixel */
+    float *albedo; /* 12 B / pixel */
+} RtcHitBuffers;
+int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCamera *cam, const RtcRenderDesc *d,
+                               const RtcHitBuffers *out, void *stream);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */
@@ -362,6 +392,12 @@ int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
  * d->spp, the RNG-state buffer's identity (footprint resource 8).  That launch returns RTC_EINVAL where the entry point
  * would (a bad range, RTC_F_OVERLAP, no accumulator or state buffer). */
 int rtc_plan_sim_set_sample_range(RtcPlanSim *sim, int first, int count, unsigned long long rngBuffer);
+/* Makes the next rtc_plan_sim_launch (only) a first-hit launch (rtc_render_first_hit_async): the four buffers' identities
+ * (footprint resource 10, one write record per identity that is not 0; 0: the buffer is not asked for).  That launch's
+ * colors / accum / segments arguments are ignored; its kernel is kernel 10; it returns RTC_EINVAL where the entry point
+ * would (every identity 0, a flag other than RTC_F_NO_TILE_CULL, bad geometry). */
+int rtc_plan_sim_set_first_hit(RtcPlanSim *sim, unsigned long long prim, unsigned long long depth,
+                               unsigned long long normal, unsigned long long albedo);
 /* Plans one rtc_scene_update_async on the caller's stream `stream`, in rtc_plan_sim_launch's encodings: the waits, then the
  * refit kernel (kernel 9) with two footprint records -- it writes one generation of the scene records (resource 9, id = the
  * generation) and may read the other -- then one u64 record (~0, 0, the generation written, 0, 0, 0).  Launches planned

@@ -47,6 +47,7 @@ from ._abi import (  # noqa: F401
     RtcCamera,
     RtcChainReport,
     RtcError,
+    RtcHitBuffers,
     RtcLoopStats,
     RtcRenderDesc,
     RtcSampleRange,
@@ -266,6 +267,7 @@ class DeviceScene:
         h = C.c_void_p()
         check(lib().rtc_scene_upload(_ptr(t), nt, _ptr(s), ns, device, C.byref(h)), "rtc_scene_upload")
         self._h = h
+        self._device = device
         self.tri_count = nt
         self.sphere_count = ns
 
@@ -293,6 +295,42 @@ class DeviceScene:
                                              C.c_void_p(rng_ptr) if rng_ptr else None,
                                              C.c_void_p(segments_ptr) if segments_ptr else None,
                                              C.c_void_p(stream) if stream else None), "rtc_render_samples_async")
+
+    def render_first_hit_async(self, cam: RtcCamera, cfg: RenderConfig, prim_ptr: int = 0, depth_ptr: int = 0,
+                               normal_ptr: int = 0, albedo_ptr: int = 0, stream: int | None = None):
+        """rtc_render_first_hit_async: what every selected pixel's primary ray sees (calculateRayCollision,
+        raytracing.c:216-240), into the device buffers given (0: not wanted; at least one): prim int32 [rows, W]
+        (triangle t >= 0, sphere i as -2 - i, miss -1), depth float32 [rows, W] (999999 on a miss), normal and albedo
+        float32 [rows, W, 3] (+0 on a miss), the reference's values bit for bit.  Of cfg only the geometry, the row
+        selection, triangles_only and tile_cull count (no scene, samples or bounces).  Asynchronous on `stream`, complete
+        there; it leaves the frame and geometry events armed."""
+        d = cfg.desc()
+        d.flags = 0 if cfg.tile_cull else RTC_F_NO_TILE_CULL
+        out = RtcHitBuffers(prim_ptr or None, depth_ptr or None, normal_ptr or None, albedo_ptr or None)
+        check(lib().rtc_render_first_hit_async(self._h, C.byref(cam), C.byref(d), C.byref(out),
+                                               C.c_void_p(stream) if stream else None), "rtc_render_first_hit_async")
+
+    def first_hit(self, cam: RtcCamera, cfg: RenderConfig, want=("prim", "depth", "normal", "albedo")) -> dict:
+        """The first-hit buffers named in `want` as host arrays: allocates torch tensors on the scene's device, launches
+        render_first_hit_async on torch's current stream there, synchronises and returns {name: numpy array} -- prim
+        int32 [rows, W], depth float32 [rows, W], normal and albedo float32 [rows, W, 3]."""
+        import torch
+
+        shapes = {"prim": ((), torch.int32), "depth": ((), torch.float32), "normal": ((3,), torch.float32),
+                  "albedo": ((3,), torch.float32)}
+        want = tuple(want)
+        if not want or any(k not in shapes for k in want):
+            raise ValueError(f"DeviceScene.first_hit: want {want!r} is not a non-empty subset of {tuple(shapes)}")
+        rows = cfg.rows()
+        dev = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+        bufs = {k: torch.zeros((rows, cfg.width) + shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+        if rows == 0:  # (nothing selected: the empty tensors have no address to hand over)
+            return {k: bufs[k].cpu().numpy() for k in want}
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            self.render_first_hit_async(cam, cfg, *(bufs[k].data_ptr() if k in bufs else 0 for k in shapes), stream=st)
+            torch.cuda.current_stream().synchronize()
+        return {k: bufs[k].cpu().numpy() for k in want}
 
     def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
         """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with

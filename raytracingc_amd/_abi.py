@@ -69,6 +69,10 @@ class RtcSampleRange(C.Structure):  # samples [first, first + count) of RtcRende
     _fields_ = [("first", C.c_int), ("count", C.c_int)]
 
 
+class RtcHitBuffers(C.Structure):  # rtc_render_first_hit_async's device buffers, each nullable (include/rtc.h)
+    _fields_ = [("prim", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p)]
+
+
 class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geometry-kernel launch chose (include/rtc.h)
     _fields_ = [(k, C.c_int) for k in ("multi", "count", "hits", "general", "spheres", "resume", "chainPrimF", "wgsPerCu",
                                        "chainDyn", "clusterCount", "chunkCount", "launches")]
@@ -157,6 +161,7 @@ EXPORTS = [
     "rtc_scene_update_async", "rtc_scene_update", "rtc_plan_sim_update", "rtc_plan_sim_set_update_fault",
     "rtc_scene_records_host", "rtc_probe_scene_records",
     "rtc_scene_chain_report",
+    "rtc_render_first_hit_async", "rtc_plan_sim_set_first_hit",
 ]
 
 _lib = None
@@ -264,6 +269,10 @@ def lib() -> C.CDLL:
         L.rtc_probe_scene_records.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "rtc_scene_chain_report"):  # (absent from libraries of earlier rounds loaded for A/B timing)
         L.rtc_scene_chain_report.argtypes = [vp, C.POINTER(RtcChainReport)]
+    if hasattr(L, "rtc_render_first_hit_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_render_first_hit_async.argtypes = [vp, C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
+                                                 C.POINTER(RtcHitBuffers), vp]
+        L.rtc_plan_sim_set_first_hit.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
     _lib = L
     return L
 

@@ -103,6 +103,24 @@ void set_sample_range(Request &r, int first, int count, uint64_t rngState)
     r.flags &= ~RTC_F_OVERLAP; /* (the entry point refuses it) */
 }
 
+void set_first_hit(Request &r, const uint64_t ids[4])
+{
+    r.firstHit = true;
+    memcpy(r.hit, ids, sizeof r.hit);
+    r.flags &= RTC_F_NO_TILE_CULL; /* (the entry point refuses every other flag) */
+    r.segments = false;
+    /* no Color, accumulator or sample decides what it writes: the key is the camera and the rows alone */
+    r.key.colors = r.key.accum = 0;
+}
+
+int geometry_error(const RtcRenderDesc &d)
+{
+    if (d.width <= 0 || d.height <= 0 || d.rowStride <= 0 || d.rowStart < 0 || d.rowBand < 0 || d.rowBand > 64 ||
+        (d.rowBand & (d.rowBand - 1)) != 0)
+        return 1;
+    return (long long)d.width * d.height > (1ll << 31) / 4 ? 2 : 0;
+}
+
 void plan_launch(const State &s, const Request &r, Plan &p)
 {
     memset(&p, 0, sizeof p);
@@ -111,8 +129,10 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     Emitter E{p};
     if (r.rows <= 0) { /* nothing to render: the (empty) frame is complete once the caller's stream gets here */
         p.empty = true;
-        E.record(kStCaller, kEvGeometry);
-        E.record(kStCaller, kEvFrame);
+        if (!r.firstHit) { /* (a first-hit launch leaves the caller's hooks armed) */
+            E.record(kStCaller, kEvGeometry);
+            E.record(kStCaller, kEvFrame);
+        }
         return;
     }
     const size_t px = (size_t)r.width * (size_t)r.rows;
@@ -124,7 +144,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     /* the split launch (rtc_render_chain + the sky pass): every triangle-only scene, and the sphere scenes sphere_split
      * admits */
     p.fused = p.cull && !p.debug && (r.sphereCount == 0 || r.sphereSplit) &&
-              !(r.flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER));
+              !(r.flags & (RTC_F_NO_COOP | RTC_F_NO_REORDER)) && !r.firstHit;
     p.chain = p.fused;
     p.gridX = (unsigned)((r.width + 15) / 16);
     p.gridY = (unsigned)((r.rows + 15) / 16);
@@ -168,11 +188,15 @@ void plan_launch(const State &s, const Request &r, Plan &p)
      * it rewrites (unless its culls move to a cull stream, which waits for that slot itself, below), or writes the same
      * Color or accumulator buffer with other rows, camera or environment.  One wait on the newest such pass covers every
      * earlier one (the side stream runs them in order); evSkyDone[h] also covers launch h's geometry kernel. */
+    /* A first-hit launch writes no Color or accumulator row: it waits like an overlapped launch that keeps the caller's
+     * stream, for the pass that reads its slot (0) and its primary records, and for no other. */
+    const bool waitAll = !p.overlap && !r.firstHit;
     int waitSky = -1;
     for (int h = 0; h < kSlots; ++h)
         if (s.skyPending[h] &&
-            (!p.overlap || (h == p.half && p.cs == kStCaller) ||
-             ((s.skyKey[h].colors == r.key.colors || (r.key.accum && s.skyKey[h].accum == r.key.accum)) &&
+            (waitAll || (h == p.half && p.cs == kStCaller) ||
+             (!r.firstHit &&
+              (s.skyKey[h].colors == r.key.colors || (r.key.accum && s.skyKey[h].accum == r.key.accum)) &&
               memcmp(&s.skyKey[h], &r.key, sizeof r.key) != 0)) &&
             (waitSky < 0 || s.skySeq[h] > s.skySeq[waitSky]))
             waitSky = h;
@@ -213,9 +237,11 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     }
     /* what the launch binds: the executor hands its kernels these buffers and no other, and only these have footprints */
     const auto bind = [&p](bool on, std::initializer_list<int> bufs) { for (int b : bufs) p.bound |= (unsigned)on << b; };
-    bind(true, {kBufPrim, kBufColors, kBufSceneGen});
+    bind(true, {kBufPrim, kBufSceneGen});
+    bind(!r.firstHit, {kBufColors});
+    bind(r.firstHit, {kBufHit});
     bind(p.cull, {kBufMask, kBufPixMask, kBufWeight});
-    bind(p.cull && !p.fused, {kBufOrder});
+    bind(p.cull && !p.fused && !r.firstHit, {kBufOrder});
     bind(p.superCull, {kBufSuperMask});
     bind(p.chain, {kBufGeoList, kBufGeoSet, kBufGeoSetNext});
     bind(p.merge, {kBufPixItem, kBufGeoColor});
@@ -257,6 +283,12 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     }
     if (p.superCull)
         E.kernel(p.cs, kKSuperCull);
+    if (r.firstHit) { /* joined by construction: every kernel on the caller's stream, no hook, no counter set */
+        if (p.cull)
+            E.kernel(kStCaller, kKTileCull);
+        E.kernel(kStCaller, kKFirstHit);
+        return;
+    }
     if (!p.cull) {
         E.kernel(kStCaller, kKRender);
     } else {
@@ -383,6 +415,10 @@ const Touch kTouches[] = {
     {kKPrep, kBufSceneGen, kRead, kAlways},        {kKSuperCull, kBufSceneGen, kRead, kAlways},
     {kKTileCull, kBufSceneGen, kRead, kAlways},    {kKSky, kBufSceneGen, kRead, kAlways},
     {kKChain, kBufSceneGen, kRead, kAlways},       {kKRender, kBufSceneGen, kRead, kAlways},
+    /* rtc_first_hit: the tile's candidate words (none with RTC_F_NO_TILE_CULL: unbound), the slot's primary
+     * records, the scene records, and the caller's buffers */
+    {kKFirstHit, kBufMask, kRead, kAlways},        {kKFirstHit, kBufPrim, kRead, kAlways},
+    {kKFirstHit, kBufSceneGen, kRead, kAlways},    {kKFirstHit, kBufHit, kWrite, kAlways},
 };
 } // namespace
 
@@ -392,7 +428,7 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
     const struct { int res; unsigned long long id; } outside[kBufs - kScratchRegions] = {
         {kResPrim, (unsigned long long)p.half}, {kResGeoSet, p.geoSet}, {kResGeoSet, p.geoSetNext}, {kResSamples, 0},
         {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0},
-        {kResRngState, r.rngState}, {kResSceneGen, (unsigned long long)p.gen}};
+        {kResRngState, r.rngState}, {kResSceneGen, (unsigned long long)p.gen}, {kResHit, 0}};
     int k = 0;
     for (const Touch &t : kTouches) {
         const bool when = t.when == kAlways || (t.when == kIfResumeRead ? p.resumeRead
@@ -400,6 +436,15 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
                                                                           : p.merge == (t.when == kIfMerge));
         if (t.kernel != kernel || !p.binds(t.buf) || !when)
             continue;
+        if (t.buf == kBufHit) { /* one row per buffer asked for, its identity the caller's */
+            for (const uint64_t id : r.hit)
+                if (id) {
+                    if (k < max)
+                        out[k] = Footprint{kResHit, t.access, id, 0, 1};
+                    ++k;
+                }
+            continue;
+        }
         if (k < max && t.buf < kScratchRegions)
             out[k] = Footprint{kResScratch, t.access, 0, p.slotOffset + p.reg[t.buf].offset,
                                p.slotOffset + p.reg[t.buf].offset + p.reg[t.buf].size};
@@ -452,6 +497,8 @@ struct RtcPlanSim {
     int first, count;
     unsigned long long rngBuffer;
     int updateFault; /* rtc_plan_sim_set_update_fault */
+    bool hitNext;    /* rtc_plan_sim_set_first_hit: the next launch is a first-hit launch */
+    uint64_t hit[4];
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -485,6 +532,16 @@ extern "C" int rtc_plan_sim_set_sample_range(RtcPlanSim *s, int first, int count
     return 0;
 }
 
+extern "C" int rtc_plan_sim_set_first_hit(RtcPlanSim *s, unsigned long long prim, unsigned long long depth,
+                                          unsigned long long normal, unsigned long long albedo)
+{
+    if (!s)
+        return RTC_EINVAL;
+    s->hitNext = true;
+    s->hit[0] = prim, s->hit[1] = depth, s->hit[2] = normal, s->hit[3] = albedo;
+    return 0;
+}
+
 extern "C" int rtc_plan_sim_release(RtcPlanSim *s)
 {
     delete s;
@@ -500,6 +557,14 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
     rtcplan::Request r = rtcplan::make_request(*d, rtc_rows_selected(d), s->shape, stream, colors, accum, segments != 0,
                                                cam, env);
     r.legacySlotLayout = s->legacy != 0;
+    if (s->hitNext) { /* a first-hit launch, refused as rtc_render_first_hit_async refuses it; consumed either way */
+        s->hitNext = false;
+        s->ranged = false;
+        if (!(s->hit[0] | s->hit[1] | s->hit[2] | s->hit[3]) || (d->flags & ~RTC_F_NO_TILE_CULL) ||
+            rtcplan::geometry_error(*d))
+            return RTC_EINVAL;
+        rtcplan::set_first_hit(r, s->hit);
+    }
     if (s->ranged) { /* a pass, refused as rtc_render_samples_async refuses it; the range is consumed either way */
         s->ranged = false;
         if (s->first < 0 || s->count <= 0 || s->first > d->spp - s->count || (d->flags & RTC_F_OVERLAP) || !accum ||

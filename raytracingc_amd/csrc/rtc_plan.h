@@ -60,7 +60,9 @@ enum Event : int {
     kEvents = 5 + 2 * kSlots
 };
 enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce,
-                    kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */ };
+                    kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */,
+                    kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */ };
+static_assert(kKRefit == 9 && kKFirstHit == 10, "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
     int kind;   /* OpKind */
@@ -124,6 +126,10 @@ struct Request {
     bool resume;
     int sampleFirst, sampleCount;
     uint64_t rngState;
+    /* a first-hit launch (set_first_hit): the identities of the caller's prim, depth, normal and albedo
+     * buffers, 0 where one is not asked for */
+    bool firstHit;
+    uint64_t hit[4];
 };
 
 /* the scene's shape as the planner needs it (RtcDeviceScene; rtc_plan_sim_create / _set_spheres) */
@@ -143,6 +149,18 @@ Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uin
  * never takes the alternating cull streams. */
 void set_sample_range(Request &r, int first, int count, uint64_t rngState);
 
+/* Makes r a first-hit launch (rtc_render_first_hit_async; the caller has checked that one identity is not 0 and that the
+ * flags are RTC_F_NO_TILE_CULL at most).  It is never overlapped and keeps to the caller's stream (never the alternating
+ * cull streams): rtc_prep_primary where slot 0's records are stale, rtc_super_cull above kSuperCullPixels, the triangle
+ * tile cull, then rtc_first_hit -- no sky, chain, accumulate, order, render or reduce kernel, no Color or accumulator
+ * buffer, no counter set, list or sample slot, and with RTC_F_NO_TILE_CULL no scratch at all.  It waits for an overlapped
+ * launch still in flight in slot 0 and for no other; it records neither of the caller's two hooks. */
+void set_first_hit(Request &r, const uint64_t ids[4]);
+
+/* The geometry every launch's entry point checks (rtc_render_rows_async's check_arguments, the first-hit test hook):
+ * 0 fine, 1 bad geometry (sizes, row selection, band), 2 a frame of more than 2^29 pixels */
+int geometry_error(const RtcRenderDesc &d);
+
 /* The launch-scoped buffers: the regions of one scratch slot, in slot order, then the resources outside it */
 enum Buf : int {
     kBufMask,      /* per tile: maskWords u64 of candidate triangles */
@@ -161,6 +179,7 @@ enum Buf : int {
     kBufColors, kBufAccum, kBufCallerSegments, /* the caller's */
     kBufRngState,               /* the caller's per-pixel RNG states (a pass, Request::resume) */
     kBufSceneGen,               /* the scene records of the bound generation (Plan::gen) */
+    kBufHit,                    /* the caller's first-hit buffers (Request::hit: one footprint row per buffer asked for) */
     kBufs
 };
 struct Region {
@@ -206,7 +225,8 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 
 /* The memory one kernel of a plan touches, for the ordering test: resource kinds and byte ranges */
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
-                 kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */ };
+                 kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */,
+                 kResHit = 10 /* id: the caller's buffer */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;

@@ -98,6 +98,7 @@ extern "C" int rtc_device_count(int *count)
 #include "rtc_lane.h"
 #include "rtc_sky.h"
 #include "rtc_chain.h"
+#include "rtc_first_hit.h"
 
 /* A kernel launch whose completion also records `stop` (null: a plain launch): the event is the dispatch's own
  * completion signal, so the stream gets no separate marker packet -- each marker on the launch stream cost ~5-7 us
@@ -186,6 +187,7 @@ struct Launch {
     int wgsPerCu;    /* the geometry kernel's workgroups per CU */
     size_t chainDyn; /* and its dynamic LDS */
     bool resume;     /* a pass (rtc_render_samples_async): the RESUME kernels */
+    const RtcHitBuffers *hit = nullptr; /* a first-hit launch (rtc_render_first_hit_async): its buffers */
     dim3 grid() const { return dim3(pl.gridX, pl.gridY); } /* one 16x16 workgroup block each */
     /* every pointer into the scratch: a region the plan binds (rtcplan::Buf), in the launch's slot; unbound: null */
     template <typename T> T *region(int buf) const
@@ -194,25 +196,33 @@ struct Launch {
     }
 };
 
-static int check_arguments(const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d, const void *dColors)
+/* `who`: the entry point, for the error texts.  `hit`: a first-hit launch (no Scene, its buffers in place of dColors; every
+ * flag but RTC_F_NO_TILE_CULL refused). */
+static int check_arguments(const char *who, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                           const void *dColors, const RtcHitBuffers *hit)
 {
-    if (!scene || !cam || !d || !dColors)
-        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null argument");
-    if (d->width <= 0 || d->height <= 0 || d->rowStride <= 0 || d->rowStart < 0 || d->rowBand < 0 || d->rowBand > 64 ||
-        (d->rowBand & (d->rowBand - 1)) != 0)
-        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: bad geometry %dx%d rows %d+k*%d", d->width, d->height,
-                        d->rowStart, d->rowStride);
-    if ((long long)d->width * d->height > (1ll << 31) / 4)
+    if ((!scene && !hit) || !cam || !d || (!dColors && !hit))
+        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
+    if (hit && !hit->prim && !hit->depth && !hit->normal && !hit->albedo)
+        return rtc_fail(RTC_EINVAL, "%s: no buffer asked for (prim, depth, normal and albedo are all null)", who);
+    const int geometry = rtcplan::geometry_error(*d);
+    if (geometry == 1)
+        return rtc_fail(RTC_EINVAL, "%s: bad geometry %dx%d rows %d+k*%d", who, d->width, d->height, d->rowStart,
+                        d->rowStride);
+    if (geometry)
         return rtc_fail(RTC_EINVAL, "frame too large");
+    if (hit && (d->flags & ~RTC_F_NO_TILE_CULL))
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (a first-hit launch takes RTC_F_NO_TILE_CULL and no other flag)", who,
+                        d->flags);
     if (d->flags & (RTC_F_COOP4 | RTC_F_COOP8 | RTC_F_PIPE | RTC_F_SPEC))
-        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: RTC_F_COOP4 / COOP8 / PIPE / SPEC name kernels that were "
-                                    "removed (rtc_render_chain renders every geometry pixel)");
+        return rtc_fail(RTC_EINVAL, "%s: RTC_F_COOP4 / COOP8 / PIPE / SPEC name kernels that were "
+                                    "removed (rtc_render_chain renders every geometry pixel)", who);
     return 0;
 }
 
 /* what the kernels read of the scene's shape, the launch's shape and the camera (the plan's buffers, the scene records
  * among them: bind_plan) */
-static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, const RtcCamera &cam,
+static RenderParams render_params(const RtcDeviceScene *s, const Scene *scene, const RtcCamera &cam,
                                   const RtcRenderDesc &d, int rows, void *dColors, float *dAccum,
                                   unsigned long long *dSegments, const RtcSampleRange *range)
 {
@@ -233,7 +243,8 @@ static RenderParams render_params(const RtcDeviceScene *s, const Scene &scene, c
     P.hoist = (d.flags & RTC_F_HOIST_PRIMARY) ? 1 : 0;
     P.invSpp = d.spp > 0 ? (float)(1. / (double)d.spp) : 0.f;
     P.origin = v3(cam.origin), P.ex = v3(cam.ex), P.ey = v3(cam.ey), P.ez = v3(cam.ez), P.fov = cam.fov;
-    P.env = env_of(scene);
+    if (scene) /* (a first-hit launch has none: its kernel evaluates no environment) */
+        P.env = env_of(*scene);
     return P;
 }
 
@@ -439,26 +450,45 @@ static int run_reduce(const Launch &L, hipStream_t os, hipEvent_t)
     return 0;
 }
 
-static int (*const kPlanned[])(const Launch &, hipStream_t, hipEvent_t) = { /* by rtcplan::Kernel */
-    run_prep, run_super_cull, run_tile_cull, run_sky, run_chain, run_accumulate, run_order, run_render, run_reduce};
-static_assert(sizeof kPlanned / sizeof kPlanned[0] == rtcplan::kKReduce + 1, "one function per planned kernel");
+static int run_first_hit(const Launch &L, hipStream_t os, hipEvent_t)
+{
+    /* <SPHERES> */
+    static void (*const kFirstHit[2])(RenderParams, int *, float *, float *, float *) = {rtc_first_hit<false>,
+                                                                                         rtc_first_hit<true>};
+    const RtcHitBuffers &h = *L.hit;
+    HIP_TRY(launch_stop(kFirstHit[L.P.sphereCount > 0], L.grid(), dim3(kBlock), 0, os, nullptr, L.P, h.prim, h.depth,
+                        h.normal, h.albedo));
+    return 0;
+}
+
+/* by rtcplan::Kernel (null: rtc_scene_update_async's refit kernel, which no launch plans) */
+static int (*const kPlanned[])(const Launch &, hipStream_t, hipEvent_t) = {
+    run_prep,  run_super_cull, run_tile_cull, run_sky, run_chain,    run_accumulate,
+    run_order, run_render,     run_reduce,    nullptr, run_first_hit};
+static_assert(sizeof kPlanned / sizeof kPlanned[0] == rtcplan::kKFirstHit + 1 && rtcplan::kKRefit == rtcplan::kKReduce + 1,
+              "one function per planned kernel");
 
 /* rtc_render_rows_async; with `items` (rtc_cull_items) the launch's preparation and culls alone: the kernels after the
  * tile cull are not enqueued (the plan's events are, so the ordering state stays true: a launch whose render kernels did
- * nothing), and `items` gets the launch's counter set and list regions */
+ * nothing), and `items` gets the launch's counter set and list regions.  With `hit` (rtc_render_first_hit_async) a
+ * first-hit launch: no Scene, Color, accumulator or counters; the caller's hooks stay armed and the split launch's timing
+ * and report as they were. */
 static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                        void *dColors, float *dAccum, unsigned long long *dSegments, void *stream, RtcCullItems *items,
-                       const RtcSampleRange *range = nullptr, unsigned *dRngState = nullptr)
+                       const RtcSampleRange *range = nullptr, unsigned *dRngState = nullptr,
+                       const RtcHitBuffers *hit = nullptr)
 {
+    const char *const who = hit ? "rtc_render_first_hit_async" : "rtc_render_rows_async";
     if (!s)
-        return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: null scene");
+        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
     RtcDeviceScene *const ms = const_cast<RtcDeviceScene *>(s);
     /* The hooks are one-shot: this launch takes the events armed before it and forgets them -- before any early
      * return, so a later launch never records an event its caller has since released (rtc_scene_set_geometry_event /
-     * _frame_event); a launch that fails records neither */
-    const hipEvent_t geoEvent = s->geoEvent, frameEvent = s->frameEvent;
-    ms->geoEvent = ms->frameEvent = nullptr;
-    if (const int rc = check_arguments(scene, cam, d, dColors))
+     * _frame_event); a launch that fails records neither.  (A first-hit launch is not a frame: it leaves them armed.) */
+    const hipEvent_t geoEvent = hit ? nullptr : s->geoEvent, frameEvent = hit ? nullptr : s->frameEvent;
+    if (!hit)
+        ms->geoEvent = ms->frameEvent = nullptr;
+    if (const int rc = check_arguments(who, scene, cam, d, dColors, hit))
         return rc;
     if (range) { /* rtc_render_samples_async: nothing is enqueued for a pass that is refused */
         if (!dAccum || !dRngState)
@@ -474,7 +504,7 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
     /* the scene's buffers, scratch and kernels live on s->device; the caller's current device is restored */
     RtcDeviceGuard guard(s->device);
     if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "rtc_render_rows_async: cannot select the scene's device %d", s->device);
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
     const hipStream_t st = (hipStream_t)stream;
     if (rows == 0) { /* nothing to render: the (empty) frame is complete once `stream` gets here */
         for (hipEvent_t ev : {geoEvent, frameEvent})
@@ -483,7 +513,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         return 0;
     }
     static thread_local rtcplan::Plan pl;
-    Launch L{s, pl, render_params(s, *scene, *cam, *d, rows, dColors, dAccum, dSegments, range), 0, 0, range != nullptr};
+    Launch L{s, pl, render_params(s, scene, *cam, *d, rows, dColors, dAccum, dSegments, range), 0, 0, range != nullptr,
+             hit};
     /* every ordering decision -- slot, streams, events, which kernels, which buffers -- comes from the planner
      * (rtc_plan.h); this function executes its operations */
     const RenderParams &P = L.P;
@@ -499,11 +530,17 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
     rq.noMerge = !RTC_SKY_MERGE;
     if (range)
         rtcplan::set_sample_range(rq, range->first, range->count, (uint64_t)(uintptr_t)dRngState);
+    if (hit) {
+        const uint64_t ids[4] = {(uint64_t)(uintptr_t)hit->prim, (uint64_t)(uintptr_t)hit->depth,
+                                 (uint64_t)(uintptr_t)hit->normal, (uint64_t)(uintptr_t)hit->albedo};
+        rtcplan::set_first_hit(rq, ids);
+    }
     rtcplan::plan_launch(s->plan, rq, pl);
     /* the saved state claims only what has been enqueued: until every operation below is, a later launch sees none of
      * this launch's primary records or counter zeroing (it re-runs rtc_prep_primary) */
     ms->plan.prepValid[pl.half] = false;
-    ms->plan.cullValid = false;
+    if (!hit) /* (a first-hit launch touches no counter set) */
+        ms->plan.cullValid = false;
     if (const int rc = grow_capacity(ms, pl))
         return rc;
     bind_plan(L, d->flags);
@@ -525,8 +562,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
                 HIP_TRY(hipEventRecord(ev, os));
         } else if (op.kind == rtcplan::kOpWait) {
             HIP_TRY(hipStreamWaitEvent(os, ev, 0));
-        } else if (op.kernel < 0 || op.kernel > rtcplan::kKReduce) {
-            return rtc_fail(RTC_EINVAL, "rtc_render_rows_async: unknown planned kernel %d", op.kernel);
+        } else if (op.kernel < 0 || op.kernel > rtcplan::kKFirstHit || !kPlanned[op.kernel]) {
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned kernel %d", who, op.kernel);
         } else if (items && op.kernel > rtcplan::kKTileCull) {
             if (ev) /* (the skipped kernel's completion) */
                 HIP_TRY(hipEventRecord(ev, os));
@@ -534,7 +571,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
             return rc;
         }
     }
-    ms->timed = pl.fused && s->timing;
+    if (!hit)
+        ms->timed = pl.fused && s->timing;
     ms->plan = pl.after; /* every operation is enqueued */
     if (items) {
         if (!pl.chain)
@@ -560,6 +598,16 @@ extern "C" int rtc_render_samples_async(const RtcDeviceScene *s, const Scene *sc
     if (!range)
         return rtc_fail(RTC_EINVAL, "rtc_render_samples_async: null sample range");
     return render_rows(s, scene, cam, d, dColors, dAccum, dSegments, stream, nullptr, range, dRngState);
+}
+
+extern "C" int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCamera *cam, const RtcRenderDesc *d,
+                                          const RtcHitBuffers *out, void *stream)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_render_first_hit_async: null scene");
+    if (!out)
+        return rtc_fail(RTC_EINVAL, "rtc_render_first_hit_async: null argument");
+    return render_rows(s, nullptr, cam, d, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr, out);
 }
 
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
@@ -700,3 +748,6 @@ template __global__ void rtc_render_kernel<false, false, true>(RenderParams);
 template __global__ void rtc_render_kernel<false, true, true>(RenderParams);
 template __global__ void rtc_render_kernel<true, false, true>(RenderParams);
 template __global__ void rtc_render_kernel<true, true, true>(RenderParams);
+/* the first-hit buffers */
+template __global__ void rtc_first_hit<false>(RenderParams, int *, float *, float *, float *);
+template __global__ void rtc_first_hit<true>(RenderParams, int *, float *, float *, float *);
