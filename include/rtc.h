@@ -70,7 +70,8 @@ typedef struct RtcRenderDesc {
                                     (rtc_render_kernel), instead of by the split launch's rtc_render_chain
                                     (A/B timing; the frame is identical) */
 #define RTC_F_NO_CLUSTER_CULL 0x20 /* bounce rays test every triangle instead of only the clusters their
-                                      half-line may reach (A/B timing; identical frame) */
+                                      half-line may reach (A/B timing; identical frame); rtc_trace_rays_async: every
+                                      record in reference order, no ball test (identical buffers) */
 /* The split launch renders the pixels that see geometry with rtc_render_chain (state-indexed samples: lanes
  * evaluate the samples that start at consecutive RNG offsets, then the chain of the reference's samples is walked
  * in order).  0x40, 0x80, 0x100 and 0x200 selected older kernels for A/B timing; they were removed and these flags
@@ -337,6 +338,30 @@ typedef struct RtcHitBuffers {
 } RtcHitBuffers;
 int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCamera *cam, const RtcRenderDesc *d,
                                const RtcHitBuffers *out, void *stream);
+/* Closest hits of caller-supplied rays: element i of each buffer of `out` is
+ * calculateRayCollision(dRays[i], trianglesOnly) (raytracing.c:216-240) against the resident scene, in RtcHitBuffers'
+ * encoding (above; hitPoint = pos + dir * dst of ray i), every value the reference's bit for bit.  dRays: n Rays (24 B:
+ * pos, dir) in DEVICE memory on the scene's device; it must not alias an output buffer.  The direction is used as given:
+ * it is not normalised (the reference does not), dst is in units of dir, and the EPSILON tests on det and dst see the
+ * caller's scale; zero, NaN and infinite components get what the reference's arithmetic gives (a zero direction can hit a
+ * sphere).  Any number of spheres and a scene without triangles are accepted; trianglesOnly != 0 skips the spheres.
+ * flags: 0 -- the cluster hierarchy (bounding balls over 8 triangles and over 32 clusters, exact for every ray; a ray of
+ * |dir|_1 > 4 tests every cluster) -- or RTC_F_NO_CLUSTER_CULL: every record in reference order, the same buffers.
+ * Asynchronous on `stream` and complete at `stream`, under the rule that a scene serves one stream at a time.  It reads the
+ * generation of scene records current when it is enqueued (after rtc_scene_update_async on that stream: the new
+ * geometry), may come between RTC_F_OVERLAP launches and between passes, uses no scratch, primary record, counter set,
+ * stream or event of the scene's -- it waits for nothing, and nothing waits for it, beyond stream order -- leaves the
+ * one-shot frame and geometry events, rtc_scene_chain_report and rtc_scene_kernel_times as they were and restores the
+ * caller's current device.  n == 0: returns 0, nothing enqueued.
+ * RTC_EINVAL, with nothing enqueued, checked before any device call: a null scene, dRays or `out`; all four pointers
+ * null; n > 0x7fffffff; a flag other than RTC_F_NO_CLUSTER_CULL. */
+int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, int trianglesOnly, int flags,
+                         const RtcHitBuffers *out, void *stream);
+/* The same for HOST arrays, synchronous: stages the rays, waits for the device, runs the query on the null stream and
+ * copies back the arrays asked for (null: not wanted; at least one): prim[n], depth[n], normal[3 n], albedo[3 n].  The
+ * same refusals; RTC_ENODEV without a GPU. */
+int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trianglesOnly, int flags, int *prim,
+                   float *depth, float *normal, float *albedo);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */
@@ -407,6 +432,15 @@ int rtc_plan_sim_set_first_hit(RtcPlanSim *sim, unsigned long long prim, unsigne
 int rtc_plan_sim_update(RtcPlanSim *sim, unsigned long long stream, int *ops, int maxOps, unsigned long long *footprint,
                         int maxFootprint);
 int rtc_plan_sim_set_update_fault(RtcPlanSim *sim, int mode);
+/* Plans one rtc_trace_rays_async on the caller's stream `stream`, in rtc_plan_sim_update's encodings: one kernel op (kernel
+ * 11, stream 0, no event) with its footprint records -- it reads the current generation (resource 9, id = the generation)
+ * and the ray buffer (resource 11, id = `rays`) and writes each hit buffer asked for (resource 10, id = hit[k]; 0: not
+ * asked for), in that order -- then one u64 record (~0, 0, the generation read, 0, 0, 0).  The planner's state is left as
+ * it was.  RTC_EINVAL where the entry point refuses: `rays` 0, every hit identity 0, a flag other than
+ * RTC_F_NO_CLUSTER_CULL. */
+int rtc_plan_sim_trace_rays(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays,
+                            const unsigned long long hit[4], int flags, int *ops, int maxOps,
+                            unsigned long long *footprint, int maxFootprint);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the

@@ -332,6 +332,60 @@ class DeviceScene:
             torch.cuda.current_stream().synchronize()
         return {k: bufs[k].cpu().numpy() for k in want}
 
+    def trace_rays_async(self, rays_ptr: int, n: int, triangles_only: bool = False, flags: int = 0, prim_ptr: int = 0,
+                         depth_ptr: int = 0, normal_ptr: int = 0, albedo_ptr: int = 0, stream: int | None = None):
+        """rtc_trace_rays_async: the closest hit of n caller-supplied Rays (24 B each: pos, dir; device memory at
+        rays_ptr) against the resident scene, calculateRayCollision(ray, trianglesOnly) (raytracing.c:216-240) bit for
+        bit, into the device buffers given (0: not wanted; at least one): prim int32 [n] (triangle t >= 0, sphere i as
+        -2 - i, miss -1), depth float32 [n] (999999 on a miss), normal and albedo float32 [n, 3] (+0 on a miss).  The
+        direction is used as given (not normalised).  flags: 0 or RTC_F_NO_CLUSTER_CULL (every record, the same
+        buffers).  Asynchronous on `stream`, complete there; the scene's ordering state and events stay as they were."""
+        out = RtcHitBuffers(prim_ptr or None, depth_ptr or None, normal_ptr or None, albedo_ptr or None)
+        check(lib().rtc_trace_rays_async(self._h, C.c_void_p(rays_ptr) if rays_ptr else None, n, int(bool(triangles_only)),
+                                         flags, C.byref(out), C.c_void_p(stream) if stream else None),
+              "rtc_trace_rays_async")
+
+    def trace_rays(self, rays, triangles_only: bool = False, want=("prim", "depth", "normal", "albedo"),
+                   flags: int = 0) -> dict:
+        """The closest hits of `rays` as host arrays, {name: numpy array} for the names in `want`: prim int32 [n], depth
+        float32 [n], normal and albedo float32 [n, 3] (trace_rays_async's values).  `rays`: a numpy array of RAY_DT [n]
+        or float32 [n, 6] (pos, dir), which takes the synchronous host entry rtc_trace_rays; or a torch tensor on the
+        scene's device (float32 [n, 6], or any contiguous tensor of n x 24 bytes), which is read in place by
+        rtc_trace_rays_async on torch's current stream there -- the results are numpy arrays in both cases."""
+        shapes = {"prim": ((), np.int32), "depth": ((), np.float32), "normal": ((3,), np.float32),
+                  "albedo": ((3,), np.float32)}
+        want = tuple(want)
+        if not want or any(k not in shapes for k in want):
+            raise ValueError(f"DeviceScene.trace_rays: want {want!r} is not a non-empty subset of {tuple(shapes)}")
+        if hasattr(rays, "data_ptr"):
+            import torch
+
+            nbytes = rays.numel() * rays.element_size()
+            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
+                raise ValueError("DeviceScene.trace_rays: rays must be a contiguous device tensor of whole 24-byte Rays")
+            n = nbytes // RAY_DT.itemsize
+            kinds = {np.int32: torch.int32, np.float32: torch.float32}
+            bufs = {k: torch.zeros((n,) + shapes[k][0], dtype=kinds[shapes[k][1]], device=rays.device) for k in want}
+            if n:
+                with torch.cuda.device(rays.device):
+                    st = torch.cuda.current_stream().cuda_stream
+                    self.trace_rays_async(rays.data_ptr(), n, triangles_only, flags,
+                                          *(bufs[k].data_ptr() if k in bufs else 0 for k in shapes), stream=st)
+                    torch.cuda.current_stream().synchronize()
+            return {k: bufs[k].cpu().numpy() for k in want}
+        a = np.asarray(rays)
+        if a.dtype != RAY_DT:
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError("DeviceScene.trace_rays: rays must be RAY_DT [n] or float32 [n, 6]")
+            a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
+        a = np.ascontiguousarray(a.reshape(-1))
+        n = len(a)
+        out = {k: np.zeros((n,) + shapes[k][0], shapes[k][1]) for k in want}
+        if n:
+            check(lib().rtc_trace_rays(self._h, _ptr(a), n, int(bool(triangles_only)), flags,
+                                       *(_ptr(out[k]) if k in out else None for k in shapes)), "rtc_trace_rays")
+        return out
+
     def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
         """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with
         `state` -- a frame saved earlier, load_progress -- to the samples it still lacks).  It owns the three device

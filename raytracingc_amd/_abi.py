@@ -162,6 +162,7 @@ EXPORTS = [
     "rtc_scene_records_host", "rtc_probe_scene_records",
     "rtc_scene_chain_report",
     "rtc_render_first_hit_async", "rtc_plan_sim_set_first_hit",
+    "rtc_trace_rays_async", "rtc_trace_rays", "rtc_plan_sim_trace_rays",
 ]
 
 _lib = None
@@ -273,6 +274,10 @@ def lib() -> C.CDLL:
         L.rtc_render_first_hit_async.argtypes = [vp, C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
                                                  C.POINTER(RtcHitBuffers), vp]
         L.rtc_plan_sim_set_first_hit.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
+    if hasattr(L, "rtc_trace_rays_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_trace_rays_async.argtypes = [vp, vp, sz, ip, ip, C.POINTER(RtcHitBuffers), vp]
+        L.rtc_trace_rays.argtypes = [vp, vp, sz, ip, ip, vp, vp, vp, vp]
+        L.rtc_plan_sim_trace_rays.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, vp, ip, vp, ip, vp, ip]
     _lib = L
     return L
 

@@ -4,6 +4,50 @@
  * list (it uses their names, and rtcdev's through the file's using-directive). */
 #pragma once
 
+/* A closest-hit query's result (a Closest's idx and dst: idx < sphereCount a sphere, else sphereCount + triangle; -1 a
+ * miss) as the four buffers' values at element o, each buffer nullable -- the one statement of the encoding described
+ * below, shared by rtc_first_hit and rtc_trace_rays (rtc_trace_rays.h).  P: the kernel's arguments, of which tris, mats,
+ * spheres and sphereCount are read (RenderParams, TraceRaysArgs); (pos, dir): the ray the query traced, for a sphere's
+ * normal.  (idx and dst are passed apart and in this order: rtc_first_hit then compiles to the code it had before the
+ * function was taken out of it, instruction for instruction -- tools/kernel_diff.py.) */
+template <bool SPHERES, typename PT>
+__device__ __forceinline__ void store_hit(const PT &P, V3 pos, V3 dir, const int idx, const float dst, size_t o,
+                                          int *__restrict__ prim, float *__restrict__ depth, float *__restrict__ normal,
+                                          float *__restrict__ albedo)
+{
+    int winner = -1;
+    V3 n{0.f, 0.f, 0.f}, color{0.f, 0.f, 0.f};
+    if (idx >= 0) {
+        if (SPHERES && idx < P.sphereCount) {
+            const DevSphere sp = P.spheres[idx];
+            const V3 hitPoint = add(pos, mul(dir, dst));            /* raytracing.c:181 */
+            n = normalized(sub(hitPoint, V3{sp.cx, sp.cy, sp.cz})); /* :182 */
+            color = V3{sp.r, sp.g, sp.b};
+            winner = -2 - idx;
+        } else {
+            winner = idx - (SPHERES ? P.sphereCount : 0);
+            const DevTri T = P.tris[winner];
+            const DevMat M = P.mats[winner];
+            n = V3{T.nx, T.ny, T.nz};
+            color = V3{M.r, M.g, M.b};
+        }
+    }
+    if (prim)
+        prim[o] = winner;
+    if (depth)
+        depth[o] = dst;
+    if (normal) {
+        normal[3 * o] = n.x;
+        normal[3 * o + 1] = n.y;
+        normal[3 * o + 2] = n.z;
+    }
+    if (albedo) {
+        albedo[3 * o] = color.x;
+        albedo[3 * o + 1] = color.y;
+        albedo[3 * o + 2] = color.z;
+    }
+}
+
 /* One lane per pixel, the one-lane-per-pixel kernel's geometry in raster order (block_xy with P.order null, pixel_ray,
  * wave_tile): a wave is an 8x8 tile, its candidate words (rtc_tile_cull; P.tileMask null: every record, closest_primary)
  * are wave-uniform and the records scalar loads.  The query is closest_hit's primary one -- spheres first, then the
@@ -38,36 +82,6 @@ __global__ __launch_bounds__(kBlock) void rtc_first_hit(RenderParams P, int *__r
         c = closest_hit<SPHERES>(P, P.origin, px.dir, true, tmask, nullptr);
     if (!px.valid)
         return;
-    int winner = -1;
-    V3 n{0.f, 0.f, 0.f}, color{0.f, 0.f, 0.f};
-    if (c.idx >= 0) {
-        if (SPHERES && c.idx < P.sphereCount) {
-            const DevSphere sp = P.spheres[c.idx];
-            const V3 hitPoint = add(P.origin, mul(px.dir, c.dst));       /* raytracing.c:181 */
-            n = normalized(sub(hitPoint, V3{sp.cx, sp.cy, sp.cz}));      /* :182 */
-            color = V3{sp.r, sp.g, sp.b};
-            winner = -2 - c.idx;
-        } else {
-            winner = c.idx - (SPHERES ? P.sphereCount : 0);
-            const DevTri T = P.tris[winner];
-            const DevMat M = P.mats[winner];
-            n = V3{T.nx, T.ny, T.nz};
-            color = V3{M.r, M.g, M.b};
-        }
-    }
-    const size_t o = (size_t)px.r * (size_t)P.width + (size_t)px.x;
-    if (prim)
-        prim[o] = winner;
-    if (depth)
-        depth[o] = c.dst;
-    if (normal) {
-        normal[3 * o] = n.x;
-        normal[3 * o + 1] = n.y;
-        normal[3 * o + 2] = n.z;
-    }
-    if (albedo) {
-        albedo[3 * o] = color.x;
-        albedo[3 * o + 1] = color.y;
-        albedo[3 * o + 2] = color.z;
-    }
+    store_hit<SPHERES>(P, P.origin, px.dir, c.idx, c.dst, (size_t)px.r * (size_t)P.width + (size_t)px.x, prim, depth,
+                       normal, albedo);
 }

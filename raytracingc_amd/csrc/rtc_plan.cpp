@@ -485,6 +485,30 @@ int update_footprint(const UpdatePlan &u, Footprint *out, int max)
     return 2;
 }
 
+void plan_trace_rays(const State &s, TracePlan &t)
+{
+    memset(&t, 0, sizeof t);
+    t.after = s; /* nothing the planner keeps changes */
+    t.gen = s.gen;
+    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKTraceRays};
+}
+
+int trace_footprint(const TracePlan &t, uint64_t rays, const uint64_t hit[4], Footprint *out, int max)
+{
+    int k = 0;
+    const auto row = [&](int res, int access, unsigned long long id) {
+        if (k < max)
+            out[k] = Footprint{res, access, id, 0, 1};
+        ++k;
+    };
+    row(kResSceneGen, kRead, (unsigned long long)t.gen);
+    row(kResRays, kRead, rays);
+    for (int b = 0; b < 4; ++b)
+        if (hit[b])
+            row(kResHit, kWrite, hit[b]);
+    return k;
+}
+
 } // namespace rtcplan
 
 /* ---- the CPU test hook (include/rtc.h rtc_plan_sim_*) ---------------------------------------------------------- */
@@ -638,6 +662,38 @@ extern "C" int rtc_plan_sim_update(RtcPlanSim *s, unsigned long long stream, int
         q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)u.writes, q[3] = q[4] = q[5] = 0;
     }
     return u.nOps | ((nf + 1) << 8);
+}
+
+extern "C" int rtc_plan_sim_trace_rays(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,
+                                       const unsigned long long hit[4], int flags, int *ops, int maxOps,
+                                       unsigned long long *fp, int maxFp)
+{
+    /* refused as rtc_trace_rays_async refuses it */
+    if (!s || !ops || !rays || !hit || !(hit[0] | hit[1] | hit[2] | hit[3]) || (flags & ~RTC_F_NO_CLUSTER_CULL))
+        return RTC_EINVAL;
+    (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
+    rtcplan::TracePlan t;
+    rtcplan::plan_trace_rays(s->st, t);
+    s->st = t.after;
+    const uint64_t ids[4] = {hit[0], hit[1], hit[2], hit[3]};
+    int nf = 0;
+    for (int i = 0; i < t.nOps && i < maxOps; ++i) {
+        const rtcplan::Op &o = t.ops[i];
+        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
+        rtcplan::Footprint f[6];
+        const int k = rtcplan::trace_footprint(t, rays, ids, f, 6);
+        for (int j = 0; j < k; ++j, ++nf)
+            if (fp && nf < maxFp) {
+                unsigned long long *q = fp + 6 * (size_t)nf;
+                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
+                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
+            }
+    }
+    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation read, -, -, -) */
+        unsigned long long *q = fp + 6 * (size_t)nf;
+        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)t.gen, q[3] = q[4] = q[5] = 0;
+    }
+    return t.nOps | ((nf + 1) << 8);
 }
 
 extern "C" int rtc_plan_sim_regions(const RtcPlanSim *s, unsigned long long *out, int maxRows)

@@ -61,8 +61,9 @@ enum Event : int {
 };
 enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce,
                     kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */,
-                    kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */ };
-static_assert(kKRefit == 9 && kKFirstHit == 10, "the kernels' numbers are the test hooks' encoding");
+                    kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */,
+                    kKTraceRays /* rtc_trace_rays_async's kernel (plan_trace_rays); never part of a launch */ };
+static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11, "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
     int kind;   /* OpKind */
@@ -226,7 +227,7 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 /* The memory one kernel of a plan touches, for the ordering test: resource kinds and byte ranges */
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
                  kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */,
-                 kResHit = 10 /* id: the caller's buffer */ };
+                 kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -251,5 +252,21 @@ struct UpdatePlan {
 void plan_update(const State &s, int fault, UpdatePlan &u);
 /* the refit kernel's footprint: the generation it writes and the one it may copy from */
 int update_footprint(const UpdatePlan &u, Footprint *out, int max);
+
+/* One rtc_trace_rays_async: one kernel on the caller's stream that reads the current generation of the
+ * scene records and the caller's rays and writes the caller's hit buffers.  It uses no scratch slot, primary record,
+ * counter set, stream or event of the scene's, so it waits for nothing and arms nothing: stream order alone places it
+ * after the update that wrote its generation and before the one that will rewrite it (an update writes the generation no
+ * launch binds, on the caller's stream).  `after` equals the state it was planned from. */
+struct TracePlan {
+    int gen; /* the generation the kernel reads */
+    int nOps;
+    Op ops[1];
+    State after;
+};
+void plan_trace_rays(const State &s, TracePlan &t);
+/* the kernel's footprint: the generation read, the rays read (id: the buffer), one write per hit buffer asked for
+ * (hit[k] == 0: not asked for), in that order */
+int trace_footprint(const TracePlan &t, uint64_t rays, const uint64_t hit[4], Footprint *out, int max);
 
 } // namespace rtcplan

@@ -99,6 +99,7 @@ extern "C" int rtc_device_count(int *count)
 #include "rtc_sky.h"
 #include "rtc_chain.h"
 #include "rtc_first_hit.h"
+#include "rtc_trace_rays.h"
 
 /* A kernel launch whose completion also records `stop` (null: a plain launch): the event is the dispatch's own
  * completion signal, so the stream gets no separate marker packet -- each marker on the launch stream cost ~5-7 us
@@ -610,6 +611,105 @@ extern "C" int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCame
     return render_rows(s, nullptr, cam, d, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr, out);
 }
 
+/* ---- caller-supplied rays ----------------------------------------------------------------------- */
+/* the refusals of rtc_trace_rays_async and rtc_trace_rays, before any device call and before `s` is read */
+static int check_trace_rays(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
+                            const void *const out[4], bool haveOut)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
+    if (!rays || !haveOut)
+        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
+    if (!out[0] && !out[1] && !out[2] && !out[3])
+        return rtc_fail(RTC_EINVAL, "%s: no buffer asked for (prim, depth, normal and albedo are all null)", who);
+    if (n > (size_t)0x7fffffff)
+        return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
+    if (flags & ~RTC_F_NO_CLUSTER_CULL)
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (a ray query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who,
+                        flags);
+    return 0;
+}
+
+extern "C" int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, int trianglesOnly, int flags,
+                                    const RtcHitBuffers *out, void *stream)
+{
+    const char *const who = "rtc_trace_rays_async";
+    const void *const bufs[4] = {out ? out->prim : nullptr, out ? out->depth : nullptr, out ? out->normal : nullptr,
+                                 out ? out->albedo : nullptr};
+    if (const int rc = check_trace_rays(who, s, dRays, n, flags, bufs, out != nullptr))
+        return rc;
+    if (n == 0)
+        return 0;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* the planner names the generation and the one operation (rtc_plan.h plan_trace_rays); the ordering state stays as it
+     * is (TracePlan::after == s->plan), and so do the hooks, the timing events and the chain report */
+    rtcplan::TracePlan tp;
+    rtcplan::plan_trace_rays(s->plan, tp);
+    const SceneRecords &g = s->gen[tp.gen];
+    TraceRaysArgs a{};
+    a.tris = g.tris, a.mats = g.mats, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters;
+    a.chunks = g.chunks;
+    a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
+    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
+    a.rays = (const float *)dRays, a.n = (unsigned)n;
+    a.prim = out->prim, a.depth = out->depth, a.normal = out->normal, a.albedo = out->albedo;
+    /* <SPHERES, CULL> */
+    static void (*const kTraceRays[2][2])(TraceRaysArgs) = {{rtc_trace_rays<false, false>, rtc_trace_rays<false, true>},
+                                                            {rtc_trace_rays<true, false>, rtc_trace_rays<true, true>}};
+    for (int i = 0; i < tp.nOps; ++i) {
+        const rtcplan::Op &op = tp.ops[i];
+        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKTraceRays || op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
+        hipLaunchKernelGGL(kTraceRays[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
+                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trianglesOnly, int flags, int *prim,
+                              float *depth, float *normal, float *albedo)
+{
+    const char *const who = "rtc_trace_rays";
+    void *const host[4] = {prim, depth, normal, albedo};
+    if (const int rc = check_trace_rays(who, s, rays, n, flags, host, true))
+        return rc;
+    if (n == 0)
+        return 0;
+    int devices = 0;
+    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
+        return rc;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* staged through device buffers on the null stream, like rtc_scene_update */
+    const size_t bytes[4] = {n * sizeof(int), n * sizeof(float), n * 3 * sizeof(float), n * 3 * sizeof(float)};
+    void *dRays = nullptr, *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipMalloc(&dRays, n * sizeof(Ray));
+    if (e == hipSuccess)
+        e = hipMemcpy(dRays, rays, n * sizeof(Ray), hipMemcpyHostToDevice);
+    for (int k = 0; k < 4; ++k)
+        if (e == hipSuccess && host[k])
+            e = hipMalloc(&dev[k], bytes[k]);
+    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    const RtcHitBuffers out{(int *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3]};
+    int rc = e == hipSuccess ? rtc_trace_rays_async(s, (const Ray *)dRays, n, trianglesOnly, flags, &out, nullptr)
+                             : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
+    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (int k = 0; k < 4; ++k)
+        if (rc == 0 && dev[k] && (e = hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (void *p : {dRays, dev[0], dev[1], dev[2], dev[3]})
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items)
 {
@@ -751,3 +851,8 @@ template __global__ void rtc_render_kernel<true, true, true>(RenderParams);
 /* the first-hit buffers */
 template __global__ void rtc_first_hit<false>(RenderParams, int *, float *, float *, float *);
 template __global__ void rtc_first_hit<true>(RenderParams, int *, float *, float *, float *);
+/* caller-supplied rays */
+template __global__ void rtc_trace_rays<false, true>(TraceRaysArgs);
+template __global__ void rtc_trace_rays<true, true>(TraceRaysArgs);
+template __global__ void rtc_trace_rays<false, false>(TraceRaysArgs);
+template __global__ void rtc_trace_rays<true, false>(TraceRaysArgs);
