@@ -76,7 +76,30 @@ struct ChainWaveLds {
 constexpr unsigned long long kNoHitKey = ((unsigned long long)0x497423F0u << 32) | 0xFFFFFFFFull; /* 999999.f */
 static_assert(kChunkClusters <= 32, "cluster masks are 32-bit");
 static_assert(kChainPairs >= 64 * kClusterSize, "one cluster's pairs of a full wave fit the list");
-static_assert(kChainPairs * sizeof(unsigned short) >= 3 * 64 * sizeof(float), "a window's staged samples fit the list");
+/* The in-kernel sums' staging (rtc_render_chain, flush()): component c of a window's staged sample i at
+ * stage[c * kStageRow + i] in the pair list's space; lane c < 3 then reads its row four samples at a time (ds_read_b128).
+ * The row length is padded: the generic loop reads one quad ahead (at most quad 16 = dwords 64..67 of a row), the rows
+ * start 16-byte aligned, and they start 4 banks apart -- ds_read_b128 banks by (dword address) mod 64, and lanes 0..2
+ * are in one of its 16-lane groups, so the three lanes' quads (same quad index, three rows) must not share a bank.
+ * The staging lanes write consecutive dwords of a row (ds_write_b32: 32 lanes per group, banks mod 32): no conflict. */
+constexpr int kStageRow = 68;
+constexpr bool stage_rows_disjoint(int row)
+{
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b) {
+            const int d = ((b - a) * row) % 64; /* row b's quad starts d banks after row a's; each covers 4 banks */
+            if (d < 4 || d > 60)
+                return false;
+        }
+    return true;
+}
+static_assert(kStageRow >= 64 + 4, "the quad read ahead of a full window stays inside the row");
+static_assert(kStageRow % 4 == 0 && offsetof(ChainWaveLds, pair) % 16 == 0 && alignof(ChainWaveLds) >= 16,
+              "the rows start 16-byte aligned (ds_read_b128)");
+static_assert(stage_rows_disjoint(kStageRow), "the three summing lanes' ds_read_b128 hit disjoint banks");
+constexpr int kStageLaneStride = 1; /* dwords between the entries two neighbouring staging lanes write */
+static_assert(kStageLaneStride % 2 == 1, "a 32-lane group's staging writes fall on 32 distinct banks");
+static_assert(kChainPairs * sizeof(unsigned short) >= 3 * kStageRow * sizeof(float), "a window's staged samples fit the list");
 /* rtc_render_chain's static LDS (powf tables, the waves' ChainWaveLds, the work counter) and the block budget
  * that keeps 4 blocks (16 waves) per CU */
 constexpr size_t kChainStaticLds = sizeof(PowTablesLds) +
@@ -903,23 +926,76 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
             int p = 0;
             SampleSlot *slot = P.sampleBuf + (size_t)it * (size_t)P.spp;
             /* in-kernel sums: the window's samples are staged in sample order in LDS -- the pair list's space, free
-             * until the next window's bounces; component c of staged sample i at stage[3 i + c] -- and lane c then adds
-             * them in order.  Interleaved, the three summing lanes read three consecutive dwords (three banks) and the
-             * staging lanes write at a stride of 3 dwords (a permutation of the 64 banks): no bank conflicts (round 4's
-             * stage[64 c + i] put the three readers on one bank: 6.3 M conflict cycles per 1080p launch) */
+             * until the next window's bounces; component c of staged sample i at stage[c kStageRow + i] (kStageRow, above:
+             * its padding and the banks) -- and lane c then adds its row in order, main.c:99's sequential f32 adds.  The
+             * row comes into registers four samples per ds_read_b128, ahead of the adds, so that the dependent adds issue
+             * back to back instead of each batch of eight waiting for its own LDS round trip (until round 14:
+             * stage[3 i + c], dword reads threaded between the 64 adds of a full window).  The last quad of a count that is no multiple of four is
+             * read whole and only its staged entries are added: the other dwords are whatever the pair list left there.
+             * Both syncs stay: the first orders the staging writes before the reads; the second the reads before the
+             * space's next writer, another lane -- the next window's pair build, or a staging run after a mid-window flush */
             float *const stage = (float *)W.pair;
             int staged = 0;
-            auto flush = [&]() {
+            /* full: the call may see a full window (the flush at the window's end; a flush mid-window follows a lane
+             * that was not staged, so fewer than 64 are) */
+            auto flush = [&](const bool full) {
+                DSECT_BEGIN(df0);
                 wave_lds_sync();
-                if (lane < 3) {
-                    const float *src = stage + lane;
-#pragma unroll 8
-                    for (int i = 0; i < staged; ++i)
-                        acc = acc + src[3 * i];
+                DSECT_END(df0, 25);
+                DSECT_BEGIN(df1);
+                if (full && staged == 64) { /* (uniform) every window of a frame of one-hit pixels: no loop */
+                    if (lane < 3) {
+                        const float4 *row = (const float4 *)(stage + lane * kStageRow);
+                        /* groups of kGroup quads, the next group requested before this one's adds: the kernels without
+                         * the GENERAL code hold the whole row (64 registers, all 16 reads ahead of the first add), the
+                         * GENERAL ones, which have no registers to spare, two groups of four quads at a time */
+                        constexpr int kGroup = GENERAL ? 4 : 16;
+                        float4 v[16];
+#pragma unroll
+                        for (int g = 0; g < kGroup; ++g)
+                            v[g] = row[g];
+#pragma unroll
+                        for (int g0 = 0; g0 < 16; g0 += kGroup) {
+#pragma unroll
+                            for (int g = g0 + kGroup; g < 16 && g < g0 + 2 * kGroup; ++g)
+                                v[g] = row[g];
+#pragma unroll
+                            for (int g = g0; g < g0 + kGroup; ++g) {
+                                acc = acc + v[g].x;
+                                acc = acc + v[g].y;
+                                acc = acc + v[g].z;
+                                acc = acc + v[g].w;
+                            }
+                        }
+                    }
+                } else if (lane < 3) {
+                    /* every other count: whole quads with the next one requested before this one's adds (the quad after
+                     * the last whole one lies inside the padded row), then the 1..3 staged entries of the last quad */
+                    const float4 *row = (const float4 *)(stage + lane * kStageRow);
+                    float4 v = row[0];
+                    int i = 0;
+                    for (; i + 4 <= staged; i += 4) {
+                        const float4 nx = row[(i >> 2) + 1];
+                        acc = acc + v.x;
+                        acc = acc + v.y;
+                        acc = acc + v.z;
+                        acc = acc + v.w;
+                        v = nx;
+                    }
+                    if (i < staged)
+                        acc = acc + v.x;
+                    if (i + 1 < staged)
+                        acc = acc + v.y;
+                    if (i + 2 < staged)
+                        acc = acc + v.z;
                 }
+                DSECT_END(df1, 26);
+                DSECT_BEGIN(df2);
                 wave_lds_sync();
+                DSECT_END(df2, 27);
                 staged = 0;
             };
+            DSECT_BEGIN(dwalk);
             while (k < P.spp && p < nAct) {
                 const unsigned long long win = (nAct >= 64 ? ~0ull : ((1ull << nAct) - 1ull)) & (~0ull << p);
                 const unsigned long long notOne = ~ones & win;
@@ -933,10 +1009,10 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
 #endif
                 } else {
                     if (lane >= p && lane < p + take) {
-                        const int i = 3 * (staged + lane - p);
+                        const int i = (staged + lane - p) * kStageLaneStride;
                         stage[i] = t.x;
-                        stage[i + 1] = t.y;
-                        stage[i + 2] = t.z;
+                        stage[kStageRow + i] = t.y;
+                        stage[2 * kStageRow + i] = t.z;
                     }
                     staged += take;
                 }
@@ -956,13 +1032,13 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                         slot[kk] = SampleSlot{qx, qy, qz};
                 } else if (m == 1) {
                     if (lane == q) {
-                        stage[3 * staged] = t.x;
-                        stage[3 * staged + 1] = t.y;
-                        stage[3 * staged + 2] = t.z;
+                        stage[staged] = t.x;
+                        stage[kStageRow + staged] = t.y;
+                        stage[2 * kStageRow + staged] = t.z;
                     }
                     ++staged;
                 } else { /* the staged samples first, then this one m times */
-                    flush();
+                    flush(false);
                     const float v = lane == 0 ? qx : (lane == 1 ? qy : qz);
                     for (int b = 0; b < m; ++b)
                         acc = acc + v;
@@ -973,8 +1049,9 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                     break;
                 p = q + hq;
             }
+            DSECT_END(dwalk, 24); /* 24 the walk and its staging; 25 sync, 26 reads and adds, 27 sync inside flush() */
             if (!deferred)
-                flush();
+                flush(true);
             jn += (unsigned)p;
 #ifdef RTC_DIAG
             {

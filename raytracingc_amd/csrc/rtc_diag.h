@@ -15,7 +15,7 @@ extern "C" int rtc_diag_set_buffer(void *dptr)
 }
 /* heavy-kernel section cycles (s_memtime deltas summed over waves): 0 primary trace, 1 cluster tests,
  * 2 general filter loop, 3 general exact loop, 4 lane reduction, 5 hit shading, 6 sky (miss), 7 loop total */
-constexpr int kDiagSects = 24;
+constexpr int kDiagSects = 28;
 __device__ unsigned long long g_rtc_sect[kDiagSects]; /* [8..12] window statistics (rtc_render_chain) */
 /* rtc_render_chain's diagnostics, written with plain stores to per-wave-slot / per-item addresses (no same-address global
  * atomics: thousands of them queued at a kernel's end held up other waves' memory operations behind them in the L2
@@ -82,7 +82,7 @@ extern "C" int rtc_diag_set_cull_buffer(void *dptr)
             r_[0] = (a), r_[1] = (b), r_[2] = (c), r_[3] = (geo), r_[4] = (pre), r_[5] = (loop), r_[6] = (cand); \
         }                                                                                                      \
     } while (0)
-__shared__ unsigned long long s_rtc_sect[4][kDiagSects]; /* [wave][section]: 0..7, 13..23 (rtc_render_chain) */
+__shared__ unsigned long long s_rtc_sect[4][kDiagSects]; /* [wave][section]: 0..7, 13..27 (rtc_render_chain) */
 #define DSECT_BEGIN(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 #define DSECT_END(v, k)                                                                                        \
     do {                                                                                                       \
@@ -103,7 +103,7 @@ __shared__ unsigned long long s_rtc_sect[4][kDiagSects]; /* [wave][section]: 0..
     } while (0)
 extern "C" int rtc_diag_sections(unsigned long long *out, int reset)
 {
-    /* out: kDiagSects (24) counters */
+    /* out: kDiagSects (28) counters */
     if (out) {
         HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rtc_sect), kDiagSects * sizeof(unsigned long long)));
         std::vector<unsigned long long> w((size_t)kWaveLog * kDiagSects);

@@ -18,12 +18,16 @@ os.environ["RTC_LIB_PATH"] = os.environ.get("RTC_DIAG_LIB") or os.path.join(REPO
 import raytracingc_amd as rt  # noqa: E402
 from conftest import load_tris  # noqa: E402
 
-NS = 24
+NS = 28
 TOP = {19: "prologue", 15: "item_setup", 0: "window_setup", 1: "primary_trace", 17: "bounce_trace", 16: "shading",
        20: "later_bounce_trace", 21: "later_shading", 7: "walk_and_sums", 18: "item_tail"}
 NESTED = {14: ("bounce_trace", "first_bounce_table"), 3: ("*bounce_trace", "cluster_cull"),
           4: ("*bounce_trace", "pair_build"), 5: ("*bounce_trace", "pair_passes"), 2: ("*shading", "hit"),
-          6: ("*shading", "environment")}
+          6: ("*shading", "environment"),
+          # the in-kernel sums inside walk_and_sums: the walk with its staging writes (a mid-window flush included), then
+          # the last flush's wait for the staging, its reads and adds, and the sync after them; the rest is the window's tail
+          24: ("walk_and_sums", "walk_and_staging"), 25: ("walk_and_sums", "sums_sync_before"),
+          26: ("walk_and_sums", "sums_reads_and_adds"), 27: ("walk_and_sums", "sums_sync_after")}
 scene_name = sys.argv[1] if len(sys.argv) > 1 else "ultracomplex"
 W, H, SPP = (int(v) for v in sys.argv[2:5]) if len(sys.argv) > 4 else (1920, 1080, 64)
 tris, _ = load_tris(scene_name)

@@ -100,7 +100,7 @@ for rep in range(2):
         tot = isec[rows].sum(axis=0)
         m = max(int(tot[MAIN].sum()), 1)
         return {COLS[c]: round(float(tot[c]) / m, 3) for c in range(16) if tot[c]}
-    allsec = np.zeros(24, np.uint64)
+    allsec = np.zeros(28, np.uint64)  # kDiagSects
     L.rtc_diag_sections(allsec.ctypes.data, 1)
     grid = nWaves // 4
     q = lambda v, p: round(float(np.percentile(v, p)), 2)  # noqa: E731

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 evidence of one workload (run on the GPU box): a kernel trace of the bench command and PMC passes, one
-# counter group per run, each under its own time limit, over tools/one_render.py <workload>; outputs under
+# counter group per run and no tracing beside the counters, each under its own time limit, over tools/one_render.py <workload>; outputs under
 # gpurun_out/prof_<workload>_<tag>/ (digest: tools/pmc_digest.py).  usage: tools/profile_workload.sh <workload> <tag>
 set -u
 export TMPDIR=/tmp
@@ -26,6 +26,6 @@ G3="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_AC
 g=0
 for grp in "$G1" "$G2" "$G3" "FETCH_SIZE" "WRITE_SIZE"; do
   g=$((g + 1))
-  step pmc_g$g 90 rocprofv3 --kernel-trace --pmc $grp -d "$OUT/pmc_g$g" -o p --output-format csv -- python3 "$R/tools/one_render.py" "$w" 2 || exit $?
+  step pmc_g$g 90 rocprofv3 --pmc $grp -d "$OUT/pmc_g$g" -o p --output-format csv -- python3 "$R/tools/one_render.py" "$w" 2 || exit $?
 done
 echo done
