@@ -94,6 +94,9 @@ typedef struct RtcRenderDesc {
                                       like RTC_F_NO_COOP.  Never more than 32 spheres, and not with RTC_F_NO_COOP,
                                       RTC_F_NO_REORDER, RTC_F_NO_TILE_CULL or RTC_F_DEBUG_BOUNCES.  Same frame bit for
                                       bit. */
+#define RTC_F_NO_DRAW_CACHE 0x4000 /* the launch neither reads nor fills the scene's draw cache (rtc_scene_set_draw_cache):
+                                      rtc_render_chain computes every hit draw as before the cache.  A/B timing and
+                                      tests.  Same frame bit for bit. */
 #define RTC_F_OVERLAP       0x800 /* frame pipelining (device-resident split only): the launch does not make
                                      `stream` wait for its sky pass, so the next launches on the same scene render
                                      (scratch in 8 slots) while this one's sky pass still runs.  A later overlapped
@@ -268,6 +271,27 @@ typedef struct RtcChainReport {
     int chainPrimF, wgsPerCu, chainDyn, clusterCount, chunkCount, launches;
 } RtcChainReport;
 int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *out);
+/* The draw cache (no reference counterpart; it never changes a frame).  A sample's m-th hit draws RandomDiretion's six
+ * values and the roulette's one from the pixel's seed x + y * width (main.c:95) advanced by 7 (j + m) draws: a function of
+ * the frame's width and the pixel alone, whatever the camera, scene, materials or environment.  The scene keeps, per pixel
+ * that has seen geometry, the 64 entries D_j = (RandomDiretion from the seed advanced 7 j draws, the roulette value that
+ * follows), j = 0..63, in a 1-KB block of device memory, filled once by the launch that first meets the pixel (the tile
+ * cull allocates, a fill kernel behind it computes) and read by rtc_render_chain's first window of every later launch in
+ * place of its Box-Muller.  Only the launches that run the chain kernel without its GENERAL code use it (in-kernel sums,
+ * single chunk, no counters, spheres, passes or hoisting); every sample still traces its rays and evaluates the
+ * environment.  Blocks are never evicted: when the pool is full, new pixels are computed as before.  A launch whose width
+ * or height differs from the cached frame's clears the cache behind a device synchronisation.
+ * rtc_scene_set_draw_cache: the pool's capacity in blocks (0 disables; < 0 the default: RTC_DRAW_CACHE_BLOCKS at upload,
+ * else 1 GiB of blocks, in either case at most the frame's pixel count); when anything is cached it synchronises the
+ * device and drops it.  (rtc_render and rtc_render_multi, whose scenes render one frame, run without the cache.)
+ * rtc_scene_draw_cache_reset: synchronises and clears.  rtc_scene_draw_cache_stats: synchronises; out = blocks in use,
+ * capacity (0 before the first cached launch), the last cached launch's fresh items, its uncached items.
+ * rtc_probe_draw_cache: synchronises; the 64 entries (256 floats) of the pixel with this seed into out and its block in
+ * *block, or *block = -1 when it has none. */
+int rtc_scene_set_draw_cache(RtcDeviceScene *s, long long blocks);
+int rtc_scene_draw_cache_reset(RtcDeviceScene *s);
+int rtc_scene_draw_cache_stats(const RtcDeviceScene *s, unsigned long long out[4]);
+int rtc_probe_draw_cache(const RtcDeviceScene *s, unsigned int seed, float *out, int *block);
 /* Sphere scenes (calculateRayCollision's sphere loop, raytracing.c:219-228).  A launch that renders spheres takes the split
  * launch -- the pixels whose primary ray hits nothing go to the sky pass, the others to rtc_render_chain, which tests the
  * spheres first and lets a triangle win only when strictly closer -- when all of these hold: at most 32 spheres; the
@@ -413,6 +437,10 @@ int rtc_plan_sim_launch(RtcPlanSim *sim, const RtcRenderDesc *d, unsigned long l
 /* The simulated scene's spheres (0 by default) and whether its upload gate would allow the split launch for them; a
  * launch with d->trianglesOnly renders none. */
 int rtc_plan_sim_set_spheres(RtcPlanSim *sim, int sphereCount, int gateAllows);
+/* The simulated scene's draw cache (off by default): on, the launches that would use it declare the slot table with its
+ * pool counter (footprint resource 12) and their slot's item-draw array (resource 13, id = the slot), and a launch that
+ * clears the cache or regrows the item-draw array reports it in the `scratch regrown` field (the device is synchronised). */
+int rtc_plan_sim_set_draw_cache(RtcPlanSim *sim, int on);
 /* Makes the next rtc_plan_sim_launch (only) a pass of rtc_render_samples_async: samples [first, first + count) of its
  * d->spp, the RNG-state buffer's identity (footprint resource 8).  That launch returns RTC_EINVAL where the entry point
  * would (a bad range, RTC_F_OVERLAP, no accumulator or state buffer). */

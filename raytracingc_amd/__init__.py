@@ -32,6 +32,7 @@ from ._abi import (  # noqa: F401
     RTC_F_OVERLAP,
     RTC_F_HOST_ROWS,
     RTC_F_SPLIT_SPHERES,
+    RTC_F_NO_DRAW_CACHE,
     RTC_F_NO_REORDER,
     RTC_F_NO_TILE_CULL,
     RTC_SEGMENT_COUNTERS,
@@ -158,13 +159,17 @@ class RenderConfig:
     # a launch that renders spheres takes the split launch (tile cull with sphere coverage, sky pass, rtc_render_chain with
     # spheres) whatever the scene's gate decided (DeviceScene.sphere_split; RTC_F_SPLIT_SPHERES; same frame)
     split_spheres: bool = False
+    # the launch may read and fill the scene's draw cache (DeviceScene.set_draw_cache); False: RTC_F_NO_DRAW_CACHE, every
+    # hit draw computed in the geometry kernel (A/B timing and tests; same frame)
+    draw_cache: bool = True
 
     def flags(self) -> int:
         return ((RTC_F_HOIST_PRIMARY if self.hoist else 0) | (RTC_F_DEBUG_BOUNCES if self.debug_bounces else 0)
                 | (0 if self.tile_cull else RTC_F_NO_TILE_CULL) | (0 if self.reorder else RTC_F_NO_REORDER)
                 | (0 if self.coop else RTC_F_NO_COOP) | (0 if self.cluster_cull else RTC_F_NO_CLUSTER_CULL)
                 | (RTC_F_CHAIN_INLINE if self.chain_inline else 0) | (RTC_F_OVERLAP if self.overlap else 0)
-                | (RTC_F_HOST_ROWS if self.host_rows else 0) | (RTC_F_SPLIT_SPHERES if self.split_spheres else 0))
+                | (RTC_F_HOST_ROWS if self.host_rows else 0) | (RTC_F_SPLIT_SPHERES if self.split_spheres else 0)
+                | (0 if self.draw_cache else RTC_F_NO_DRAW_CACHE))
 
     def desc(self) -> RtcRenderDesc:
         return RtcRenderDesc(self.width, self.height, self.spp, self.max_bounce, int(self.triangles_only),
@@ -435,6 +440,30 @@ class DeviceScene:
         out.update(chain_prim_f=bool(r.chainPrimF), wgs_per_cu=r.wgsPerCu, chain_dyn=r.chainDyn,
                    cluster_count=r.clusterCount, chunk_count=r.chunkCount, launches=r.launches)
         return out
+
+    def set_draw_cache(self, blocks: int = -1):
+        """The draw cache's capacity in 1-KB blocks, one per cached pixel (rtc_scene_set_draw_cache): 0 disables it, a
+        negative value restores the default.  Synchronises the device and drops what is cached."""
+        check(lib().rtc_scene_set_draw_cache(self._h, int(blocks)), "rtc_scene_set_draw_cache")
+
+    def draw_cache_reset(self):
+        """Forget every cached pixel (rtc_scene_draw_cache_reset; synchronises the device)."""
+        check(lib().rtc_scene_draw_cache_reset(self._h), "rtc_scene_draw_cache_reset")
+
+    def draw_cache_stats(self) -> dict:
+        """rtc_scene_draw_cache_stats (synchronises the device): blocks in use, capacity (0 before the first launch that
+        uses the cache), and the last such launch's fresh (newly cached) and uncached items."""
+        out = (C.c_ulonglong * 4)()
+        check(lib().rtc_scene_draw_cache_stats(self._h, out), "rtc_scene_draw_cache_stats")
+        return {"blocks": int(out[0]), "capacity": int(out[1]), "fresh": int(out[2]), "uncached": int(out[3])}
+
+    def draw_cache_block(self, seed: int):
+        """The cached block of the pixel with this seed (x + y * width), float32 [64, 4] -- entry j: RandomDiretion from
+        the seed advanced 7 j draws, then the roulette value -- or None when the pixel has none (rtc_probe_draw_cache)."""
+        out = np.zeros((64, 4), np.float32)
+        blk = C.c_int(-1)
+        check(lib().rtc_probe_draw_cache(self._h, int(seed), _ptr(out), C.byref(blk)), "rtc_probe_draw_cache")
+        return out if blk.value >= 0 else None
 
     @property
     def sphere_split(self) -> bool:

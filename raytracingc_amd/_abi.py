@@ -115,6 +115,7 @@ RTC_F_CHAIN_INLINE = 0x400
 RTC_F_OVERLAP = 0x800
 RTC_F_HOST_ROWS = 0x1000
 RTC_F_SPLIT_SPHERES = 0x2000  # sphere launches take the split launch whatever the scene's gate says (A/B, tests)
+RTC_F_NO_DRAW_CACHE = 0x4000  # the launch neither reads nor fills the scene's draw cache (A/B, tests)
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007
@@ -163,6 +164,8 @@ EXPORTS = [
     "rtc_scene_chain_report",
     "rtc_render_first_hit_async", "rtc_plan_sim_set_first_hit",
     "rtc_trace_rays_async", "rtc_trace_rays", "rtc_plan_sim_trace_rays",
+    "rtc_scene_set_draw_cache", "rtc_scene_draw_cache_reset", "rtc_scene_draw_cache_stats", "rtc_probe_draw_cache",
+    "rtc_plan_sim_set_draw_cache",
 ]
 
 _lib = None
@@ -278,6 +281,12 @@ def lib() -> C.CDLL:
         L.rtc_trace_rays_async.argtypes = [vp, vp, sz, ip, ip, C.POINTER(RtcHitBuffers), vp]
         L.rtc_trace_rays.argtypes = [vp, vp, sz, ip, ip, vp, vp, vp, vp]
         L.rtc_plan_sim_trace_rays.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, vp, ip, vp, ip, vp, ip]
+    if hasattr(L, "rtc_scene_set_draw_cache"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_set_draw_cache.argtypes = [vp, C.c_longlong]
+        L.rtc_scene_draw_cache_reset.argtypes = [vp]
+        L.rtc_scene_draw_cache_stats.argtypes = [vp, vp]
+        L.rtc_probe_draw_cache.argtypes = [vp, C.c_uint, vp, C.POINTER(C.c_int)]
+        L.rtc_plan_sim_set_draw_cache.argtypes = [vp, ip]
     _lib = L
     return L
 

@@ -574,7 +574,13 @@ __device__ __forceinline__ ChainStage chain_stage(const RenderParams &P, unsigne
  * and an item that sums in-kernel starts from the stored accumulator (a deferred item's sum: rtc_accumulate_samples_resume).
  * At the item's end one lane stores the state 7 jn draws on: jn is the chain's position after the pass's last sample, the
  * hits so far (a primary miss or maxBounce == 0 leaves jn = 0, the state where it was). */
-template <bool MULTI, bool COUNT, bool HITS, bool GENERAL, bool SPHERES = false, bool RESUME = false>
+/* DRAWS (the two kernels without the GENERAL code only; the draw cache, rtc_params.h DrawCache): an item's block number comes
+ * with its record through the one-item-ahead prefetch (P.itemDraw, lanes 4..7 of the record load).  For an item with a block,
+ * lane l requests entry l of the block (one global_load_dwordx4) at the item's start, as soon as the block is known, and the
+ * primary hit of the item's first window (jn == 0) takes that value -- the same function of (seed, l) that it would compute
+ * -- in place of Box-Muller, and enters it in W.draw as before.  Windows with jn > 0, lanes past the window's active ones
+ * and items without a block compute, on wave-uniform branches.  (The seed is the pixel index there: no RESUME.) */
+template <bool MULTI, bool COUNT, bool HITS, bool GENERAL, bool SPHERES = false, bool RESUME = false, bool DRAWS = false>
 __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC_CHAIN_WAVES))) void rtc_render_chain(
     RenderParams P)
 {
@@ -665,7 +671,14 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
         const int base = l ? __builtin_amdgcn_readlane(incl, l - 1) : 0;
         return (size_t)l * KARG(geoCap) + (size_t)(it2 - base);
     };
+    static_assert(!DRAWS || (!GENERAL && !RESUME && !SPHERES && !MULTI && !COUNT), "the draw cache: the kernels without GENERAL");
     const auto record_dwords = [&](int it2) -> unsigned {
+        if constexpr (DRAWS) { /* lanes 4..7 of every eight: the item's block + 1 (P.itemDraw), by the same load */
+            const size_t e = entry_of(it2);
+            const unsigned *const rec = KARG(geoList) + e * (size_t)kItemRecDwords + (size_t)(lane & (kItemRecDwords - 1));
+            const unsigned *const blk = KARG(itemDraw) + e;
+            return gload((lane & kItemRecDwords) ? blk : rec, 0);
+        }
         return gload(KARG(geoList), entry_of(it2) * (size_t)kItemRecDwords + (size_t)(lane & (kItemRecDwords - 1)));
     };
     /* the tile of a record (its dword 0, item_record) */
@@ -706,6 +719,15 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                                       (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 1) << 32;
         const unsigned long long m1 = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 2) |
                                       (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)vm, 3) << 32;
+        /* DRAWS: the item's cached draws, entry `lane` of its block, requested here and consumed at the primary hit of the
+         * item's first window (four registers live across the primary trace, which is scalar work) */
+        float4 cachedDraw = make_float4(0.f, 0.f, 0.f, 0.f);
+        unsigned drawBlock = 0;
+        if constexpr (DRAWS) {
+            drawBlock = (unsigned)__builtin_amdgcn_readlane((int)vc, kItemRecDwords);
+            if (drawBlock) /* (uniform) */
+                cachedDraw = gload4(KARG(drawPool), (size_t)(drawBlock - 1u) * kDrawEntries + (size_t)lane);
+        }
         /* the next item: its number (the LDS counter read at this item's previous start), its entry, and the counter for
          * the one after */
         const int itNext = __builtin_amdgcn_readfirstlane(nextIt);
@@ -882,9 +904,13 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(RTC
                          * reads entry lane + iter, or computes it when that is past the window's active lanes */
                         float4 D;
                         if (first || lane + iter >= nAct) {
-                            unsigned s = first ? rng : rng * J.a + J.c;
-                            const V3 rd = random_direction(s);
-                            D = make_float4(rd.x, rd.y, rd.z, random_value(s));
+                            if (DRAWS && first && drawBlock != 0u && jn == 0u) { /* (uniform) the cached entry `lane` */
+                                D = cachedDraw;
+                            } else {
+                                unsigned s = first ? rng : rng * J.a + J.c;
+                                const V3 rd = random_direction(s);
+                                D = make_float4(rd.x, rd.y, rd.z, random_value(s));
+                            }
                             if (first)
                                 W.draw[lane] = D; /* read in later iterations, after chain_trace_pairs' LDS syncs */
                         } else {

@@ -64,9 +64,15 @@ __global__ __launch_bounds__(64) void rtc_super_cull(RenderParams P, unsigned lo
  * workgroup with a sphere pixel; the tile's triangle mask words are the triangle-only launch's.  A template, not a
  * uniform branch: rtc_tile_cull (without spheres) is the kernel every other launch ran before, instruction for
  * instruction. */
-template <bool SPH>
+/* DRAWS (the draw cache, rtc_params.h DrawCache): the lane that appends a pixel's item record looks up the pixel's block
+ * in the slot table (by its seed x + y * width, frame coordinates); a pixel without one takes a block while the pool has
+ * room -- one atomic per tile with such pixels -- and enters it in the table with its seed in blockSeed, for the fill kernel
+ * behind this one; the item's block + 1 (0: none, the geometry kernel computes its draws) goes to itemDraw beside the
+ * record.  A template like SPH: the other launches' kernels stay what they were. */
+template <bool SPH, bool DRAWS = false>
 __device__ __forceinline__ void tile_cull_body(const RenderParams &P, unsigned long long *__restrict__ mask,
-                                               unsigned *__restrict__ weight, unsigned long long *__restrict__ pixMask)
+                                               unsigned *__restrict__ weight, unsigned long long *__restrict__ pixMask,
+                                               const DrawCache &C = DrawCache{})
 {
     const bool split = P.geoList != nullptr; /* (uniform) */
     if (KARG(cullPrio)) /* (RenderParams::cullPrio) */
@@ -182,6 +188,31 @@ __device__ __forceinline__ void tile_cull_body(const RenderParams &P, unsigned l
     if (lane == 0)
         pixMask[tile] = b;
     if (P.geoList && b) {
+        unsigned blk = 0; /* DRAWS: this lane's pixel's block + 1 */
+        if constexpr (DRAWS) {
+            const bool geo = (b >> lane) & 1ull;
+            const unsigned seed = (unsigned)(px.x + px.y * P.width); /* main.c:95 */
+            const bool inTable = geo && seed < C.tablePixels;
+            if (inTable)
+                blk = C.table[seed];
+            const unsigned long long want = __ballot(inTable && blk == 0u);
+            if (want) { /* (uniform) pixels new to the cache: nothing of this in the steady state */
+                const unsigned n = (unsigned)__popcll(want);
+                unsigned base = C.capacity;
+                if (lane == 0 && __atomic_load_n(&C.ctr[kDcTaken], __ATOMIC_RELAXED) < C.capacity)
+                    base = atomicAdd(&C.ctr[kDcTaken], n);
+                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                const unsigned k = base + (unsigned)__popcll(want & ((1ull << lane) - 1ull));
+                if (((want >> lane) & 1ull) && k < C.capacity) { /* granted: the table entry, the fill's input */
+                    blk = k + 1u;
+                    C.table[seed] = blk;
+                    C.blockSeed[k] = seed;
+                }
+            }
+            const unsigned long long none = __ballot(geo && blk == 0u);
+            if (none && lane == 0)
+                atomicAdd(&C.ctr[kDcUncachedAcc], (unsigned)__popcll(none));
+        }
         /* this tile's geometry pixels, appended to sub-list tile % kGeoLists (rtc_render_chain's work) */
         const auto append = [&](unsigned long long gb, int l) {
             int base = 0;
@@ -193,6 +224,8 @@ __device__ __forceinline__ void tile_cull_body(const RenderParams &P, unsigned l
             if (((gb >> lane) & 1ull) && base + __popcll(gb) <= P.geoCap) {
                 const int pos = base + __popcll(gb & ((1ull << lane) - 1ull));
                 ((uint4 *)P.geoList)[(size_t)l * P.geoCap + pos] = item_record(P, px, tile, lane);
+                if constexpr (DRAWS)
+                    C.itemDraw[(size_t)l * P.geoCap + pos] = blk;
                 if (P.pixItem) /* the pixel's entry: pos of sub-list l (the sky pass turns it into its item) */
                     P.pixItem[(size_t)tile * 64 + lane] = (unsigned)(pos * kGeoLists + l);
             }
@@ -227,6 +260,42 @@ __global__ __launch_bounds__(kBlock) void rtc_tile_cull_sph(RenderParams P, unsi
                                                            unsigned long long *__restrict__ pixMask)
 {
     tile_cull_body<SPH>(P, mask, weight, pixMask);
+}
+
+/* The tile cull of a launch that uses the draw cache (tile_cull_body<.., DRAWS>), and the fill kernel the executor issues
+ * behind it under the same planned operation (its completion is the operation's event).  Templates for the same reason as
+ * rtc_tile_cull_sph: their code is emitted where the instantiation list names them. */
+template <bool DRAWS>
+__global__ __launch_bounds__(kBlock) void rtc_tile_cull_draws(RenderParams P, unsigned long long *__restrict__ mask,
+                                                             unsigned *__restrict__ weight,
+                                                             unsigned long long *__restrict__ pixMask, DrawCache C)
+{
+    tile_cull_body<false, DRAWS>(P, mask, weight, pixMask, C);
+}
+/* The blocks the cull before it handed out, [fill mark, taken): a wave per block, lane j computes entry j -- the seed
+ * advanced by 7 j draws, RandomDiretion and the roulette value, by the geometry kernel's own functions (random_direction
+ * with its exact fallback, random_value) -- all 64 entries whatever the launch's spp.  Dense, full-lane, independent work.
+ * In the steady state nothing is fresh: every workgroup reads the two counters and ends.  Workgroup 0 moves the fill mark
+ * (into the other parity's word, which no workgroup of this launch reads) and publishes the launch's statistics. */
+constexpr int kFillBlocks = 512; /* workgroups of 4 waves */
+template <bool DRAWS>
+__global__ __launch_bounds__(256) void rtc_fill_draws(DrawCache C)
+{
+    const unsigned hi = min(C.ctr[kDcTaken], C.capacity);
+    const unsigned lo = min(C.ctr[C.parity ? kDcFilled1 : kDcFilled0], hi);
+    const int lane = threadIdx.x & 63;
+    const RngJump laneJump = rng_jump_by(7u * (unsigned)lane);
+    for (unsigned k = lo + blockIdx.x * 4u + (threadIdx.x >> 6); k < hi; k += gridDim.x * 4u) {
+        unsigned s = C.blockSeed[k] * laneJump.a + laneJump.c;
+        const V3 rd = random_direction(s);
+        C.pool[(size_t)k * kDrawEntries + lane] = make_float4(rd.x, rd.y, rd.z, random_value(s));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        C.ctr[C.parity ? kDcFilled0 : kDcFilled1] = hi;
+        C.ctr[kDcFresh] = hi - lo;
+        C.ctr[kDcUncached] = C.ctr[kDcUncachedAcc];
+        C.ctr[kDcUncachedAcc] = 0u;
+    }
 }
 
 /* Launch order of the render kernel's workgroups: a counting sort of the weights, heaviest bucket first

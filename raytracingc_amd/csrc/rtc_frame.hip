@@ -172,6 +172,7 @@ extern "C" int rtc_render(const Triangle *tris, int triCount, const Sphere *sphe
     RtcDeviceScene *s = nullptr;
     if (int rc = rtc_scene_upload(tris, triCount, spheres, sphereCount, device, &s))
         return rc;
+    (void)rtc_scene_set_draw_cache(s, 0); /* a scene that renders one frame: nothing would read a draw cache again */
     struct SceneGuard {
         RtcDeviceScene *s;
         ~SceneGuard() { rtc_scene_release(s); }
@@ -348,6 +349,7 @@ extern "C" int rtc_render_multi(const Triangle *tris, int triCount, const Sphere
         p.rows = rtc_rows_selected(&dg_desc);
         if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, shareAll, &p.s))
             return rc;
+        (void)rtc_scene_set_draw_cache(p.s, 0); /* a scene that renders one frame: nothing would read a draw cache again */
         HIP_TRY(hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking));
         HIP_TRY(p.col.alloc(partPx * 3, g));
         HIP_TRY(hipMemset(p.col.p, 0, partPx * 3));
@@ -500,6 +502,7 @@ int rtc_render_multi_host_rows(const Triangle *tris, int triCount, const Sphere 
         p.rows = rtc_rows_selected(&dg_desc);
         if (int rc = rtc_scene_upload_with_share(tris, triCount, spheres, sphereCount, g, share, shareAll, &p.s))
             return rc;
+        (void)rtc_scene_set_draw_cache(p.s, 0); /* a scene that renders one frame: nothing would read a draw cache again */
         HIP_TRY(hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking));
         HIP_TRY(p.col.alloc(partPx * 3 + 16, g));
         if (outAccum)

@@ -249,6 +249,17 @@ static_assert(kGeoSetInts >= kGeoLists * kGeoCountStride, "a counter set holds e
 static_assert(kSkySlots == rtcplan::kSlots && kGeoRing == rtcplan::kGeoRing && kGeoLists == rtcplan::kGeoLists &&
                   kGeoCountStride == rtcplan::kGeoCountStride && kItemRecDwords * 4 == rtcplan::kItemRecordBytes,
               "the planner's slot and counter-set layout is the device's");
+/* The draw cache's blocks and counter words (rtc_params.h DrawCache) */
+constexpr int kDrawEntries = 64; /* entries (float4) per block: one window's lanes */
+constexpr size_t kDrawBlockBytes = kDrawEntries * 16;
+enum DrawCtr : int {
+    kDcTaken = 0,    /* blocks handed out (may pass the capacity by requests that were not granted: readers clamp) */
+    kDcFilled0 = 1,  /* the fill mark, alternating between two words by the fill's parity: a fill reads its own ... */
+    kDcFilled1 = 2,  /* ... and writes the next fill's, so no workgroup reads the word another one writes */
+    kDcUncachedAcc = 3, /* this launch's items without a block so far (the fill moves it to kDcUncached and zeroes it) */
+    kDcFresh = 4, kDcUncached = 5, /* the last launch's fresh and uncached items (rtc_scene_draw_cache_stats) */
+    kDcWords = 8
+};
 /* One generation of the scene records: everything a launch reads of the scene's geometry.  A scene keeps two
  * (DESIGN §3.9): launches read the current one, rtc_scene_update_async writes the other and makes it current. */
 struct SceneRecords {
@@ -316,7 +327,24 @@ struct RtcDeviceScene {
     bool timing; /* record them (rtc_scene_set_timing; off by default: each record costs the launch a few us) */
     bool timed;  /* the last launch was a split launch that recorded them */
     RtcChainReport chainReport; /* what the last geometry-kernel launch chose (run_chain; rtc_scene_chain_report) */
+    /* The draw cache (rtc_params.h DrawCache), allocated at the first launch that uses it and freed with the
+     * scene.  The pool's blocks are append-only -- written once by the fill behind the cull that allocated them, before
+     * any geometry kernel that can name them; never touched again -- which is why launches in flight may read them while
+     * a later launch's cull and fill run.  Cleared (table, counters) behind a device synchronisation when the frame size
+     * changes (plan.drawWidth x plan.drawHeight: what the table is built for). */
+    struct Draws {
+        long long blocks;        /* the capacity asked for (rtc_scene_set_draw_cache; < 0: the default; 0: off) */
+        unsigned *table;         /* tablePixels entries */
+        size_t tablePixels;
+        unsigned *ctr;           /* DrawCtr words */
+        unsigned *blockSeed;     /* capacity entries */
+        void *pool;              /* capacity blocks of 1 KB */
+        size_t capacity;         /* blocks allocated (0: not yet) */
+        unsigned char *itemDraw; /* kSkySlots arrays (plan.itemDrawCap bytes) */
+        int parity;              /* the next fill's (DrawCtr kDcFilled0 / 1) */
+    } draws;
 };
+constexpr long long kDrawCacheDefaultBytes = 1ll << 30; /* of 1-KB blocks, at most the frame's pixel count */
 
 /* A split launch's geometry-pixel lists once its culls have run, for rtc_probe_item_records: the launch's preparation,
  * superblock and tile culls on the null stream and none of its render kernels (rtc_render.hip); device pointers into the
@@ -339,6 +367,12 @@ struct RtcCullItems {
 };
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items);
+/* The draw cache's memory for a launch that uses it (rtc_scene.hip; the scene's device is current): the first such launch
+ * allocates; `reset` (another frame size, or none yet) clears the table and the counters and `growBytes` > 0 regrows the
+ * slots' item-draw arrays to that size, each behind a device synchronisation -- no launch in flight reads what goes. */
+int rtc_draws_prepare(RtcDeviceScene *s, int width, int height, bool reset, size_t growBytes);
+/* everything of it freed (the caller has synchronised); the scene's capacity setting stays */
+void rtc_draws_free(RtcDeviceScene *s);
 
 /* True when the bounce ray (pos, dir) provably cannot hit any triangle of cluster K (see DevCluster): the
  * half-line's distance to the ball centre exceeds T >= r + eps.  rho = |dir|_1 >= |dir| bounds the eps terms;

@@ -60,8 +60,18 @@ struct RenderParams {
         unsigned *__restrict__ geoColor;
         unsigned *__restrict__ rngState;
     };
-    SampleSlot *__restrict__ sampleBuf; /* rtc_render_chain, deferred accumulation: [item][spp] radiance * (1/spp) */
-    int *__restrict__ itemPix;      /* [item] the pixel's offset in the launch's Color rows */
+    /* The draw cache's two pointers for the geometry kernel (the DRAWS instantiations) share the deferred samples' places
+     * -- a launch that uses the cache sums in-kernel (sampleCap == 0: no kernel of it reads sampleBuf or itemPix), and the
+     * DRAWS kernels have no deferred path -- so that the struct keeps its size and layout, as with rngState.  drawPool: the
+     * pool's blocks (float4[64] each); itemDraw: per entry of the launch's lists, 0 or the item's block + 1. */
+    union {
+        SampleSlot *__restrict__ sampleBuf; /* rtc_render_chain, deferred accumulation: [item][spp] radiance * (1/spp) */
+        const float4 *__restrict__ drawPool;
+    };
+    union {
+        int *__restrict__ itemPix;      /* [item] the pixel's offset in the launch's Color rows */
+        const unsigned *__restrict__ itemDraw;
+    };
     int sampleCap;                  /* items with a slot in sampleBuf; items beyond it accumulate in-kernel */
     int chainPrimF;                 /* rtc_render_chain stages DevPrimF[triPadded] in LDS */
     unsigned char *__restrict__ colors;
@@ -116,6 +126,13 @@ template <typename T> __device__ __forceinline__ unsigned gload(const T *p, size
     static_assert(sizeof(T) == 4, "dwords");
     return ((const __attribute__((address_space(1))) unsigned *)p)[i];
 }
+/* 16 bytes likewise (global_load_dwordx4) */
+__device__ __forceinline__ float4 gload4(const float4 *p, size_t i)
+{
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    const v4 v = ((const __attribute__((address_space(1))) v4 *)p)[i];
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 template <typename T> __device__ __forceinline__ T karg_at(size_t off)
 {
     const __attribute__((address_space(4))) char *base =
@@ -146,6 +163,25 @@ static_assert(offsetof(RenderParams, tileMask) == 80 && offsetof(RenderParams, s
               "RenderParams keeps the layout the kernels of ordinary launches were compiled against");
 
 constexpr int kTileW = 16, kTileH = 16, kBlock = 256;
+
+/* ---- the draw cache ------------------------------------------------------------------------------------
+ * Per pixel that has seen geometry, the 64 hit draws D_j = (RandomDiretion from the seed advanced 7 j draws, the roulette
+ * value that follows): what rtc_render_chain's first window enters in ChainWaveLds::draw, a function of the seed
+ * x + y * width alone.  The argument of the caching tile cull and of the fill kernel behind it (rtc_cull.h).
+ * The blocks are APPEND-ONLY: a block is written once, by the fill of the launch whose cull allocated it, before any
+ * geometry kernel that can name it starts (the cull operation's completion event is the fill's); later culls and fills
+ * never touch an allocated block or a non-zero table entry.  So a geometry kernel may read blocks while a later launch's
+ * cull and fill run. */
+/* (kDrawEntries and the counter words, DrawCtr: rtc_layout.h, shared with the host code that allocates and reads them) */
+struct DrawCache {
+    unsigned *__restrict__ table;     /* [tablePixels] by seed: 0 none, k + 1 block k */
+    unsigned *__restrict__ ctr;       /* DrawCtr */
+    unsigned *__restrict__ blockSeed; /* [capacity] block k's seed (the fill's input) */
+    float4 *__restrict__ pool;        /* [capacity][kDrawEntries] */
+    unsigned *__restrict__ itemDraw;  /* the launch slot's: per entry of the lists, 0 or block + 1 */
+    unsigned capacity, tablePixels;
+    int parity;
+};
 
 
 /* The pixel a lane renders and its primary ray (rowThread, main.c:88-94).  A 256-thread workgroup covers

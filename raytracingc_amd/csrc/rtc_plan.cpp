@@ -91,7 +91,13 @@ Request make_request(const RtcRenderDesc &d, int rows, const SceneShape &sc, uin
                          (d.flags & RTC_F_HOIST_PRIMARY) ? 1 : 0, d.rowBand > 1 ? __builtin_ctz((unsigned)d.rowBand) : 0};
     memcpy(r.key.dims, dims, sizeof dims);
     memcpy(r.origin, cam, sizeof r.origin);
+    r.height = d.height;
     return r;
+}
+
+void set_draw_cache(Request &r, int eligible)
+{
+    r.drawCache = eligible & 3;
 }
 
 void set_sample_range(Request &r, int first, int count, uint64_t rngState)
@@ -234,6 +240,22 @@ void plan_launch(const State &s, const Request &r, Plan &p)
                 n.samplesCap = p.samplesNeed;
             p.sampleCap = (int)cap;
         }
+        /* the draw cache: the launches whose geometry kernel has no GENERAL code (rtc_render.hip chain_flags: in-kernel
+         * sums, no hoisting, counters, spheres or pass; the scene's part is Request::drawCache), unless the launch opts out.
+         * The slot table is built for one frame size: another one clears it; the slots' item-draw arrays (one u32 per entry
+         * of the lists) grow like the scratch, slot h at h x the allocation's slot size */
+        p.draws = ((r.drawCache >> (p.smallShare ? 1 : 0)) & 1) && r.spp > 0 && p.sampleCap == 0 && !r.segments &&
+                  !r.resume && r.sphereCount == 0 && !(r.flags & (RTC_F_HOIST_PRIMARY | RTC_F_NO_DRAW_CACHE));
+        if (p.draws) {
+            p.drawReset = s.drawWidth != r.width || s.drawHeight != r.height;
+            n.drawWidth = r.width, n.drawHeight = r.height;
+            const size_t slotItemDraw = align_up((size_t)kGeoLists * p.geoCap * 4, 256);
+            p.itemDrawNeed = kSlots * slotItemDraw;
+            p.itemDrawGrow = p.itemDrawNeed > s.itemDrawCap;
+            if (p.itemDrawGrow)
+                n.itemDrawCap = p.itemDrawNeed;
+            p.itemDrawOffset = (size_t)p.half * (n.itemDrawCap / kSlots);
+        }
     }
     /* what the launch binds: the executor hands its kernels these buffers and no other, and only these have footprints */
     const auto bind = [&p](bool on, std::initializer_list<int> bufs) { for (int b : bufs) p.bound |= (unsigned)on << b; };
@@ -249,6 +271,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     bind(r.key.accum != 0, {kBufAccum});
     bind(r.segments, {kBufSegSlots, kBufCallerSegments});
     bind(r.resume, {kBufRngState});
+    bind(p.draws, {kBufDrawTable, kBufItemDraw});
 
     if (p.cs != kStCaller) {
         /* the cull stream runs this launch's first kernels: after everything the caller enqueued before the launch and
@@ -419,6 +442,9 @@ const Touch kTouches[] = {
      * records, the scene records, and the caller's buffers */
     {kKFirstHit, kBufMask, kRead, kAlways},        {kKFirstHit, kBufPrim, kRead, kAlways},
     {kKFirstHit, kBufSceneGen, kRead, kAlways},    {kKFirstHit, kBufHit, kWrite, kAlways},
+    /* the draw cache (rtc_plan.h Buf: the pool's blocks are append-only and in no row) */
+    {kKTileCull, kBufDrawTable, kWrite, kAlways},  {kKTileCull, kBufItemDraw, kWrite, kAlways},
+    {kKChain, kBufItemDraw, kRead, kAlways},
 };
 } // namespace
 
@@ -428,7 +454,8 @@ int kernel_footprint(const Plan &p, const Request &r, int kernel, Footprint *out
     const struct { int res; unsigned long long id; } outside[kBufs - kScratchRegions] = {
         {kResPrim, (unsigned long long)p.half}, {kResGeoSet, p.geoSet}, {kResGeoSet, p.geoSetNext}, {kResSamples, 0},
         {kResSegSlots, 0}, {kResColors, r.key.colors}, {kResAccum, r.key.accum}, {kResCallerSegments, 0},
-        {kResRngState, r.rngState}, {kResSceneGen, (unsigned long long)p.gen}, {kResHit, 0}};
+        {kResRngState, r.rngState}, {kResSceneGen, (unsigned long long)p.gen}, {kResHit, 0},
+        {kResDrawTable, 0}, {kResItemDraw, (unsigned long long)p.half}};
     int k = 0;
     for (const Touch &t : kTouches) {
         const bool when = t.when == kAlways || (t.when == kIfResumeRead ? p.resumeRead
@@ -523,6 +550,7 @@ struct RtcPlanSim {
     int updateFault; /* rtc_plan_sim_set_update_fault */
     bool hitNext;    /* rtc_plan_sim_set_first_hit: the next launch is a first-hit launch */
     uint64_t hit[4];
+    bool drawCache;  /* rtc_plan_sim_set_draw_cache: the scene has a draw cache and may use it in every launch shape */
 };
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
@@ -544,6 +572,14 @@ extern "C" int rtc_plan_sim_set_spheres(RtcPlanSim *s, int sphereCount, int gate
         return RTC_EINVAL;
     s->shape.sphereCount = sphereCount;
     s->shape.splitGate = gateAllows != 0;
+    return 0;
+}
+
+extern "C" int rtc_plan_sim_set_draw_cache(RtcPlanSim *s, int on)
+{
+    if (!s)
+        return RTC_EINVAL;
+    s->drawCache = on != 0;
     return 0;
 }
 
@@ -596,6 +632,8 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
             return RTC_EINVAL;
         rtcplan::set_sample_range(r, s->first, s->count, s->rngBuffer);
     }
+    if (s->drawCache)
+        rtcplan::set_draw_cache(r, 3);
     rtcplan::Plan &p = s->last;
     rtcplan::plan_launch(s->st, r, p);
     s->st = p.after;
@@ -616,10 +654,12 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
                 q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
             }
     }
-    /* the scratch regrowth (hipFree + hipMalloc: the device is synchronised first) and the plan's shape, after the ops */
+    /* the scratch regrowth (hipFree + hipMalloc: the device is synchronised first; so it is before the draw cache is
+     * cleared or its item-draw arrays regrown) and the plan's shape, after the ops */
     if (fp && nf < maxFp) {
         unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = p.scratchGrow || p.samplesGrow, q[2] = (unsigned long long)p.half, q[3] = p.chainOnCs,
+        q[0] = ~0ull, q[1] = p.scratchGrow || p.samplesGrow || p.drawReset || p.itemDrawGrow,
+        q[2] = (unsigned long long)p.half, q[3] = p.chainOnCs,
         q[4] = p.overlap, q[5] = p.slotOffset;
     }
     return p.nOps | ((nf + 1) << 8);

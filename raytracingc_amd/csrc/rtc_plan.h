@@ -105,6 +105,10 @@ struct State {
      * update follows -- the scene serves one stream at a time, and a caller that changes streams orders them (rtc.h). */
     int gen;
     unsigned char slotGens[kSlots];
+    /* the draw cache: the frame size its slot table is built for (0 x 0: none yet) and the bytes allocated
+     * for the slots' item-draw arrays */
+    int drawWidth, drawHeight;
+    size_t itemDrawCap;
 };
 void init(State &s);
 
@@ -131,6 +135,11 @@ struct Request {
      * buffers, 0 where one is not asked for */
     bool firstHit;
     uint64_t hit[4];
+    /* the scene's draw cache (set_draw_cache; 0: off or the scene cannot use it): bit 0, whole frames would run the chain
+     * kernel without its GENERAL code as far as the scene decides it (one chunk, the primary filter records staged at the
+     * whole frames' workgroups per CU); bit 1, small shares would.  The launch's own conditions are plan_launch's. */
+    int drawCache;
+    int height; /* the frame's (the slot table is indexed by x + y * width over the whole frame) */
 };
 
 /* the scene's shape as the planner needs it (RtcDeviceScene; rtc_plan_sim_create / _set_spheres) */
@@ -158,6 +167,9 @@ void set_sample_range(Request &r, int first, int count, uint64_t rngState);
  * launch still in flight in slot 0 and for no other; it records neither of the caller's two hooks. */
 void set_first_hit(Request &r, const uint64_t ids[4]);
 
+/* The scene's draw cache as the launch may use it (Request::drawCache) */
+void set_draw_cache(Request &r, int eligible);
+
 /* The geometry every launch's entry point checks (rtc_render_rows_async's check_arguments, the first-hit test hook):
  * 0 fine, 1 bad geometry (sizes, row selection, band), 2 a frame of more than 2^29 pixels */
 int geometry_error(const RtcRenderDesc &d);
@@ -181,6 +193,14 @@ enum Buf : int {
     kBufRngState,               /* the caller's per-pixel RNG states (a pass, Request::resume) */
     kBufSceneGen,               /* the scene records of the bound generation (Plan::gen) */
     kBufHit,                    /* the caller's first-hit buffers (Request::hit: one footprint row per buffer asked for) */
+    /* The draw cache (Plan::draws).  kBufDrawTable: the slot table (seed -> block) with the pool counter and the blocks'
+     * seeds -- written by the tile cull (its lanes allocate; the fill kernel issued under the same operation moves the
+     * fill mark) and touched by no other kernel; culls are ordered among themselves by kEvFork.  kBufItemDraw: the slot's
+     * array of one block number per item, written by the tile cull beside the item record and read by the geometry
+     * kernel.  The pool's blocks are in neither: they are append-only -- a block is written once, by the fill kernel of the
+     * launch whose cull allocated it, which completes (the cull operation's event) before any geometry kernel that can
+     * name the block starts; later culls and fills never touch an allocated block or a non-zero table entry. */
+    kBufDrawTable, kBufItemDraw,
     kBufs
 };
 struct Region {
@@ -212,6 +232,11 @@ struct Plan {
     unsigned long long geoSet, geoSetNext; /* counter sets (ring indices) */
     bool prep, prepCounts; /* rtc_prep_primary runs, and zeroes the counter set too */
     bool cullPrio;
+    /* the draw cache: the launch's tile cull allocates and fills blocks and its geometry kernel reads them; the cache is
+     * cleared first (another frame size, or none yet), the item-draw arrays regrown first -- both behind a device
+     * synchronisation; the bytes of all kSlots arrays and where this launch's starts */
+    bool draws, drawReset, itemDrawGrow;
+    size_t itemDrawNeed, itemDrawOffset;
     int nOps;
     Op ops[40];
     State after;         /* the ordering state once every operation is enqueued */
@@ -227,7 +252,8 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 /* The memory one kernel of a plan touches, for the ordering test: resource kinds and byte ranges */
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
                  kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */,
-                 kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */ };
+                 kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */,
+                 kResDrawTable = 12, kResItemDraw = 13 /* id: the slot */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;

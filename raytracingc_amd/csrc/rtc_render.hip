@@ -118,11 +118,11 @@ static hipError_t launch_stop(void (*k)(K...), dim3 g, dim3 b, size_t sh, hipStr
 /* ---- which instantiation of rtc_render_chain a launch runs ----------------------------------------------------
  * The template flags, in the template's order (their meaning: rtc_chain.h). */
 struct ChainFlags {
-    bool multi, count, hits, general, spheres, resume;
+    bool multi, count, hits, general, spheres, resume, draws;
     constexpr bool operator==(const ChainFlags &o) const
     {
         return multi == o.multi && count == o.count && hits == o.hits && general == o.general && spheres == o.spheres &&
-               resume == o.resume;
+               resume == o.resume && draws == o.draws;
     }
 };
 
@@ -131,11 +131,13 @@ struct ChainFlags {
  * launch that is none of multi-chunk, counting, deferring, with spheres or a pass runs a kernel without the GENERAL code,
  * and only there does `hits` choose: both choices render the same frame, so only the static_asserts below and the
  * launch's report (rtc_scene_chain_report, which tests/test_gpu_chain_paths.py holds to the launch meant) notice a
- * wrong one. */
-constexpr ChainFlags chain_flags(bool multi, bool count, bool defer, bool hits, bool spheres, bool resume)
+ * wrong one.  `draws`: the launch uses the draw cache (rtcplan::Plan::draws, planned for launches without the GENERAL code
+ * only); a GENERAL kernel never reads it. */
+constexpr ChainFlags chain_flags(bool multi, bool count, bool defer, bool hits, bool spheres, bool resume,
+                                 bool draws = false)
 {
     const bool general = multi || count || defer || spheres || resume;
-    return ChainFlags{multi, count, hits && !general, general, spheres, resume};
+    return ChainFlags{multi, count, hits && !general, general, spheres, resume, draws && !general};
 }
 
 struct ChainVariant {
@@ -153,20 +155,22 @@ template <int n> constexpr int chain_variant(const ChainVariant (&table)[n], Cha
     return n;
 }
 
-/* `rule` for each of chain_flags' 64 inputs (`in`: one bit per parameter, below) and the flags it gives */
-constexpr int kInMulti = 1, kInCount = 2, kInDefer = 4, kInHits = 8, kInSpheres = 16, kInResume = 32;
+/* `rule` for each of chain_flags' 128 inputs (`in`: one bit per parameter, below) and the flags it gives */
+constexpr int kInMulti = 1, kInCount = 2, kInDefer = 4, kInHits = 8, kInSpheres = 16, kInResume = 32, kInDraws = 64;
 template <typename Rule> constexpr bool every_chain_launch(Rule rule)
 {
-    for (int in = 0; in < 64; ++in)
+    for (int in = 0; in < 128; ++in)
         if (!rule(in, chain_flags(in & kInMulti, in & kInCount, in & kInDefer, in & kInHits, in & kInSpheres,
-                                  in & kInResume)))
+                                  in & kInResume, in & kInDraws)))
             return false;
     return true;
 }
-static_assert(every_chain_launch([](int in, ChainFlags f) { return f.general == ((in & ~kInHits) != 0); }),
+static_assert(every_chain_launch([](int in, ChainFlags f) { return f.general == ((in & ~(kInHits | kInDraws)) != 0); }),
               "GENERAL whenever the launch is multi-chunk, counting, deferring, with spheres or a pass");
-static_assert(every_chain_launch([](int in, ChainFlags f) { return f.hits == (in == kInHits); }),
+static_assert(every_chain_launch([](int in, ChainFlags f) { return f.hits == ((in & ~kInDraws) == kInHits); }),
               "HITS only when none of them holds and the scene is hit-heavy");
+static_assert(every_chain_launch([](int in, ChainFlags f) { return f.draws == (!!(in & kInDraws) && !f.general); }),
+              "DRAWS only in the two kernels without GENERAL");
 static_assert(every_chain_launch([](int in, ChainFlags f) {
                   return f.multi == !!(in & kInMulti) && f.count == !!(in & kInCount) &&
                          f.spheres == !!(in & kInSpheres) && f.resume == !!(in & kInResume);
@@ -189,6 +193,7 @@ struct Launch {
     size_t chainDyn; /* and its dynamic LDS */
     bool resume;     /* a pass (rtc_render_samples_async): the RESUME kernels */
     const RtcHitBuffers *hit = nullptr; /* a first-hit launch (rtc_render_first_hit_async): its buffers */
+    DrawCache dc{};  /* a launch that uses the draw cache (pl.draws): the caching tile cull's and the fill's argument */
     dim3 grid() const { return dim3(pl.gridX, pl.gridY); } /* one 16x16 workgroup block each */
     /* every pointer into the scratch: a region the plan binds (rtcplan::Buf), in the launch's slot; unbound: null */
     template <typename T> T *region(int buf) const
@@ -304,6 +309,17 @@ static void bind_plan(Launch &L, int flags)
         P.wideItems = pl.wideItems;
         P.cullPrio = pl.cullPrio;
     }
+    if (pl.binds(rtcplan::kBufDrawTable) && pl.binds(rtcplan::kBufItemDraw)) { /* (rtc_draws_prepare has run) */
+        const RtcDeviceScene::Draws &D = s->draws;
+        L.dc.table = D.table, L.dc.ctr = D.ctr, L.dc.blockSeed = D.blockSeed, L.dc.pool = (float4 *)D.pool;
+        L.dc.itemDraw = (unsigned *)(D.itemDraw + pl.itemDrawOffset);
+        L.dc.capacity = (unsigned)D.capacity;
+        L.dc.tablePixels = (unsigned)((size_t)P.width * (size_t)P.height);
+        L.dc.parity = D.parity;
+        /* the geometry kernel's two (in the deferred samples' places: a launch that uses the cache has no such slots) */
+        P.drawPool = L.dc.pool;
+        P.itemDraw = L.dc.itemDraw;
+    }
     if (pl.binds(rtcplan::kBufSamples)) { /* (a pass: P.spp is its sample count, as the planner sized the slots) */
         P.sampleBuf = (SampleSlot *)s->samples;
         P.itemPix = (int *)(s->samples + (size_t)pl.sampleCap * (size_t)P.spp * sizeof(SampleSlot));
@@ -313,13 +329,32 @@ static void bind_plan(Launch &L, int flags)
 
 /* dynamic LDS of the geometry kernel: the clustered records (single-chunk scenes), then the primary filter records
  * when the block stays within its workgroups per CU */
+/* whether a launch at wgsPerCu workgroups per CU stages the primary filter records (single-chunk scenes whose block stays
+ * within its share of the CU's LDS) */
+static bool chain_prim_f_staged(const RtcDeviceScene *s, int wgsPerCu)
+{
+    const size_t recLds = s->chunkCount <= 1 ? (size_t)soa_slots(s->clusterCount * kClusterSize) * sizeof(DevTri) : 0;
+    const size_t pfLds = (size_t)s->triPadded * sizeof(DevPrimF);
+    return s->chunkCount <= 1 && kChainStaticLds + recLds + pfLds <= kCuLds / (size_t)wgsPerCu;
+}
+
+/* rtcplan::Request::drawCache: the scene's part of "the launch runs a geometry kernel without the GENERAL code" -- the
+ * cache is on, the scene is one chunk and its primary filter records are staged -- for whole frames (bit 0) and small
+ * shares (bit 1), whose workgroups per CU differ */
+static int draw_cache_eligible(const RtcDeviceScene *s)
+{
+    if (s->draws.blocks == 0 || s->triCount == 0)
+        return 0;
+    return (chain_prim_f_staged(s, s->chainWgsFull) ? 1 : 0) | (chain_prim_f_staged(s, RTC_CHAIN_WGS_SHARE) ? 2 : 0);
+}
+
 static void size_chain_lds(Launch &L)
 {
     const RtcDeviceScene *s = L.s;
     L.wgsPerCu = L.pl.smallShare ? RTC_CHAIN_WGS_SHARE : s->chainWgsFull;
     const size_t recLds = s->chunkCount <= 1 ? (size_t)soa_slots(s->clusterCount * kClusterSize) * sizeof(DevTri) : 0;
     const size_t pfLds = (size_t)s->triPadded * sizeof(DevPrimF);
-    L.P.chainPrimF = s->chunkCount <= 1 && kChainStaticLds + recLds + pfLds <= kCuLds / (size_t)L.wgsPerCu;
+    L.P.chainPrimF = chain_prim_f_staged(s, L.wgsPerCu);
     const size_t floorLds = chain_lds_floor(L.wgsPerCu);
     L.chainDyn = std::max<size_t>(recLds + (L.P.chainPrimF ? pfLds : 0),
                                   floorLds > kChainStaticLds ? floorLds - kChainStaticLds : 0);
@@ -353,6 +388,16 @@ static int run_tile_cull(const Launch &L, hipStream_t os, hipEvent_t ev)
     const bool spheres = L.P.geoList && L.P.sphereCount > 0; /* the sphere split: sphere pixels are geometry pixels */
     static void (*const kCull[2])(RenderParams, unsigned long long *, unsigned *, unsigned long long *) = {
         rtc_tile_cull, rtc_tile_cull_sph<true>};
+    if (L.pl.draws) {
+        /* the draw cache: the caching cull, then the fill of the blocks it handed out -- two launches under the one planned
+         * operation, whose completion event is the fill's: the sky pass forks and the next cull starts behind both.  The
+         * fill's parity moves on once it is enqueued (a fill that was not leaves the mark where the next one reads it) */
+        HIP_TRY(launch_stop(rtc_tile_cull_draws<true>, L.grid(), dim3(kBlock), lds, os, nullptr, L.P, mask, weight, pixMask,
+                            L.dc));
+        HIP_TRY(launch_stop(rtc_fill_draws<true>, dim3(kFillBlocks), dim3(256), 0, os, ev, L.dc));
+        const_cast<RtcDeviceScene *>(L.s)->draws.parity ^= 1;
+        return 0;
+    }
     HIP_TRY(launch_stop(kCull[spheres], L.grid(), dim3(kBlock), lds, os, ev, L.P, mask, weight, pixMask));
     return 0;
 }
@@ -394,11 +439,16 @@ static int run_chain(const Launch &L, hipStream_t os, hipEvent_t ev)
         CHAIN_ROW(false, false, false, true, false, true),   CHAIN_ROW(false, true, false, true, false, true),
         CHAIN_ROW(true, false, false, true, false, true),    CHAIN_ROW(true, true, false, true, false, true),
         CHAIN_ROW(false, false, false, true, true, true),    CHAIN_ROW(false, true, false, true, true, true),
-        CHAIN_ROW(true, false, false, true, true, true),     CHAIN_ROW(true, true, false, true, true, true)};
+        CHAIN_ROW(true, false, false, true, true, true),     CHAIN_ROW(true, true, false, true, true, true),
+        /* the draw cache: the two kernels without GENERAL */
+        CHAIN_ROW(false, false, false, false, false, false, true), CHAIN_ROW(false, false, true, false, false, false, true)};
     constexpr int kVariants = (int)(sizeof kChain / sizeof kChain[0]);
     static_assert(every_chain_launch([](int, ChainFlags f) { return chain_variant(kChain, f) < kVariants; }),
                   "every launch selects an instantiated kernel");
-    const int variant = chain_variant(kChain, chain_flags(multi, count, defer, hits, P.sphereCount > 0, L.resume));
+    const int variant =
+        chain_variant(kChain, chain_flags(multi, count, defer, hits, P.sphereCount > 0, L.resume, L.pl.draws));
+    if (kChain[variant].flags.draws != L.pl.draws) /* (the planner's conditions are chain_flags' and draw_cache_eligible's) */
+        return rtc_fail(RTC_EINVAL, "rtc_render_chain: the launch was planned with the draw cache but runs a GENERAL kernel");
     { /* rtc_scene_chain_report: the row taken and size_chain_lds' choices (host stores only) */
         const ChainFlags &f = kChain[variant].flags;
         RtcChainReport &r = const_cast<RtcDeviceScene *>(s)->chainReport;
@@ -536,6 +586,8 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
                                  (uint64_t)(uintptr_t)hit->normal, (uint64_t)(uintptr_t)hit->albedo};
         rtcplan::set_first_hit(rq, ids);
     }
+    if (!hit && !items) /* (the probes' launches enqueue no geometry kernel: nothing would fill or read a block) */
+        rtcplan::set_draw_cache(rq, draw_cache_eligible(s));
     rtcplan::plan_launch(s->plan, rq, pl);
     /* the saved state claims only what has been enqueued: until every operation below is, a later launch sees none of
      * this launch's primary records or counter zeroing (it re-runs rtc_prep_primary) */
@@ -544,6 +596,9 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         ms->plan.cullValid = false;
     if (const int rc = grow_capacity(ms, pl))
         return rc;
+    if (pl.draws) /* the draw cache's memory: allocated, cleared for this frame size, the item-draw arrays large enough */
+        if (const int rc = rtc_draws_prepare(ms, d->width, d->height, pl.drawReset, pl.itemDrawGrow ? pl.itemDrawNeed : 0))
+            return rc;
     bind_plan(L, d->flags);
     if (range) /* (after bind_plan: the state pointer lies where an ordinary launch keeps geoColor, unbound in a pass) */
         L.P.rngState = dRngState;
@@ -856,3 +911,9 @@ template __global__ void rtc_trace_rays<false, true>(TraceRaysArgs);
 template __global__ void rtc_trace_rays<true, true>(TraceRaysArgs);
 template __global__ void rtc_trace_rays<false, false>(TraceRaysArgs);
 template __global__ void rtc_trace_rays<true, false>(TraceRaysArgs);
+/* the draw cache */
+template __global__ void rtc_tile_cull_draws<true>(RenderParams, unsigned long long *, unsigned *, unsigned long long *,
+                                                   DrawCache);
+template __global__ void rtc_fill_draws<true>(DrawCache);
+template __global__ void rtc_render_chain<false, false, false, false, false, false, true>(RenderParams);
+template __global__ void rtc_render_chain<false, false, true, false, false, false, true>(RenderParams);

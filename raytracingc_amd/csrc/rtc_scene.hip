@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -665,6 +666,151 @@ extern "C" int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *o
     return 0;
 }
 
+/* ---- the draw cache's memory (rtc_layout.h RtcDeviceScene::Draws; the kernels: rtc_cull.h, rtc_chain.h) -------------- */
+void rtc_draws_free(RtcDeviceScene *s)
+{
+    RtcDeviceScene::Draws &D = s->draws;
+    for (void *p : {(void *)D.table, (void *)D.ctr, (void *)D.blockSeed, D.pool, (void *)D.itemDraw})
+        if (p)
+            (void)hipFree(p);
+    const long long blocks = D.blocks;
+    D = RtcDeviceScene::Draws{};
+    D.blocks = blocks;
+    /* the next launch that uses the cache plans a cleared table and new item-draw arrays */
+    s->plan.drawWidth = s->plan.drawHeight = 0;
+    s->plan.itemDrawCap = 0;
+}
+
+static int draws_prepare(RtcDeviceScene *s, int width, int height, bool reset, size_t growBytes)
+{
+    RtcDeviceScene::Draws &D = s->draws;
+    const size_t pixels = (size_t)width * (size_t)height;
+    if (reset || growBytes || !D.capacity)
+        HIP_TRY(hipDeviceSynchronize());
+    if (!D.capacity)
+        reset = true;
+    if (reset) {
+        /* the pool: allocated at the first launch that uses the cache and never grown under launches in flight (that would
+         * need a hipFree); a cleared cache for a larger frame, behind the synchronisation above, gets the larger pool */
+        const long long want = D.blocks < 0 ? kDrawCacheDefaultBytes / (long long)kDrawBlockBytes : D.blocks;
+        const size_t cap = std::min<size_t>((size_t)want, pixels);
+        if (cap == 0 || cap >= 0xffffffffull)
+            return rtc_fail(RTC_EINVAL, "draw cache: %zu blocks", cap);
+        if (cap > D.capacity) {
+            for (void *p : {(void *)D.blockSeed, D.pool})
+                if (p)
+                    HIP_TRY(hipFree(p));
+            D.blockSeed = nullptr, D.pool = nullptr, D.capacity = 0;
+            HIP_TRY(hipMalloc(&D.blockSeed, cap * sizeof(unsigned)));
+            HIP_TRY(hipMalloc(&D.pool, cap * kDrawBlockBytes));
+            D.capacity = cap;
+        }
+        if (!D.ctr)
+            HIP_TRY(hipMalloc(&D.ctr, kDcWords * sizeof(unsigned)));
+        if (pixels > D.tablePixels) {
+            if (D.table)
+                HIP_TRY(hipFree(D.table));
+            D.table = nullptr, D.tablePixels = 0;
+            HIP_TRY(hipMalloc(&D.table, pixels * sizeof(unsigned)));
+            D.tablePixels = pixels;
+        }
+        HIP_TRY(hipMemset(D.table, 0, pixels * sizeof(unsigned)));
+        HIP_TRY(hipMemset(D.ctr, 0, kDcWords * sizeof(unsigned)));
+        D.parity = 0;
+    }
+    if (growBytes) {
+        if (D.itemDraw)
+            HIP_TRY(hipFree(D.itemDraw));
+        D.itemDraw = nullptr;
+        HIP_TRY(hipMalloc(&D.itemDraw, growBytes));
+    }
+    if (reset) /* (the scene's streams do not wait for the null stream's memsets) */
+        HIP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
+int rtc_draws_prepare(RtcDeviceScene *s, int width, int height, bool reset, size_t growBytes)
+{
+    const int rc = draws_prepare(s, width, height, reset, growBytes);
+    if (rc) { /* nothing half-built stays behind */
+        (void)hipDeviceSynchronize();
+        rtc_draws_free(s);
+    }
+    return rc;
+}
+
+extern "C" int rtc_scene_set_draw_cache(RtcDeviceScene *s, long long blocks)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_set_draw_cache: null scene");
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_scene_set_draw_cache: cannot select the scene's device %d", s->device);
+    const RtcDeviceScene::Draws &D = s->draws;
+    if (D.table || D.ctr || D.blockSeed || D.pool || D.itemDraw) { /* (nothing to drop before the first cached launch) */
+        HIP_TRY(hipDeviceSynchronize());
+        rtc_draws_free(s);
+    }
+    s->draws.blocks = blocks < 0 ? -1 : blocks;
+    return 0;
+}
+
+extern "C" int rtc_scene_draw_cache_reset(RtcDeviceScene *s)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_draw_cache_reset: null scene");
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_scene_draw_cache_reset: cannot select the scene's device %d", s->device);
+    HIP_TRY(hipDeviceSynchronize());
+    /* the next launch that uses the cache clears it (plan_launch: no frame size yet) */
+    s->plan.drawWidth = s->plan.drawHeight = 0;
+    return 0;
+}
+
+extern "C" int rtc_scene_draw_cache_stats(const RtcDeviceScene *s, unsigned long long out[4])
+{
+    if (!s || !out)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_draw_cache_stats: null argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_scene_draw_cache_stats: cannot select the scene's device %d", s->device);
+    const RtcDeviceScene::Draws &D = s->draws;
+    if (!D.capacity)
+        return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned c[kDcWords];
+    HIP_TRY(hipMemcpy(c, D.ctr, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = std::min<unsigned long long>(c[kDcTaken], D.capacity);
+    out[1] = D.capacity;
+    out[2] = c[kDcFresh];
+    out[3] = c[kDcUncached];
+    return 0;
+}
+
+extern "C" int rtc_probe_draw_cache(const RtcDeviceScene *s, unsigned int seed, float *out, int *block)
+{
+    if (!s || !out || !block)
+        return rtc_fail(RTC_EINVAL, "rtc_probe_draw_cache: null argument");
+    *block = -1;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "rtc_probe_draw_cache: cannot select the scene's device %d", s->device);
+    const RtcDeviceScene::Draws &D = s->draws;
+    if (!D.capacity || (size_t)seed >= (size_t)s->plan.drawWidth * (size_t)s->plan.drawHeight)
+        return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned k = 0;
+    HIP_TRY(hipMemcpy(&k, D.table + seed, sizeof k, hipMemcpyDeviceToHost));
+    if (k == 0 || k > D.capacity)
+        return 0;
+    HIP_TRY(hipMemcpy(out, (const unsigned char *)D.pool + (size_t)(k - 1) * kDrawBlockBytes, kDrawBlockBytes,
+                      hipMemcpyDeviceToHost));
+    *block = (int)(k - 1);
+    return 0;
+}
+
 extern "C" int rtc_scene_upload(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, int device,
                                 RtcDeviceScene **out)
 {
@@ -723,6 +869,12 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
     s->maskWords = (s->triPadded + 63) / 64;
     s->clusterCount = (triCount + kClusterSize - 1) / kClusterSize;
     s->chunkCount = (s->clusterCount + kChunkClusters - 1) / kChunkClusters;
+    { /* the draw cache's capacity in blocks: RTC_DRAW_CACHE_BLOCKS (0: off), else the default (rtc_scene_set_draw_cache) */
+        const char *v = getenv("RTC_DRAW_CACHE_BLOCKS");
+        char *end = nullptr;
+        const long long b = v && *v ? strtoll(v, &end, 10) : -1;
+        s->draws.blocks = v && *v && end && *end == '\0' && b >= 0 ? b : -1;
+    }
     /* whole frames of scenes whose bounce rays often hit again (fsuzane) run 4 chain workgroups per CU: their frame is
      * nearly all geometry kernel, which then has the registers the co-resident sky waves would use (round 5, 1080p x64:
      * fsuzane 1.25 -> 1.16 ms per frame; ultracomplex 0.348 -> 0.379, complex 4K 1.22 -> 1.34, so 3 stays the default,
@@ -838,6 +990,7 @@ extern "C" int rtc_scene_release(RtcDeviceScene *s)
         (void)hipFree(s->segSlots);
     if (s->geoCounts)
         (void)hipFree(s->geoCounts);
+    rtc_draws_free(s);
     if (s->evFork)
         (void)hipEventDestroy(s->evFork);
     if (s->evJoin)

@@ -17,12 +17,13 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 root, workload = sys.argv[1], sys.argv[2]
 KERNELS = ("rtc_render_chain", "rtc_render_sky", "rtc_accumulate_samples", "rtc_tile_cull", "rtc_super_cull",
-           "rtc_prep_primary")
+           "rtc_prep_primary", "rtc_fill_draws")
 
 
 def short(name):
@@ -32,13 +33,23 @@ def short(name):
     return None
 
 
+def untimed(name):
+    """The instantiations that run only beside the timed ones: rtc_render_chain<MULTI, COUNT = true, ...> (the counters'
+    launch); of the other templates, as before, a name whose last argument is true (a pass)."""
+    m = re.search(r"rtc_render_chain<([^>]*)>", name)
+    if m:
+        args = [a.strip() for a in m.group(1).split(",")]
+        return len(args) > 1 and args[1] == "true"
+    return "rtc_tile_cull" not in name and "rtc_fill_draws" not in name and name.endswith("true>(RenderParams)")
+
+
 # kernel trace stats
 stats = {}
 for f in glob.glob(os.path.join(root, "trace", "**", "*kernel_stats.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
         k = short(r["Name"])
         # the timed instantiation: rtc_render_chain<MULTI, COUNT=false>; the counting one runs only for the counters
-        if k and not r["Name"].endswith("true>(RenderParams)"):
+        if k and not untimed(r["Name"]):
             stats[k] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6,
                         "total_ms": float(r["TotalDurationNs"]) / 1e6}
 # counters: every pass directory pmc_* holds one counter group over the same renders
@@ -48,7 +59,7 @@ for d in sorted(glob.glob(os.path.join(root, "pmc_*"))):
         acc = collections.defaultdict(lambda: collections.defaultdict(float))
         for r in csv.DictReader(open(f)):
             k = short(r.get("Kernel_Name", ""))
-            if k and not r.get("Kernel_Name", "").endswith("true>(RenderParams)"):
+            if k and not untimed(r.get("Kernel_Name", "")):
                 acc[k][(r["Counter_Name"], r.get("Dispatch_Id"))] += float(r["Counter_Value"])
         for k, cv in acc.items():
             by = collections.defaultdict(list)
