@@ -386,6 +386,45 @@ int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, in
  * same refusals; RTC_ENODEV without a GPU. */
 int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trianglesOnly, int flags, int *prim,
                    float *depth, float *normal, float *albedo);
+/* Radiance along caller-supplied rays: for ray i, main.c:95-100 with the ray given instead of derived
+ * from a pixel -- rngState = dSeeds[i]; acc = +0 when sampleFirst == 0, otherwise dRadiance[3 i ..]; sampleCount times
+ * acc = acc + calcColor(dRays[i], trianglesOnly, maxBounce, *scene) * (float)(1. / spp) (raytracing.c:262-296); then
+ * dRadiance[3 i ..] = acc and, where dSeedsOut is not null, dSeedsOut[i] = rngState.  Every float is the reference's bit
+ * for bit (where the reference gives a NaN: a NaN).  The direction is used as given, as rtc_trace_rays_async uses it: not
+ * normalised, dst in units of dir, the EPSILON tests at the caller's scale; bounce directions come out of the reference's
+ * own lerp.  dSegments, where not null, is one device u64 to which the launch atomically adds its number of
+ * calculateRayCollision calls.
+ * The samples of one ray are sequential: they form one RNG chain, and the kernel is one lane per ray.  A caller who wants
+ * many samples of one ray quickly passes that ray many times with different seeds and averages.
+ * `scene` and `d` are host pointers, borrowed for the call.  dRays (n Rays), dSeeds (n) and dRadiance (3 n floats) are
+ * required DEVICE pointers on the scene's device; dSeedsOut (n) may be null and may be dSeeds (in place); dRays aliases
+ * no output.  With sampleFirst > 0 the caller passes the previous call's dSeedsOut as dSeeds and the same dRadiance:
+ * calls over [0, a), [a, b), .., [z, spp) leave the radiance, the seeds and the segment count of one call of spp samples,
+ * bit for bit.
+ * d->flags: 0 (the cluster hierarchy) or RTC_F_NO_CLUSTER_CULL (every record in reference order, the same values).
+ * Asynchronous on `stream` and complete there, under rtc_trace_rays_async's rules word for word: it reads the generation
+ * current when it is enqueued, may come between RTC_F_OVERLAP launches, between passes and after an update, uses no
+ * scratch, primary record, counter set, stream or event of the scene's, leaves the one-shot events,
+ * rtc_scene_chain_report, rtc_scene_kernel_times and the draw cache as they were and restores the caller's current
+ * device.  n == 0: returns 0, nothing enqueued.
+ * RTC_EINVAL, with nothing enqueued, checked before any device call and before `s` is read: a null s, scene, dRays,
+ * dSeeds, d or dRadiance; n > 0x7fffffff; spp <= 0; sampleFirst < 0, sampleCount <= 0 or sampleFirst + sampleCount > spp;
+ * a flag other than RTC_F_NO_CLUSTER_CULL (RTC_F_DEBUG_BOUNCES included: calcDebugColor is not offered for caller rays). */
+typedef struct RtcPathDesc {
+    int spp;            /* the weight's accumulationCount: every sample is weighted (float)(1. / spp) (main.c:99) */
+    int maxBounce;      /* calcColor's maxBounce; <= 0: no segment is traced, a sample is +0 and draws nothing */
+    int trianglesOnly;
+    int flags;          /* 0 or RTC_F_NO_CLUSTER_CULL */
+    int sampleFirst, sampleCount; /* this call evaluates samples [sampleFirst, sampleFirst + sampleCount) of spp */
+} RtcPathDesc;
+int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene, const Ray *dRays, const unsigned int *dSeeds,
+                          size_t n, const RtcPathDesc *d, float *dRadiance, unsigned int *dSeedsOut,
+                          unsigned long long *dSegments, void *stream);
+/* The same for HOST arrays, synchronous, built like rtc_trace_rays: stages the rays and seeds (and, with sampleFirst > 0,
+ * the radiance; and the segment counter's value), waits for the device, runs the query on the null stream and copies
+ * back radiance[3 n], seedsOut[n] and *segments (the last two nullable).  The same refusals; RTC_ENODEV without a GPU. */
+int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds, size_t n,
+                    const RtcPathDesc *d, float *radiance, unsigned int *seedsOut, unsigned long long *segments);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */
@@ -469,6 +508,17 @@ int rtc_plan_sim_set_update_fault(RtcPlanSim *sim, int mode);
 int rtc_plan_sim_trace_rays(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays,
                             const unsigned long long hit[4], int flags, int *ops, int maxOps,
                             unsigned long long *footprint, int maxFootprint);
+/* Plans one rtc_trace_paths_async on the caller's stream `stream`, in rtc_plan_sim_trace_rays's encodings: one kernel op
+ * (kernel 12, stream 0, no event) with its footprint records -- it reads the current generation (resource 9), the ray
+ * buffer (resource 11, id = `rays`), the seeds (resource 14, id = `seeds`) and, with sampleFirst > 0, the radiance
+ * (resource 15, id = `radiance`), writes the radiance and, where asked for (an identity that is not 0), the seeds
+ * (resource 14, id = `seedsOut`) and the caller's segment counter (resource 7, an atomic add), in that order -- then one
+ * u64 record (~0, 0, the generation read, 0, 0, 0).  The planner's state is left as it was.  RTC_EINVAL where the entry
+ * point refuses: `rays`, `seeds` or `radiance` 0, sampleFirst < 0, a flag other than RTC_F_NO_CLUSTER_CULL. */
+int rtc_plan_sim_trace_paths(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays,
+                             unsigned long long seeds, unsigned long long radiance, unsigned long long seedsOut,
+                             unsigned long long segments, int sampleFirst, int flags, int *ops, int maxOps,
+                             unsigned long long *footprint, int maxFootprint);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the

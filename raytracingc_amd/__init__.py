@@ -50,6 +50,7 @@ from ._abi import (  # noqa: F401
     RtcError,
     RtcHitBuffers,
     RtcLoopStats,
+    RtcPathDesc,
     RtcRenderDesc,
     RtcSampleRange,
     RtcStats,
@@ -390,6 +391,95 @@ class DeviceScene:
             check(lib().rtc_trace_rays(self._h, _ptr(a), n, int(bool(triangles_only)), flags,
                                        *(_ptr(out[k]) if k in out else None for k in shapes)), "rtc_trace_rays")
         return out
+
+    def trace_paths_async(self, scene: Scene, rays_ptr: int, seeds_ptr: int, n: int, spp: int, max_bounce: int,
+                          radiance_ptr: int, triangles_only: bool = False, flags: int = 0, first: int = 0,
+                          count: int | None = None, seeds_out_ptr: int = 0, segments_ptr: int = 0,
+                          stream: int | None = None):
+        """rtc_trace_paths_async: the radiance along n caller-supplied Rays (device memory at rays_ptr) with the RNG
+        seeds at seeds_ptr (uint32 [n]): samples [first, first + count) of spp (count None: the rest) of main.c:95-100
+        with the ray given -- acc = acc + calcColor(ray, trianglesOnly, maxBounce, scene) * (float)(1. / spp) -- into
+        radiance_ptr (float32 [n, 3]; read first when first > 0), the RNG states into seeds_out_ptr (0: not wanted; may be
+        seeds_ptr) and the number of calculateRayCollision calls added to the u64 at segments_ptr (0: not wanted).  The
+        samples of one ray are sequential.  Asynchronous on `stream`, complete there; the scene's ordering state and
+        events stay as they were."""
+        d = RtcPathDesc(int(spp), int(max_bounce), int(bool(triangles_only)), int(flags), int(first),
+                        int(spp) - int(first) if count is None else int(count))
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        check(lib().rtc_trace_paths_async(self._h, C.byref(scene), vp(rays_ptr), vp(seeds_ptr), n, C.byref(d),
+                                          vp(radiance_ptr), vp(seeds_out_ptr), vp(segments_ptr), vp(stream)),
+              "rtc_trace_paths_async")
+
+    def trace_paths(self, rays, seeds, scene: Scene, spp: int, max_bounce: int, triangles_only: bool = False,
+                    flags: int = 0, first: int = 0, count: int | None = None, radiance=None,
+                    segments: bool = False) -> dict:
+        """The radiance along `rays` as host arrays: {"radiance": float32 [n, 3], "seeds": uint32 [n]} (the RNG states
+        after the samples) plus "segments": int (the calculateRayCollision calls) when asked for -- trace_paths_async's
+        values for samples [first, first + count) of spp (count None: the rest).  With first > 0 `radiance` is the
+        accumulator so far and `seeds` the states the previous call returned.  `rays` and `seeds` (and `radiance`):
+        numpy arrays (RAY_DT [n] or float32 [n, 6]; uint32 [n]; float32 [n, 3]), which take the synchronous host entry
+        rtc_trace_paths; or torch tensors on the scene's device, read in place by rtc_trace_paths_async on torch's
+        current stream there (the inputs are left as they were) -- the results are numpy arrays in both cases."""
+        count = int(spp) - int(first) if count is None else int(count)
+        if first > 0 and radiance is None:
+            raise ValueError("DeviceScene.trace_paths: first > 0 continues an accumulation: pass its radiance")
+        if hasattr(rays, "data_ptr"):
+            import torch
+
+            nbytes = rays.numel() * rays.element_size()
+            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
+                raise ValueError("DeviceScene.trace_paths: rays must be a contiguous device tensor of whole 24-byte Rays")
+            n = nbytes // RAY_DT.itemsize
+            if not hasattr(seeds, "data_ptr") or seeds.device != rays.device or not seeds.is_contiguous() or \
+                    seeds.numel() * seeds.element_size() != 4 * n:
+                raise ValueError("DeviceScene.trace_paths: seeds must be a contiguous tensor of n 4-byte words on the rays' device")
+            if first > 0:
+                if not hasattr(radiance, "data_ptr") or radiance.device != rays.device or \
+                        radiance.dtype != torch.float32 or radiance.numel() != 3 * n:
+                    raise ValueError("DeviceScene.trace_paths: radiance must be a float32 [n, 3] tensor on the rays' device")
+                rad = radiance.contiguous().clone().reshape(n, 3)
+            else:
+                rad = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+            out = torch.zeros(n, dtype=torch.int32, device=rays.device)
+            seg = torch.zeros(1, dtype=torch.int64, device=rays.device)
+            if n:
+                with torch.cuda.device(rays.device):
+                    st = torch.cuda.current_stream().cuda_stream
+                    self.trace_paths_async(scene, rays.data_ptr(), seeds.data_ptr(), n, spp, max_bounce, rad.data_ptr(),
+                                           triangles_only, flags, first, count, out.data_ptr(),
+                                           seg.data_ptr() if segments else 0, stream=st)
+                    torch.cuda.current_stream().synchronize()
+            res = {"radiance": rad.cpu().numpy(), "seeds": out.cpu().numpy().view(np.uint32)}
+            if segments:
+                res["segments"] = int(seg.cpu().numpy()[0])
+            return res
+        a = np.asarray(rays)
+        if a.dtype != RAY_DT:
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError("DeviceScene.trace_paths: rays must be RAY_DT [n] or float32 [n, 6]")
+            a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
+        a = np.ascontiguousarray(a.reshape(-1))
+        n = len(a)
+        sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.uint32)
+        if len(sd) != n:
+            raise ValueError(f"DeviceScene.trace_paths: {len(sd)} seeds for {n} rays")
+        if first > 0:
+            rad = np.array(radiance, np.float32, order="C")  # (a copy: the caller's array is left as it was)
+            if rad.size != 3 * n:
+                raise ValueError("DeviceScene.trace_paths: radiance must be float32 [n, 3]")
+            rad = rad.reshape(n, 3)
+        else:
+            rad = np.zeros((n, 3), np.float32)
+        out = np.zeros(n, np.uint32)
+        seg = C.c_ulonglong(0)
+        if n:
+            d = RtcPathDesc(int(spp), int(max_bounce), int(bool(triangles_only)), int(flags), int(first), count)
+            check(lib().rtc_trace_paths(self._h, C.byref(scene), _ptr(a), _ptr(sd), n, C.byref(d), _ptr(rad), _ptr(out),
+                                        C.cast(C.pointer(seg), C.c_void_p) if segments else None), "rtc_trace_paths")
+        res = {"radiance": rad, "seeds": out}
+        if segments:
+            res["segments"] = int(seg.value)
+        return res
 
     def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
         """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with

@@ -73,6 +73,10 @@ class RtcHitBuffers(C.Structure):  # rtc_render_first_hit_async's device buffers
     _fields_ = [("prim", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p)]
 
 
+class RtcPathDesc(C.Structure):  # rtc_trace_paths_async's sample weight, bounces and sample range (include/rtc.h)
+    _fields_ = [(k, C.c_int) for k in ("spp", "maxBounce", "trianglesOnly", "flags", "sampleFirst", "sampleCount")]
+
+
 class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geometry-kernel launch chose (include/rtc.h)
     _fields_ = [(k, C.c_int) for k in ("multi", "count", "hits", "general", "spheres", "resume", "chainPrimF", "wgsPerCu",
                                        "chainDyn", "clusterCount", "chunkCount", "launches")]
@@ -166,6 +170,7 @@ EXPORTS = [
     "rtc_trace_rays_async", "rtc_trace_rays", "rtc_plan_sim_trace_rays",
     "rtc_scene_set_draw_cache", "rtc_scene_draw_cache_reset", "rtc_scene_draw_cache_stats", "rtc_probe_draw_cache",
     "rtc_plan_sim_set_draw_cache",
+    "rtc_trace_paths_async", "rtc_trace_paths", "rtc_plan_sim_trace_paths",
 ]
 
 _lib = None
@@ -287,6 +292,11 @@ def lib() -> C.CDLL:
         L.rtc_scene_draw_cache_stats.argtypes = [vp, vp]
         L.rtc_probe_draw_cache.argtypes = [vp, C.c_uint, vp, C.POINTER(C.c_int)]
         L.rtc_plan_sim_set_draw_cache.argtypes = [vp, ip]
+    if hasattr(L, "rtc_trace_paths_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_trace_paths_async.argtypes = [vp, C.POINTER(Scene), vp, vp, sz, C.POINTER(RtcPathDesc), vp, vp, vp, vp]
+        L.rtc_trace_paths.argtypes = [vp, C.POINTER(Scene), vp, vp, sz, C.POINTER(RtcPathDesc), vp, vp, vp]
+        L.rtc_plan_sim_trace_paths.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
+                                               C.c_ulonglong, C.c_ulonglong, ip, ip, vp, ip, vp, ip]
     _lib = L
     return L
 

@@ -62,8 +62,10 @@ enum Event : int {
 enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce,
                     kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */,
                     kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */,
-                    kKTraceRays /* rtc_trace_rays_async's kernel (plan_trace_rays); never part of a launch */ };
-static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11, "the kernels' numbers are the test hooks' encoding");
+                    kKTraceRays /* rtc_trace_rays_async's kernel (plan_trace_rays); never part of a launch */,
+                    kKTracePaths /* rtc_trace_paths_async's kernel (plan_trace_paths); never part of a launch */ };
+static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12,
+              "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
     int kind;   /* OpKind */
@@ -253,7 +255,8 @@ void plan_launch(const State &s, const Request &r, Plan &p);
 enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3, kResSegSlots = 4, kResColors = 5,
                  kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */,
                  kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */,
-                 kResDrawTable = 12, kResItemDraw = 13 /* id: the slot */ };
+                 kResDrawTable = 12, kResItemDraw = 13 /* id: the slot */,
+                 kResSeeds = 14 /* id: the caller's seed buffer */, kResRadiance = 15 /* id: the caller's buffer */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -294,5 +297,16 @@ void plan_trace_rays(const State &s, TracePlan &t);
 /* the kernel's footprint: the generation read, the rays read (id: the buffer), one write per hit buffer asked for
  * (hit[k] == 0: not asked for), in that order */
 int trace_footprint(const TracePlan &t, uint64_t rays, const uint64_t hit[4], Footprint *out, int max);
+
+/* One rtc_trace_paths_async: plan_trace_rays's plan with the path kernel -- one kernel on the caller's
+ * stream, nothing of the scene's beyond the records of the current generation, `after` equal to the state it was planned
+ * from. */
+void plan_trace_paths(const State &s, TracePlan &t);
+/* the kernel's footprint, in this order: the generation read, the rays read, the seeds read (ids: the buffers), the
+ * radiance read only when the call continues an accumulation (readRadiance: sampleFirst > 0), the radiance written, the
+ * seeds written (id: the out buffer; 0: not asked for) and the caller's segment counter added to atomically (when asked
+ * for; id 0 as in a launch's footprint) */
+int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t radiance, uint64_t seedsOut, bool segments,
+                    bool readRadiance, Footprint *out, int max);
 
 } // namespace rtcplan

@@ -100,6 +100,7 @@ extern "C" int rtc_device_count(int *count)
 #include "rtc_chain.h"
 #include "rtc_first_hit.h"
 #include "rtc_trace_rays.h"
+#include "rtc_trace_paths.h"
 
 /* A kernel launch whose completion also records `stop` (null: a plain launch): the event is the dispatch's own
  * completion signal, so the stream gets no separate marker packet -- each marker on the launch stream cost ~5-7 us
@@ -765,6 +766,118 @@ extern "C" int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n
     return rc;
 }
 
+/* ---- caller-supplied rays: radiance --------------------------------------------------------------- */
+/* the refusals of rtc_trace_paths_async and rtc_trace_paths, before any device call and before `s` is read */
+static int check_trace_paths(const char *who, const RtcDeviceScene *s, const Scene *scene, const void *rays,
+                             const void *seeds, size_t n, const RtcPathDesc *d, const void *radiance)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
+    if (!scene || !rays || !seeds || !d || !radiance)
+        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
+    if (n > (size_t)0x7fffffff)
+        return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
+    if (d->spp <= 0)
+        return rtc_fail(RTC_EINVAL, "%s: spp %d", who, d->spp);
+    if (d->sampleFirst < 0 || d->sampleCount <= 0 || d->sampleFirst > d->spp - d->sampleCount)
+        return rtc_fail(RTC_EINVAL, "%s: samples [%d, %d + %d) of spp %d", who, d->sampleFirst, d->sampleFirst,
+                        d->sampleCount, d->spp);
+    if (d->flags & ~RTC_F_NO_CLUSTER_CULL)
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (a path query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who,
+                        d->flags);
+    return 0;
+}
+
+extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene, const Ray *dRays,
+                                     const unsigned int *dSeeds, size_t n, const RtcPathDesc *d, float *dRadiance,
+                                     unsigned int *dSeedsOut, unsigned long long *dSegments, void *stream)
+{
+    const char *const who = "rtc_trace_paths_async";
+    if (const int rc = check_trace_paths(who, s, scene, dRays, dSeeds, n, d, dRadiance))
+        return rc;
+    if (n == 0)
+        return 0;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* as rtc_trace_rays_async: the planner names the generation and the one operation (rtc_plan.h plan_trace_paths), and
+     * the ordering state, the hooks, the timing events, the chain report and the draw cache stay as they are */
+    rtcplan::TracePlan tp;
+    rtcplan::plan_trace_paths(s->plan, tp);
+    const SceneRecords &g = s->gen[tp.gen];
+    TracePathsArgs a{};
+    a.tris = g.tris, a.mats = g.mats, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters;
+    a.chunks = g.chunks;
+    a.triPadded = s->triPadded, a.sphereCount = d->trianglesOnly ? 0 : s->sphereCount;
+    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
+    a.env = env_of(*scene);
+    a.invSpp = (float)(1. / d->spp); /* main.c:99 */
+    a.sampleFirst = d->sampleFirst, a.sampleCount = d->sampleCount, a.maxBounce = d->maxBounce;
+    a.rays = (const float *)dRays, a.n = (unsigned)n;
+    a.seeds = dSeeds, a.radiance = dRadiance, a.seedsOut = dSeedsOut, a.segments = dSegments;
+    /* <SPHERES, CULL> */
+    static void (*const kTracePaths[2][2])(TracePathsArgs) = {
+        {rtc_trace_paths<false, false>, rtc_trace_paths<false, true>},
+        {rtc_trace_paths<true, false>, rtc_trace_paths<true, true>}};
+    for (int i = 0; i < tp.nOps; ++i) {
+        const rtcplan::Op &op = tp.ops[i];
+        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKTracePaths || op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
+        hipLaunchKernelGGL(kTracePaths[a.sphereCount > 0][!(d->flags & RTC_F_NO_CLUSTER_CULL)],
+                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds,
+                               size_t n, const RtcPathDesc *d, float *radiance, unsigned int *seedsOut,
+                               unsigned long long *segments)
+{
+    const char *const who = "rtc_trace_paths";
+    if (const int rc = check_trace_paths(who, s, scene, rays, seeds, n, d, radiance))
+        return rc;
+    if (n == 0)
+        return 0;
+    int devices = 0;
+    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
+        return rc;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* staged through device buffers on the null stream, like rtc_trace_rays; the radiance goes in too when the call
+     * continues an accumulation, and the segment counter starts at the caller's value */
+    const size_t bytes[5] = {n * sizeof(Ray), n * sizeof(unsigned), n * 3 * sizeof(float), n * sizeof(unsigned),
+                             sizeof(unsigned long long)};
+    const void *const in[5] = {rays, seeds, d->sampleFirst > 0 ? radiance : nullptr, nullptr, segments};
+    void *const out[5] = {nullptr, nullptr, radiance, seedsOut, segments};
+    const bool want[5] = {true, true, true, seedsOut != nullptr, segments != nullptr};
+    void *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5; ++k) {
+        if (e == hipSuccess && want[k])
+            e = hipMalloc(&dev[k], bytes[k]);
+        if (e == hipSuccess && want[k] && in[k])
+            e = hipMemcpy(dev[k], in[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    int rc = e == hipSuccess
+                 ? rtc_trace_paths_async(s, scene, (const Ray *)dev[0], (const unsigned *)dev[1], n, d, (float *)dev[2],
+                                         (unsigned *)dev[3], (unsigned long long *)dev[4], nullptr)
+                 : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
+    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (int k = 0; k < 5; ++k)
+        if (rc == 0 && dev[k] && out[k] && (e = hipMemcpy(out[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (void *p : dev)
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items)
 {
@@ -917,3 +1030,8 @@ template __global__ void rtc_tile_cull_draws<true>(RenderParams, unsigned long l
 template __global__ void rtc_fill_draws<true>(DrawCache);
 template __global__ void rtc_render_chain<false, false, false, false, false, false, true>(RenderParams);
 template __global__ void rtc_render_chain<false, false, true, false, false, false, true>(RenderParams);
+/* caller-supplied rays: radiance */
+template __global__ void rtc_trace_paths<false, true>(TracePathsArgs);
+template __global__ void rtc_trace_paths<true, true>(TracePathsArgs);
+template __global__ void rtc_trace_paths<false, false>(TracePathsArgs);
+template __global__ void rtc_trace_paths<true, false>(TracePathsArgs);

@@ -1,0 +1,198 @@
+/* rtc_trace_paths.h -- rtc_trace_paths: the radiance along caller-supplied rays against the resident scene
+ * (rtc_trace_paths_async): main.c:95-100 with the ray given instead of derived from a pixel -- per ray,
+ * sampleCount times acc = acc + calcColor(ray, trianglesOnly, maxBounce, scene) * (float)(1. / spp) (raytracing.c:262-296)
+ * on one RNG chain that starts at the caller's seed.
+ * A section of rtc_render.hip's translation unit: included there once, after rtc_trace_rays.h (it uses the names of the
+ * headers above it in that file's list, and rtcdev's through the file's using-directive). */
+#pragma once
+
+/* The kernel's own arguments: the record part of TraceRaysArgs (the bound generation's records and their counts), the
+ * environment, the sample range and the five buffers. */
+struct TracePathsArgs {
+    const DevTri *__restrict__ tris;         /* reference order, triPadded + 8 records */
+    const DevMat *__restrict__ mats;
+    const DevSphere *__restrict__ spheres;
+    const DevTri *__restrict__ clTris;       /* cluster order, pad0 = reference index (-1: padding, a zero record) */
+    const DevCluster *__restrict__ clusters;
+    const DevCluster *__restrict__ chunks;
+    int triPadded, sphereCount, clusterCount, chunkCount;
+    EnvParams env;                           /* env_of(*scene); the kernel points its tables at the LDS copies */
+    float invSpp;                            /* (float)(1. / spp), main.c:99 */
+    int sampleFirst, sampleCount, maxBounce;
+    const float *__restrict__ rays;          /* n Rays: pos.xyz, dir.xyz (24 B, 4-byte aligned) */
+    unsigned n;                              /* <= 0x7fffffff */
+    const unsigned *seeds;                   /* n; may be seedsOut (in place): not restrict */
+    float *radiance;                         /* 3 n; read when sampleFirst > 0, written */
+    unsigned *seedsOut;                      /* n; nullable */
+    unsigned long long *segments;            /* one u64, nullable: += calculateRayCollision calls */
+};
+
+/* The closest hit of one ray per lane (calculateRayCollision, raytracing.c:216-240), wave-wide: rtc_trace_rays' walk
+ * (rtc_trace_rays.h has the description and the argument for its exactness) as a function, statement for statement, with
+ * the participating lanes as an argument.  `live` is this lane's bit of that mask: a lane that is not live runs through the
+ * wave-uniform loops with whatever ray it holds, keeps no ball in the ballots and gets a result its caller discards.
+ * Call it from wave-uniform control flow.
+ * rtc_trace_rays keeps its own copy of these statements: calling this function from it (tried returning the Closest, filling
+ * a reference, and with the arguments by value) changed the register allocation and block order of its four kernels, and
+ * the kernels of earlier rounds stay instruction-identical (tools/kernel_diff.py). */
+template <bool SPHERES, bool CULL>
+__device__ __forceinline__ Closest trace_closest(const TracePathsArgs &A, V3 pos, V3 dir, bool live)
+{
+    Closest c{999999.f, -1}; /* HitInfo closest = {0, 999999} */
+    if (SPHERES) {
+        for (int k = 0; k < A.sphereCount; ++k) {
+            const DevSphere sp = A.spheres[k];
+            float d;
+            if (ray_sphere(pos, dir, V3{sp.cx, sp.cy, sp.cz}, sp.radius, d) && d < c.dst) {
+                c.dst = d;
+                c.idx = k;
+            }
+        }
+    }
+    const int base = SPHERES ? A.sphereCount : 0;
+    if (!CULL) {
+        RenderParams P{}; /* (closest_general reads the records and their padded count, nothing else) */
+        P.tris = A.tris;
+        P.triPadded = A.triPadded;
+        closest_general(P, pos, dir, c, base);
+    } else {
+        const float rho = fabsf(dir.x) + fabsf(dir.y) + fabsf(dir.z), dd = dir_dd(dir);
+        const bool cull = live && rho <= kClusterRhoMax; /* this lane may cull: it has a ray, within the bound's premise */
+        for (int h = 0; h < A.chunkCount; ++h) {
+            const int c0 = h * kChunkClusters, nCl = min(kChunkClusters, A.clusterCount - c0);
+            if (A.chunkCount > 1) {
+                const DevCluster H = KLOAD(A.chunks, h);
+                if (!__ballot(live && !(cull && cluster_culled(pos, dir, rho, dd, H))))
+                    continue;
+            }
+            for (int k = 0; k < nCl; ++k) {
+                const DevCluster K = KLOAD(A.clusters, c0 + k);
+                if (!__ballot(live && !(cull && cluster_culled(pos, dir, rho, dd, K))))
+                    continue;
+                const DevTri *rec = A.clTris + (size_t)(c0 + k) * kClusterSize;
+#pragma unroll 4
+                for (int j = 0; j < kClusterSize; ++j) {
+                    const DevTri R = KLOAD(rec, j);
+                    if (general_filter(pos, dir, R))
+                        general_exact(pos, dir, R, base + __float_as_int(R.pad0), c);
+                }
+            }
+        }
+    }
+    return c;
+}
+
+/* One lane per ray, a wave 64 consecutive rays; lanes past n load and store nothing, are never alive and stay in the
+ * wave-wide operations.  rtc_lane.h's state machine without the camera, the tile masks, hoisting and DEBUG: while any
+ * lane of the wave is alive every alive lane traces one segment -- trace_closest, the wave-wide part: the lanes that are
+ * not alive run through it with a stale ray whose result is discarded -- and then takes the hit branch (raytracing.c:
+ * 274-287, rtc_lane.h's arithmetic) or the miss branch (:291, environment).  At a sample's end acc = acc + light *
+ * invSpp (main.c:99) and the lane restarts from its own ray, or dies after sampleCount samples.  The samples of one ray
+ * are sequential (one RNG chain); a lane whose ray is done idles until the wave's last ray ends.
+ * A lane's result depends on its ray and seed alone: trace_closest's does not depend on the other lanes' rays, and
+ * everything else is per lane.
+ * The only LDS is the powf tables (PowTablesLds).  The seed is read before the loop and written after it, so seedsOut
+ * may be seeds.  The segment count is reduced over the wave and added once per wave. */
+template <bool SPHERES, bool CULL>
+__global__ __launch_bounds__(kBlock) void rtc_trace_paths(TracePathsArgs A)
+{
+    __shared__ PowTablesLds sPow;
+    sPow.fill(threadIdx.x);
+    __syncthreads();
+    sPow.attach(A.env);
+
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < (size_t)A.n;
+    V3 pos0{0.f, 0.f, 0.f}, dir0{0.f, 0.f, 0.f}, acc{0.f, 0.f, 0.f};
+    unsigned rng = 0;
+    if (live) {
+        const float *r = A.rays + 6 * i;
+        pos0 = V3{r[0], r[1], r[2]};
+        dir0 = V3{r[3], r[4], r[5]};
+        rng = A.seeds[i];
+        if (A.sampleFirst > 0) /* the accumulator after sampleFirst samples */
+            acc = V3{A.radiance[3 * i], A.radiance[3 * i + 1], A.radiance[3 * i + 2]};
+    }
+    bool alive = live && A.maxBounce > 0;
+    if (live && !alive) /* calcColor without a bounce loop returns +0: acc + 0 * invSpp, the same after one sample or many */
+        acc = add(acc, mul(V3{0.f, 0.f, 0.f}, A.invSpp));
+    int sample = 0, bounce = 0;
+    V3 pos = pos0, dir = dir0, rayColor{1.f, 1.f, 1.f}, light{0.f, 0.f, 0.f};
+    unsigned long long segCalls = 0;
+
+    while (__any(alive)) {
+        const Closest c = trace_closest<SPHERES, CULL>(A, pos, dir, alive);
+        if (alive) {
+            segCalls++;
+            bool endSample;
+            if (c.idx >= 0) {
+                /* closest.hitPoint = ray.pos + ray.dir * closest.dst (raytracing.c:238) */
+                const V3 hitPoint = add(pos, mul(dir, c.dst));
+                V3 normal, color;
+                float emission, smoothness;
+                if (SPHERES && c.idx < A.sphereCount) {
+                    const DevSphere sp = A.spheres[c.idx];
+                    normal = normalized(sub(hitPoint, V3{sp.cx, sp.cy, sp.cz})); /* raytracing.c:182 */
+                    color = V3{sp.r, sp.g, sp.b};
+                    emission = sp.emission;
+                    smoothness = sp.smoothness;
+                } else {
+                    const int t = c.idx - (SPHERES ? A.sphereCount : 0);
+                    const DevTri T = A.tris[t];
+                    const DevMat M = A.mats[t];
+                    normal = V3{T.nx, T.ny, T.nz};
+                    color = V3{M.r, M.g, M.b};
+                    emission = M.emission;
+                    smoothness = M.smoothness;
+                }
+                /* calcColor hit branch, raytracing.c:274-287 */
+                const V3 diffuseDir = normalized(add(normal, random_direction(rng)));
+                const V3 specularDir = reflect(dir, normal);
+                dir = lerp(diffuseDir, specularDir, smoothness);
+                pos = hitPoint;
+                const V3 emitted = mul(color, emission);
+                light = add(light, mulv(emitted, rayColor));
+                rayColor = mulv(rayColor, color);
+                const float p = fmax_ref(fmax_ref(rayColor.x, rayColor.y), rayColor.z);
+                endSample = p < random_value(rng);
+                if (!endSample) {
+                    rayColor = mul(rayColor, rcp_cr(p)); /* (float)(1.0 / p) */
+                    bounce++;
+                    endSample = bounce >= A.maxBounce;
+                }
+            } else {
+                /* miss branch, raytracing.c:291 */
+                light = add(light, mulv(environment(dir, A.env), rayColor));
+                endSample = true;
+            }
+            if (endSample) {
+                /* main.c:99: acc = acc + calcColor(...) * (float)(1./spp) */
+                acc = add(acc, mul(light, A.invSpp));
+                sample++;
+                if (sample >= A.sampleCount) {
+                    alive = false;
+                } else {
+                    pos = pos0;
+                    dir = dir0;
+                    rayColor = V3{1.f, 1.f, 1.f};
+                    light = V3{0.f, 0.f, 0.f};
+                    bounce = 0;
+                }
+            }
+        }
+    }
+
+    if (live) {
+        A.radiance[3 * i] = acc.x;
+        A.radiance[3 * i + 1] = acc.y;
+        A.radiance[3 * i + 2] = acc.z;
+        if (A.seedsOut)
+            A.seedsOut[i] = rng; /* a ray without a hit drew nothing: its seed */
+    }
+    if (A.segments) {
+        for (int off = 32; off > 0; off >>= 1)
+            segCalls += __shfl_xor(segCalls, off);
+        if ((threadIdx.x & 63) == 0 && segCalls)
+            atomicAdd(A.segments, segCalls);
+    }
+}
