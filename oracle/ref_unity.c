@@ -14,7 +14,11 @@
  *   (4) a float capture hook on vec3ToColor (raytracing.c:11) used by rowThread (main.c:100), giving the
  *       pre-quantisation framebuffer;
  *   (5) KAT entry points that call the reference functions themselves (RandomValue, rayTriangle,
- *       raySphere, getEnvironmentLight, calcColor, loaders) on inputs read from binary files.
+ *       raySphere, getEnvironmentLight, calcColor, loaders) on inputs read from binary files;
+ *   (6) the sphere array made replaceable: scene.h:17-20 is included once under another name for its
+ *       array, and `spheres` then names a pointer that starts at that array, so calculateRayCollision
+ *       (raytracing.c:220-226) indexes the pointer; sphereCount (scene.h:20) loses its `const` by (3).
+ *       --kat-calc-raw points both, and triangles / triangleCount, at raw Triangle[] / Sphere[] files.
  *
  * Behaviour of the render is otherwise exactly the reference's (same flags, same BMP, 12 row-interleaved
  * pthreads main.c:43,84).  The wrapper main parses its own leading options and forwards the rest to the
@@ -43,6 +47,13 @@ static void rtc_ref_capture(int x, int y, float r, float g, float b);
 /* (3) make accumulationCount writable */
 #define const
 #define main rtc_ref_main
+/* (6) scene.h is `#pragma once`: included here first, its array is rtc_ref_builtin_spheres (and sphereCount
+ *     its length, 1); every later use of `spheres` reads the pointer */
+#define spheres rtc_ref_builtin_spheres
+#include "scene.h"
+#undef spheres
+static Sphere *rtc_ref_spheres = rtc_ref_builtin_spheres;
+#define spheres rtc_ref_spheres
 #include "moremath.c"
 #include "raytracing.c"
 #include "objloader.c"
@@ -51,6 +62,7 @@ static void rtc_ref_capture(int x, int y, float r, float g, float b);
 #undef vec3ToColor
 #undef main
 #undef const
+#undef spheres
 
 /* ------------------------------------------------------------------------------------------------ */
 static float *g_fb = NULL;
@@ -249,6 +261,33 @@ int main(int argc, char **argv)
                 out[i].seedAfter = rngState;
             }
             write_all(argv[a + 3], out, n * sizeof(KatCalcOut));
+            return 0;
+        } else if (strcmp(argv[a], "--kat-calc-raw") == 0 && a + 6 < argc) {
+            /* --kat-calc-raw <tris.bin> <spheres.bin> <trianglesOnly> <debug 0|1> <in> <out>: calcColor (or
+             * calcDebugColor) per record against a raw Triangle[] (68 B each) and a raw Sphere[] (36 B each);
+             * either file may be empty */
+            size_t tb, sb, nb;
+            void *tbuf = read_all(argv[a + 1], &tb);
+            void *sbuf = read_all(argv[a + 2], &sb);
+            if (tb % sizeof(Triangle) != 0 || sb % sizeof(Sphere) != 0)
+                die("raw geometry: not a whole number of records");
+            triangles = tbuf;
+            triangleCount = (int)(tb / sizeof(Triangle));
+            rtc_ref_spheres = sbuf;
+            sphereCount = (int)(sb / sizeof(Sphere));
+            int tonly = atoi(argv[a + 3]);
+            int debug = atoi(argv[a + 4]);
+            scene.normalizedSunDirection = normalized(sunDirection);
+            KatCalcIn *in = read_all(argv[a + 5], &nb);
+            size_t n = nb / sizeof(KatCalcIn);
+            KatCalcOut *out = calloc(n ? n : 1, sizeof(KatCalcOut));
+            for (size_t i = 0; i < n; ++i) {
+                rngState = in[i].seed;
+                out[i].color = debug ? calcDebugColor(in[i].ray, tonly, in[i].maxBounce, scene)
+                                     : calcColor(in[i].ray, tonly, in[i].maxBounce, scene);
+                out[i].seedAfter = rngState;
+            }
+            write_all(argv[a + 6], out, n * sizeof(KatCalcOut));
             return 0;
         } else if (strcmp(argv[a], "--dump-tris") == 0 && a + 2 < argc) {
             /* --dump-tris <mode: default|path.obj> <out> */

@@ -16,6 +16,10 @@ the deterministic variant described in SURVEY.md F4 (oracle/ref_unity.c, oracle/
   kat_debug_<scene>.npz  calcDebugColor (raytracing.c:242-260) per (ray, seed, maxBounce)
   kat_calc_materials.npz calcColor on the finite scenes of tests/material_scenes.py (smoothness -1 .. 3e38, colours outside
                          [0, 1], emission 3e38), each written out as a triangles.txt for the reference's own parser
+  kat_ref_<family>.npz   calcColor (and, for adversarial and spheres, calcDebugColor) on the scenes of tests/reference_calc.py
+                         -- adversarial, boxes, materials (non-finite ones included), spheres (any number of them),
+                         populations --, each given to the reference as raw Triangle[] and Sphere[] records (--kat-calc-raw).
+                         No geometry and no rays are stored, only their sha256: the tests rebuild them from that module
   loader/high_ns_obj.tris  loadOBJTriangles on an MTL with Ns 6250 and Ns 4000 (smoothness 2.5 and 2)
   render_golden.json     full renders (main.c render loop): sha256 of the pre-quantisation float
                          framebuffer and md5 of the BMP, per configuration
@@ -406,6 +410,15 @@ def gen_meta():
         with np.load(materials) as k:
             meta["kat_calc_materials_keys"] = sorted(k.files)
             meta["kat_calc_materials_scenes"] = [str(n) for n in k["names"]]
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from reference_calc import FAMILIES
+
+    for family in FAMILIES:
+        path = os.path.join(HERE, f"kat_ref_{family}.npz")
+        if os.path.exists(path):
+            with np.load(path) as k:
+                meta[f"kat_ref_{family}_keys"] = sorted(k.files)
+                meta[f"kat_ref_{family}_scenes"] = [str(n) for n in k["names"]]
     with open(os.path.join(HERE, "golden_meta.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
 
@@ -565,6 +578,45 @@ def gen_kat_calc_materials(work):
     save_npz(os.path.join(HERE, "kat_calc_materials.npz"), **arrays)
 
 
+def gen_kat_ref(work):
+    """calcColor / calcDebugColor of the reference on every case of tests/reference_calc.py, one file per family: the
+    cases one after another (names, counts = records per case, per case max_bounce and the sha256 of the Triangle[],
+    Sphere[] and Ray[] bytes the reference read), then the records' pixels, color, seed_after and, for the families with
+    calcDebugColor, debug_color and debug_seed_after, concatenated."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import reference_calc as rc
+
+    for family in rc.FAMILIES:
+        d = os.path.join(work, "ref_" + family)
+        os.makedirs(d)
+        modes = (0, 1) if family in rc.DEBUG_FAMILIES else (0,)
+        per_case = {k: [] for k in ("names", "counts", "max_bounce", "sha_tris", "sha_spheres", "sha_rays")}
+        records = {k: [] for k in ("pixels", "color", "seed_after", "debug_color", "debug_seed_after")[:1 + 2 * len(modes)]}
+        for case in rc.cases(family):
+            rays, seeds = rc.inputs(case)
+            ft, fs, fi = (os.path.join(d, n) for n in ("tris.bin", "spheres.bin", "calc.in"))
+            case.tris.tofile(ft)
+            case.spheres.tofile(fs)
+            kin = np.zeros(len(rays), np.dtype([("ray", RAY_DT), ("seed", "<u4"), ("mb", "<i4")]))
+            kin["ray"], kin["seed"], kin["mb"] = rays, seeds, case.max_bounce
+            kin.tofile(fi)
+            for debug in modes:
+                fo = os.path.join(d, "calc.out")
+                run_ref(["--kat-calc-raw", ft, fs, str(case.triangles_only), str(debug), fi, fo], d)
+                res = np.fromfile(fo, np.dtype([("color", "<f4", 3), ("seedAfter", "<u4")]))
+                assert len(res) == len(rays)
+                records["debug_color" if debug else "color"].append(res["color"])
+                records["debug_seed_after" if debug else "seed_after"].append(res["seedAfter"])
+            records["pixels"].append(case.pixels.astype(np.int32))
+            for k, v in zip(per_case, (case.name, len(rays), case.max_bounce) + rc.input_hashes(case, rays)):
+                per_case[k].append(v)
+        arrays = {k: np.array(v, np.int32 if k in ("counts", "max_bounce") else None) for k, v in per_case.items()}
+        arrays.update({k: np.concatenate(v) for k, v in records.items()})
+        path = os.path.join(HERE, f"kat_ref_{family}.npz")
+        save_npz(path, **arrays)
+        print(f"kat_ref_{family}: {len(arrays['names'])} cases, {len(arrays['pixels'])} records, {os.path.getsize(path)} bytes")
+
+
 def gen_loader_high_ns(work):
     """loadOBJTriangles (objloader.c: smoothness = sqrt(0.001 Ns), no clamp) on tests/test_scene_build.py's MTL with
     Ns 6250 and Ns 4000."""
@@ -593,6 +645,11 @@ def main():
             gen_loader_high_ns(work)
             gen_meta()
         return
+    if sys.argv[1:] == ["--ref-families"]:  # the kat_ref_* fixtures alone (no random draws; the others unchanged)
+        with tempfile.TemporaryDirectory() as work:
+            gen_kat_ref(work)
+            gen_meta()
+        return
     rng = np.random.default_rng(20251003)
     with tempfile.TemporaryDirectory() as work:
         # default mode reads ./triangles.txt (main.c:237): give the reference a private working dir
@@ -609,6 +666,7 @@ def main():
         gen_renders(work)
         gen_kat_env_edge(work)
         gen_kat_calc_materials(work)
+        gen_kat_ref(work)
         gen_loader_high_ns(work)
         gen_meta()
 

@@ -5,7 +5,8 @@ maxBounce).  Fixed arithmetic, no random draws.  The reference clamps none of th
 smoothness = sqrt(0.001 Ns) for any Ns, triangles.txt takes any decimal), so calcColor's arithmetic on them is part of
 what the kernels must reproduce bit for bit.  tests/test_material_scenes.py shows every claim of a note with the CPU oracle
 alone, tests/test_gpu_materials.py renders the frames on every route; tests/golden/kat_calc_materials.npz pins the oracle to
-the reference's own calcColor on the finite scenes.
+the reference's own calcColor on the finite scenes (through its text format) and kat_ref_materials.npz on every scene, the
+non-finite ones and the sphere scenes included (as raw records; tests/reference_calc.py).
 
 What the values reach (rtc_chain.h chain_trace_pairs, rtc_lane.h, rtc_sky.h):
   smoothness  ray.dir = lerp(diffuseDir, specularDir, smoothness) is not unit and extrapolates outside [0, 1]; reflect keeps
