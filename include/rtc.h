@@ -425,6 +425,41 @@ int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene, const Ray
  * back radiance[3 n], seedsOut[n] and *segments (the last two nullable).  The same refusals; RTC_ENODEV without a GPU. */
 int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds, size_t n,
                     const RtcPathDesc *d, float *radiance, unsigned int *seedsOut, unsigned long long *segments);
+/* Occlusion queries for caller-supplied rays, with a distance limit: "is anything in the way within tMax?"
+ * For ray i with L = dTMax[i] (a float in units of dir, like dst; dTMax == NULL: no limit, L = +inf),
+ *     occluded[i] = 1  iff  closest.didHit && closest.dst < L,  closest = calculateRayCollision(dRays[i], trianglesOnly)
+ * (raytracing.c:216-240), i.e. iff some primitive's raySphere / rayTriangle (:162-214) reports a hit with dst < L and
+ * dst < 999999.f; otherwise 0.  The byte is exactly 0 or 1.  The comparison is strict, in f32, on the reference's own dst
+ * bit for bit: L == closest.dst is not occluded, nextafterf(closest.dst, +inf) is.  A NaN L never compares true: NaN, +-0,
+ * negative and -inf limits give 0, and so does every L <= EPSILON (both reference tests report nothing below EPSILON;
+ * such a ray tests nothing).  L = +inf, and any L >= 999999.f, ask "does calculateRayCollision hit at all".
+ * The direction is used as given, exactly as rtc_trace_rays_async uses it: it is not normalised, dst and tMax are in
+ * units of dir, the EPSILON tests see the caller's scale, and zero, NaN and infinite components get what the reference's
+ * arithmetic gives.  Line of sight from a to b is therefore pos = a, dir = b - a, tMax = 1 (such a ray with |dir|_1 > 4
+ * is never ball-culled: it tests every cluster, like a ray query's).  rayTriangle is one-sided -- dot(dir, normal) >= 0
+ * is no hit (raytracing.c:189) -- and occlusion inherits that: a triangle seen from behind does not occlude.
+ * dRays: n Rays in DEVICE memory on the scene's device; dTMax: n floats there, or null.  dOccluded: n bytes there at ANY
+ * byte alignment, or null; the kernel writes exactly bytes [0, n), with byte stores only.  dCount: one device u64, or null;
+ * the launch atomically adds its number of occluded rays to it (one atomic per wave of 64 rays that has any), so a caller
+ * gets a visible fraction without moving n bytes.  At least one of the two is not null; the inputs alias no output.
+ * flags: 0 -- the cluster hierarchy with rtc_trace_rays_async's exact-safe half-line test per bounding ball (a ray of
+ * |dir|_1 > 4 tests every cluster); a wave of 64 rays stops as soon as each of its rays has found a hit;
+ * RTC_F_NO_CLUSTER_CULL -- every record in reference order, no ball test.  The same bytes and count under either.
+ * Asynchronous on `stream` and complete there, under rtc_trace_rays_async's rules word for word: it reads the generation
+ * current when it is enqueued, may come between RTC_F_OVERLAP launches, between passes and after an update, uses no
+ * scratch, primary record, counter set, stream or event of the scene's, leaves the one-shot events,
+ * rtc_scene_chain_report, rtc_scene_kernel_times and the draw cache as they were and restores the caller's current
+ * device.  n == 0: returns 0, nothing enqueued.
+ * RTC_EINVAL, with nothing enqueued, checked before any device call and before `s` is read: a null s or dRays; dOccluded
+ * and dCount both null; n > 0x7fffffff; a flag other than RTC_F_NO_CLUSTER_CULL. */
+int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *dTMax /* nullable */, size_t n,
+                       int trianglesOnly, int flags, unsigned char *dOccluded /* nullable */,
+                       unsigned long long *dCount /* nullable */, void *stream);
+/* The same for HOST arrays, synchronous, built like rtc_trace_rays: stages the rays and limits (tMax nullable: none) and
+ * the counter's value, waits for the device, runs the query on the null stream and copies back occluded[n] and *count
+ * (each nullable, not both; *count += the occluded rays).  The same refusals; RTC_ENODEV without a GPU. */
+int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly, int flags,
+                 unsigned char *occluded, unsigned long long *count);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */
@@ -519,6 +554,16 @@ int rtc_plan_sim_trace_paths(RtcPlanSim *sim, unsigned long long stream, unsigne
                              unsigned long long seeds, unsigned long long radiance, unsigned long long seedsOut,
                              unsigned long long segments, int sampleFirst, int flags, int *ops, int maxOps,
                              unsigned long long *footprint, int maxFootprint);
+/* Plans one rtc_occluded_async on the caller's stream `stream`, in rtc_plan_sim_trace_rays's encodings: one kernel op
+ * (kernel 13, stream 0, no event) with its footprint records -- it reads the current generation (resource 9), the ray
+ * buffer (resource 11, id = `rays`) and, where given (an identity that is not 0), the limits (resource 16, id = `tMax`),
+ * writes the bytes (resource 17, id = `occluded`) and adds to the caller's counter (resource 7, an atomic add) where asked
+ * for, in that order -- then one u64 record (~0, 0, the generation read, 0, 0, 0).  The planner's state is left as it
+ * was.  RTC_EINVAL where the entry point refuses: `rays` 0, `occluded` and `count` both 0, a flag other than
+ * RTC_F_NO_CLUSTER_CULL. */
+int rtc_plan_sim_occluded(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays, unsigned long long tMax,
+                          unsigned long long occluded, unsigned long long count, int flags, int *ops, int maxOps,
+                          unsigned long long *footprint, int maxFootprint);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the

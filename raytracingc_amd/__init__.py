@@ -481,6 +481,77 @@ class DeviceScene:
             res["segments"] = int(seg.value)
         return res
 
+    def occluded_async(self, rays_ptr: int, n: int, tmax_ptr: int = 0, triangles_only: bool = False, flags: int = 0,
+                       occluded_ptr: int = 0, count_ptr: int = 0, stream: int | None = None):
+        """rtc_occluded_async: for n caller-supplied Rays (device memory at rays_ptr) and their limits (float32 [n] at
+        tmax_ptr, in units of dir; 0: no limit), whether calculateRayCollision(ray, trianglesOnly) hits with
+        dst < tMax (strict, on the reference's own dst): one byte per ray, 0 or 1, at occluded_ptr (any alignment; 0: not
+        wanted) and / or the number of occluded rays added to the u64 at count_ptr (0: not wanted); at least one.  The
+        direction is used as given: line of sight from a to b is pos = a, dir = b - a, tMax = 1.  flags: 0 or
+        RTC_F_NO_CLUSTER_CULL (every record; the same answers).  Asynchronous on `stream`, complete there; the scene's ordering state and events stay as they were."""
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        check(lib().rtc_occluded_async(self._h, vp(rays_ptr), vp(tmax_ptr), n, int(bool(triangles_only)), int(flags),
+                                       vp(occluded_ptr), vp(count_ptr), vp(stream)), "rtc_occluded_async")
+
+    def occluded(self, rays, tmax=None, triangles_only: bool = False, flags: int = 0, count: bool = False):
+        """occluded_async's answers as a numpy bool [n], or (bool [n], int) with count=True (the number of occluded rays,
+        counted by the kernel).  `rays`: a numpy array of RAY_DT [n] or float32 [n, 6] (pos, dir), which takes the
+        synchronous host entry rtc_occluded; or a torch tensor on the scene's device (float32 [n, 6], or any contiguous
+        tensor of n x 24 bytes), read in place by rtc_occluded_async on torch's current stream there.  `tmax`: None (no
+        limit), a Python float (the same limit for every ray) or an array / tensor of n float32."""
+        who = "DeviceScene.occluded"
+        on_device = hasattr(rays, "data_ptr")
+        if on_device:
+            nbytes = rays.numel() * rays.element_size()
+            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
+                raise ValueError(f"{who}: rays must be a contiguous device tensor of whole 24-byte Rays")
+            n = nbytes // RAY_DT.itemsize
+        else:
+            a = np.asarray(rays)
+            if a.dtype != RAY_DT:
+                if a.ndim != 2 or a.shape[1] != 6:
+                    raise ValueError(f"{who}: rays must be RAY_DT [n] or float32 [n, 6]")
+                a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
+            a = np.ascontiguousarray(a.reshape(-1))
+            n = len(a)
+        lim = None
+        if tmax is not None:
+            if hasattr(tmax, "data_ptr"):  # a tensor: beside device rays it is read in place where it can be
+                if tmax.numel() != n:
+                    raise ValueError(f"{who}: {tmax.numel()} limits for {n} rays")
+                lim = tmax.reshape(-1) if on_device else np.ascontiguousarray(tmax.detach().cpu().numpy().reshape(-1),
+                                                                              np.float32)
+            else:
+                t = np.asarray(tmax, np.float32)
+                if t.ndim == 0:
+                    t = np.full(n, t, np.float32)
+                if t.size != n:
+                    raise ValueError(f"{who}: {t.size} limits for {n} rays")
+                lim = np.ascontiguousarray(t.reshape(-1))
+        if n == 0:
+            return (np.zeros(0, bool), 0) if count else np.zeros(0, bool)
+        if on_device:
+            import torch
+
+            with torch.cuda.device(rays.device):
+                if lim is not None:
+                    if isinstance(lim, np.ndarray):
+                        lim = torch.from_numpy(lim.copy())  # (a copy: the caller's array may be read-only)
+                    lim = lim.to(device=rays.device, dtype=torch.float32).contiguous()
+                occ = torch.zeros(n, dtype=torch.uint8, device=rays.device)
+                cnt = torch.zeros(1, dtype=torch.int64, device=rays.device)
+                st = torch.cuda.current_stream().cuda_stream
+                self.occluded_async(rays.data_ptr(), n, lim.data_ptr() if lim is not None else 0, triangles_only, flags,
+                                    occ.data_ptr(), cnt.data_ptr() if count else 0, stream=st)
+                torch.cuda.current_stream().synchronize()
+            res = occ.cpu().numpy().astype(bool)
+            return (res, int(cnt.cpu().numpy()[0])) if count else res
+        occ = np.zeros(n, np.uint8)
+        cnt = C.c_ulonglong(0)
+        check(lib().rtc_occluded(self._h, _ptr(a), _ptr(lim), n, int(bool(triangles_only)), int(flags), _ptr(occ),
+                                 C.cast(C.pointer(cnt), C.c_void_p) if count else None), "rtc_occluded")
+        return (occ.astype(bool), int(cnt.value)) if count else occ.astype(bool)
+
     def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
         """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with
         `state` -- a frame saved earlier, load_progress -- to the samples it still lacks).  It owns the three device

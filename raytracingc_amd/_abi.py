@@ -171,6 +171,7 @@ EXPORTS = [
     "rtc_scene_set_draw_cache", "rtc_scene_draw_cache_reset", "rtc_scene_draw_cache_stats", "rtc_probe_draw_cache",
     "rtc_plan_sim_set_draw_cache",
     "rtc_trace_paths_async", "rtc_trace_paths", "rtc_plan_sim_trace_paths",
+    "rtc_occluded_async", "rtc_occluded", "rtc_plan_sim_occluded",
 ]
 
 _lib = None
@@ -297,6 +298,11 @@ def lib() -> C.CDLL:
         L.rtc_trace_paths.argtypes = [vp, C.POINTER(Scene), vp, vp, sz, C.POINTER(RtcPathDesc), vp, vp, vp]
         L.rtc_plan_sim_trace_paths.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
                                                C.c_ulonglong, C.c_ulonglong, ip, ip, vp, ip, vp, ip]
+    if hasattr(L, "rtc_occluded_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_occluded_async.argtypes = [vp, vp, vp, sz, ip, ip, vp, vp, vp]
+        L.rtc_occluded.argtypes = [vp, vp, vp, sz, ip, ip, vp, vp]
+        L.rtc_plan_sim_occluded.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
+                                            C.c_ulonglong, ip, vp, ip, vp, ip]
     _lib = L
     return L
 

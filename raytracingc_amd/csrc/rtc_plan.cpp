@@ -566,6 +566,34 @@ int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t 
     return k;
 }
 
+void plan_occluded(const State &s, TracePlan &t)
+{
+    memset(&t, 0, sizeof t);
+    t.after = s; /* nothing the planner keeps changes */
+    t.gen = s.gen;
+    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKOccluded};
+}
+
+int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_t occluded, bool count, Footprint *out,
+                       int max)
+{
+    int k = 0;
+    const auto row = [&](int res, int access, unsigned long long id) {
+        if (k < max)
+            out[k] = Footprint{res, access, id, 0, 1};
+        ++k;
+    };
+    row(kResSceneGen, kRead, (unsigned long long)t.gen);
+    row(kResRays, kRead, rays);
+    if (tMax)
+        row(kResTMax, kRead, tMax);
+    if (occluded)
+        row(kResOccluded, kWrite, occluded);
+    if (count)
+        row(kResCallerSegments, kAtomic, 0);
+    return k;
+}
+
 } // namespace rtcplan
 
 /* ---- the CPU test hook (include/rtc.h rtc_plan_sim_*) ---------------------------------------------------------- */
@@ -784,6 +812,37 @@ extern "C" int rtc_plan_sim_trace_paths(RtcPlanSim *s, unsigned long long stream
         ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
         rtcplan::Footprint f[7];
         const int k = rtcplan::paths_footprint(t, rays, seeds, radiance, seedsOut, segments != 0, sampleFirst > 0, f, 7);
+        for (int j = 0; j < k; ++j, ++nf)
+            if (fp && nf < maxFp) {
+                unsigned long long *q = fp + 6 * (size_t)nf;
+                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
+                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
+            }
+    }
+    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation read, -, -, -) */
+        unsigned long long *q = fp + 6 * (size_t)nf;
+        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)t.gen, q[3] = q[4] = q[5] = 0;
+    }
+    return t.nOps | ((nf + 1) << 8);
+}
+
+extern "C" int rtc_plan_sim_occluded(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,
+                                     unsigned long long tMax, unsigned long long occluded, unsigned long long count,
+                                     int flags, int *ops, int maxOps, unsigned long long *fp, int maxFp)
+{
+    /* refused as rtc_occluded_async refuses it */
+    if (!s || !ops || !rays || !(occluded | count) || (flags & ~RTC_F_NO_CLUSTER_CULL))
+        return RTC_EINVAL;
+    (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
+    rtcplan::TracePlan t;
+    rtcplan::plan_occluded(s->st, t);
+    s->st = t.after;
+    int nf = 0;
+    for (int i = 0; i < t.nOps && i < maxOps; ++i) {
+        const rtcplan::Op &o = t.ops[i];
+        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
+        rtcplan::Footprint f[5];
+        const int k = rtcplan::occluded_footprint(t, rays, tMax, occluded, count != 0, f, 5);
         for (int j = 0; j < k; ++j, ++nf)
             if (fp && nf < maxFp) {
                 unsigned long long *q = fp + 6 * (size_t)nf;

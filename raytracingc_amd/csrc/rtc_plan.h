@@ -63,8 +63,9 @@ enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kK
                     kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */,
                     kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */,
                     kKTraceRays /* rtc_trace_rays_async's kernel (plan_trace_rays); never part of a launch */,
-                    kKTracePaths /* rtc_trace_paths_async's kernel (plan_trace_paths); never part of a launch */ };
-static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12,
+                    kKTracePaths /* rtc_trace_paths_async's kernel (plan_trace_paths); never part of a launch */,
+                    kKOccluded /* rtc_occluded_async's kernel (plan_occluded); never part of a launch */ };
+static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12 && kKOccluded == 13,
               "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
@@ -256,7 +257,8 @@ enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3,
                  kResAccum = 6, kResCallerSegments = 7, kResRngState = 8, kResSceneGen = 9 /* id: the generation */,
                  kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */,
                  kResDrawTable = 12, kResItemDraw = 13 /* id: the slot */,
-                 kResSeeds = 14 /* id: the caller's seed buffer */, kResRadiance = 15 /* id: the caller's buffer */ };
+                 kResSeeds = 14 /* id: the caller's seed buffer */, kResRadiance = 15 /* id: the caller's buffer */,
+                 kResTMax = 16 /* id: the caller's limit buffer */, kResOccluded = 17 /* id: the caller's byte buffer */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -308,5 +310,15 @@ void plan_trace_paths(const State &s, TracePlan &t);
  * for; id 0 as in a launch's footprint) */
 int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t radiance, uint64_t seedsOut, bool segments,
                     bool readRadiance, Footprint *out, int max);
+
+/* One rtc_occluded_async: plan_trace_rays's plan with the occlusion kernel -- one kernel on the caller's
+ * stream, nothing of the scene's beyond the records of the current generation, `after` equal to the state it was planned
+ * from. */
+void plan_occluded(const State &s, TracePlan &t);
+/* the kernel's footprint, in this order: the generation read, the rays read, the limits read (ids: the buffers; tMax 0:
+ * none given), the bytes written (id: the buffer; 0: not asked for) and the caller's counter added to atomically (when
+ * asked for; resource 7 with id 0, as in a launch's footprint) */
+int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_t occluded, bool count, Footprint *out,
+                       int max);
 
 } // namespace rtcplan

@@ -101,6 +101,7 @@ extern "C" int rtc_device_count(int *count)
 #include "rtc_first_hit.h"
 #include "rtc_trace_rays.h"
 #include "rtc_trace_paths.h"
+#include "rtc_occluded.h"
 
 /* A kernel launch whose completion also records `stop` (null: a plain launch): the event is the dispatch's own
  * completion signal, so the stream gets no separate marker packet -- each marker on the launch stream cost ~5-7 us
@@ -878,6 +879,106 @@ extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, cons
     return rc;
 }
 
+/* ---- caller-supplied rays: occlusion within a distance limit -------------------------------------- */
+/* the refusals of rtc_occluded_async and rtc_occluded, before any device call and before `s` is read */
+static int check_occluded(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
+                          const void *occluded, const void *count)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
+    if (!rays)
+        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
+    if (!occluded && !count)
+        return rtc_fail(RTC_EINVAL, "%s: no output asked for (occluded and count are both null)", who);
+    if (n > (size_t)0x7fffffff)
+        return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
+    if (flags & ~RTC_F_NO_CLUSTER_CULL)
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (an occlusion query takes RTC_F_NO_CLUSTER_CULL and no other flag)",
+                        who, flags);
+    return 0;
+}
+
+extern "C" int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *dTMax, size_t n,
+                                  int trianglesOnly, int flags, unsigned char *dOccluded, unsigned long long *dCount,
+                                  void *stream)
+{
+    const char *const who = "rtc_occluded_async";
+    if (const int rc = check_occluded(who, s, dRays, n, flags, dOccluded, dCount))
+        return rc;
+    if (n == 0)
+        return 0;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* as rtc_trace_rays_async: the planner names the generation and the one operation (rtc_plan.h plan_occluded), and
+     * the ordering state, the hooks, the timing events, the chain report and the draw cache stay as they are */
+    rtcplan::TracePlan tp;
+    rtcplan::plan_occluded(s->plan, tp);
+    const SceneRecords &g = s->gen[tp.gen];
+    OccludedArgs a{};
+    a.tris = g.tris, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters, a.chunks = g.chunks;
+    a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
+    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
+    a.rays = (const float *)dRays, a.tMax = dTMax, a.n = (unsigned)n;
+    a.occluded = dOccluded, a.count = dCount;
+    /* <SPHERES, CULL> */
+    static void (*const kOccluded[2][2])(OccludedArgs) = {{rtc_occluded<false, false>, rtc_occluded<false, true>},
+                                                          {rtc_occluded<true, false>, rtc_occluded<true, true>}};
+    for (int i = 0; i < tp.nOps; ++i) {
+        const rtcplan::Op &op = tp.ops[i];
+        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKOccluded || op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
+        hipLaunchKernelGGL(kOccluded[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
+                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly,
+                            int flags, unsigned char *occluded, unsigned long long *count)
+{
+    const char *const who = "rtc_occluded";
+    if (const int rc = check_occluded(who, s, rays, n, flags, occluded, count))
+        return rc;
+    if (n == 0)
+        return 0;
+    int devices = 0;
+    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
+        return rc;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* staged through device buffers on the null stream, like rtc_trace_rays; the counter starts at the caller's value */
+    const size_t bytes[4] = {n * sizeof(Ray), n * sizeof(float), n, sizeof(unsigned long long)};
+    const void *const in[4] = {rays, tMax, nullptr, count};
+    void *const out[4] = {nullptr, nullptr, occluded, count};
+    const bool want[4] = {true, tMax != nullptr, occluded != nullptr, count != nullptr};
+    void *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4; ++k) {
+        if (e == hipSuccess && want[k])
+            e = hipMalloc(&dev[k], bytes[k]);
+        if (e == hipSuccess && want[k] && in[k])
+            e = hipMemcpy(dev[k], in[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    int rc = e == hipSuccess ? rtc_occluded_async(s, (const Ray *)dev[0], (const float *)dev[1], n, trianglesOnly, flags,
+                                                  (unsigned char *)dev[2], (unsigned long long *)dev[3], nullptr)
+                             : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
+    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (int k = 0; k < 4; ++k)
+        if (rc == 0 && dev[k] && out[k] && (e = hipMemcpy(out[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (void *p : dev)
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items)
 {
@@ -1035,3 +1136,8 @@ template __global__ void rtc_trace_paths<false, true>(TracePathsArgs);
 template __global__ void rtc_trace_paths<true, true>(TracePathsArgs);
 template __global__ void rtc_trace_paths<false, false>(TracePathsArgs);
 template __global__ void rtc_trace_paths<true, false>(TracePathsArgs);
+/* caller-supplied rays: occlusion */
+template __global__ void rtc_occluded<false, true>(OccludedArgs);
+template __global__ void rtc_occluded<true, true>(OccludedArgs);
+template __global__ void rtc_occluded<false, false>(OccludedArgs);
+template __global__ void rtc_occluded<true, false>(OccludedArgs);
