@@ -15,6 +15,7 @@ There is no CPU fallback: every render call goes to the GPU and raises if librtc
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -194,6 +195,41 @@ def _stats(st: RtcStats) -> dict:
             "discarded_tests": st.discardedTests}
 
 
+def _vp(p):
+    """An address (int; 0 or None: null) as the void pointer ctypes passes."""
+    return C.c_void_p(p) if p else None
+
+
+def _query_rays(who: str, rays):
+    """The rays of a query (DeviceScene.trace_rays, trace_paths, occluded) as (on_device, rays, n): a torch tensor on a
+    device is read in place, any contiguous one of n x 24 bytes; anything else becomes a contiguous numpy array of
+    RAY_DT [n], from RAY_DT [n] or float32 [n, 6]."""
+    if hasattr(rays, "data_ptr"):
+        nbytes = rays.numel() * rays.element_size()
+        if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
+            raise ValueError(f"{who}: rays must be a contiguous device tensor of whole 24-byte Rays")
+        return True, rays, nbytes // RAY_DT.itemsize
+    a = np.asarray(rays)
+    if a.dtype != RAY_DT:
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError(f"{who}: rays must be RAY_DT [n] or float32 [n, 6]")
+        a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
+    a = np.ascontiguousarray(a.reshape(-1))
+    return False, a, len(a)
+
+
+@contextlib.contextmanager
+def _current_stream_of(device):
+    """`device` made torch's current one: yields its current stream there (the hipStream_t as an int) and synchronises
+    that stream once the block has enqueued its work."""
+    import torch
+
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream()
+        yield st.cuda_stream
+        st.synchronize()
+
+
 RECORD_ARRAYS = ("tris", "mats", "spheres", "clTris", "clusters", "chunks")  # 64, 32, 48, 64, 32, 32 bytes per record
 _RECORD_WORDS = (16, 8, 12, 16, 8, 8)
 
@@ -332,10 +368,8 @@ class DeviceScene:
         bufs = {k: torch.zeros((rows, cfg.width) + shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
         if rows == 0:  # (nothing selected: the empty tensors have no address to hand over)
             return {k: bufs[k].cpu().numpy() for k in want}
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
+        with _current_stream_of(dev) as st:
             self.render_first_hit_async(cam, cfg, *(bufs[k].data_ptr() if k in bufs else 0 for k in shapes), stream=st)
-            torch.cuda.current_stream().synchronize()
         return {k: bufs[k].cpu().numpy() for k in want}
 
     def trace_rays_async(self, rays_ptr: int, n: int, triangles_only: bool = False, flags: int = 0, prim_ptr: int = 0,
@@ -347,9 +381,8 @@ class DeviceScene:
         direction is used as given (not normalised).  flags: 0 or RTC_F_NO_CLUSTER_CULL (every record, the same
         buffers).  Asynchronous on `stream`, complete there; the scene's ordering state and events stay as they were."""
         out = RtcHitBuffers(prim_ptr or None, depth_ptr or None, normal_ptr or None, albedo_ptr or None)
-        check(lib().rtc_trace_rays_async(self._h, C.c_void_p(rays_ptr) if rays_ptr else None, n, int(bool(triangles_only)),
-                                         flags, C.byref(out), C.c_void_p(stream) if stream else None),
-              "rtc_trace_rays_async")
+        check(lib().rtc_trace_rays_async(self._h, _vp(rays_ptr), n, int(bool(triangles_only)), flags, C.byref(out),
+                                         _vp(stream)), "rtc_trace_rays_async")
 
     def trace_rays(self, rays, triangles_only: bool = False, want=("prim", "depth", "normal", "albedo"),
                    flags: int = 0) -> dict:
@@ -363,29 +396,17 @@ class DeviceScene:
         want = tuple(want)
         if not want or any(k not in shapes for k in want):
             raise ValueError(f"DeviceScene.trace_rays: want {want!r} is not a non-empty subset of {tuple(shapes)}")
-        if hasattr(rays, "data_ptr"):
+        on_device, a, n = _query_rays("DeviceScene.trace_rays", rays)
+        if on_device:
             import torch
 
-            nbytes = rays.numel() * rays.element_size()
-            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
-                raise ValueError("DeviceScene.trace_rays: rays must be a contiguous device tensor of whole 24-byte Rays")
-            n = nbytes // RAY_DT.itemsize
             kinds = {np.int32: torch.int32, np.float32: torch.float32}
             bufs = {k: torch.zeros((n,) + shapes[k][0], dtype=kinds[shapes[k][1]], device=rays.device) for k in want}
             if n:
-                with torch.cuda.device(rays.device):
-                    st = torch.cuda.current_stream().cuda_stream
+                with _current_stream_of(rays.device) as st:
                     self.trace_rays_async(rays.data_ptr(), n, triangles_only, flags,
                                           *(bufs[k].data_ptr() if k in bufs else 0 for k in shapes), stream=st)
-                    torch.cuda.current_stream().synchronize()
             return {k: bufs[k].cpu().numpy() for k in want}
-        a = np.asarray(rays)
-        if a.dtype != RAY_DT:
-            if a.ndim != 2 or a.shape[1] != 6:
-                raise ValueError("DeviceScene.trace_rays: rays must be RAY_DT [n] or float32 [n, 6]")
-            a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
-        a = np.ascontiguousarray(a.reshape(-1))
-        n = len(a)
         out = {k: np.zeros((n,) + shapes[k][0], shapes[k][1]) for k in want}
         if n:
             check(lib().rtc_trace_rays(self._h, _ptr(a), n, int(bool(triangles_only)), flags,
@@ -405,9 +426,8 @@ class DeviceScene:
         events stay as they were."""
         d = RtcPathDesc(int(spp), int(max_bounce), int(bool(triangles_only)), int(flags), int(first),
                         int(spp) - int(first) if count is None else int(count))
-        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        check(lib().rtc_trace_paths_async(self._h, C.byref(scene), vp(rays_ptr), vp(seeds_ptr), n, C.byref(d),
-                                          vp(radiance_ptr), vp(seeds_out_ptr), vp(segments_ptr), vp(stream)),
+        check(lib().rtc_trace_paths_async(self._h, C.byref(scene), _vp(rays_ptr), _vp(seeds_ptr), n, C.byref(d),
+                                          _vp(radiance_ptr), _vp(seeds_out_ptr), _vp(segments_ptr), _vp(stream)),
               "rtc_trace_paths_async")
 
     def trace_paths(self, rays, seeds, scene: Scene, spp: int, max_bounce: int, triangles_only: bool = False,
@@ -423,13 +443,10 @@ class DeviceScene:
         count = int(spp) - int(first) if count is None else int(count)
         if first > 0 and radiance is None:
             raise ValueError("DeviceScene.trace_paths: first > 0 continues an accumulation: pass its radiance")
-        if hasattr(rays, "data_ptr"):
+        on_device, a, n = _query_rays("DeviceScene.trace_paths", rays)
+        if on_device:
             import torch
 
-            nbytes = rays.numel() * rays.element_size()
-            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
-                raise ValueError("DeviceScene.trace_paths: rays must be a contiguous device tensor of whole 24-byte Rays")
-            n = nbytes // RAY_DT.itemsize
             if not hasattr(seeds, "data_ptr") or seeds.device != rays.device or not seeds.is_contiguous() or \
                     seeds.numel() * seeds.element_size() != 4 * n:
                 raise ValueError("DeviceScene.trace_paths: seeds must be a contiguous tensor of n 4-byte words on the rays' device")
@@ -443,24 +460,15 @@ class DeviceScene:
             out = torch.zeros(n, dtype=torch.int32, device=rays.device)
             seg = torch.zeros(1, dtype=torch.int64, device=rays.device)
             if n:
-                with torch.cuda.device(rays.device):
-                    st = torch.cuda.current_stream().cuda_stream
+                with _current_stream_of(rays.device) as st:
                     self.trace_paths_async(scene, rays.data_ptr(), seeds.data_ptr(), n, spp, max_bounce, rad.data_ptr(),
                                            triangles_only, flags, first, count, out.data_ptr(),
                                            seg.data_ptr() if segments else 0, stream=st)
-                    torch.cuda.current_stream().synchronize()
             res = {"radiance": rad.cpu().numpy(), "seeds": out.cpu().numpy().view(np.uint32)}
             if segments:
                 res["segments"] = int(seg.cpu().numpy()[0])
             return res
-        a = np.asarray(rays)
-        if a.dtype != RAY_DT:
-            if a.ndim != 2 or a.shape[1] != 6:
-                raise ValueError("DeviceScene.trace_paths: rays must be RAY_DT [n] or float32 [n, 6]")
-            a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
-        a = np.ascontiguousarray(a.reshape(-1))
-        n = len(a)
-        sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.uint32)
+        sd =np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.uint32)
         if len(sd) != n:
             raise ValueError(f"DeviceScene.trace_paths: {len(sd)} seeds for {n} rays")
         if first > 0:
@@ -489,9 +497,8 @@ class DeviceScene:
         wanted) and / or the number of occluded rays added to the u64 at count_ptr (0: not wanted); at least one.  The
         direction is used as given: line of sight from a to b is pos = a, dir = b - a, tMax = 1.  flags: 0 or
         RTC_F_NO_CLUSTER_CULL (every record; the same answers).  Asynchronous on `stream`, complete there; the scene's ordering state and events stay as they were."""
-        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        check(lib().rtc_occluded_async(self._h, vp(rays_ptr), vp(tmax_ptr), n, int(bool(triangles_only)), int(flags),
-                                       vp(occluded_ptr), vp(count_ptr), vp(stream)), "rtc_occluded_async")
+        check(lib().rtc_occluded_async(self._h, _vp(rays_ptr), _vp(tmax_ptr), n, int(bool(triangles_only)), int(flags),
+                                       _vp(occluded_ptr), _vp(count_ptr), _vp(stream)), "rtc_occluded_async")
 
     def occluded(self, rays, tmax=None, triangles_only: bool = False, flags: int = 0, count: bool = False):
         """occluded_async's answers as a numpy bool [n], or (bool [n], int) with count=True (the number of occluded rays,
@@ -500,20 +507,7 @@ class DeviceScene:
         tensor of n x 24 bytes), read in place by rtc_occluded_async on torch's current stream there.  `tmax`: None (no
         limit), a Python float (the same limit for every ray) or an array / tensor of n float32."""
         who = "DeviceScene.occluded"
-        on_device = hasattr(rays, "data_ptr")
-        if on_device:
-            nbytes = rays.numel() * rays.element_size()
-            if not rays.is_cuda or not rays.is_contiguous() or nbytes % RAY_DT.itemsize:
-                raise ValueError(f"{who}: rays must be a contiguous device tensor of whole 24-byte Rays")
-            n = nbytes // RAY_DT.itemsize
-        else:
-            a = np.asarray(rays)
-            if a.dtype != RAY_DT:
-                if a.ndim != 2 or a.shape[1] != 6:
-                    raise ValueError(f"{who}: rays must be RAY_DT [n] or float32 [n, 6]")
-                a = np.ascontiguousarray(a, np.float32).view(RAY_DT).reshape(-1)
-            a = np.ascontiguousarray(a.reshape(-1))
-            n = len(a)
+        on_device, a, n = _query_rays(who, rays)
         lim = None
         if tmax is not None:
             if hasattr(tmax, "data_ptr"):  # a tensor: beside device rays it is read in place where it can be
@@ -533,17 +527,15 @@ class DeviceScene:
         if on_device:
             import torch
 
-            with torch.cuda.device(rays.device):
+            with _current_stream_of(rays.device) as st:
                 if lim is not None:
                     if isinstance(lim, np.ndarray):
                         lim = torch.from_numpy(lim.copy())  # (a copy: the caller's array may be read-only)
                     lim = lim.to(device=rays.device, dtype=torch.float32).contiguous()
                 occ = torch.zeros(n, dtype=torch.uint8, device=rays.device)
                 cnt = torch.zeros(1, dtype=torch.int64, device=rays.device)
-                st = torch.cuda.current_stream().cuda_stream
                 self.occluded_async(rays.data_ptr(), n, lim.data_ptr() if lim is not None else 0, triangles_only, flags,
                                     occ.data_ptr(), cnt.data_ptr() if count else 0, stream=st)
-                torch.cuda.current_stream().synchronize()
             res = occ.cpu().numpy().astype(bool)
             return (res, int(cnt.cpu().numpy()[0])) if count else res
         occ = np.zeros(n, np.uint8)

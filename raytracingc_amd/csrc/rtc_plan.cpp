@@ -512,86 +512,63 @@ int update_footprint(const UpdatePlan &u, Footprint *out, int max)
     return 2;
 }
 
-void plan_trace_rays(const State &s, TracePlan &t)
+void plan_query(const State &s, int kernel, TracePlan &t)
 {
     memset(&t, 0, sizeof t);
     t.after = s; /* nothing the planner keeps changes */
     t.gen = s.gen;
-    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKTraceRays};
+    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kernel};
+}
+
+int query_footprint(const TracePlan &t, std::initializer_list<QueryRow> rows, Footprint *out, int max)
+{
+    int k = 0;
+    const auto row = [&](const QueryRow &r) {
+        if (!r.present)
+            return;
+        if (k < max)
+            out[k] = Footprint{r.res, r.access, r.id, 0, 1};
+        ++k;
+    };
+    row({kResSceneGen, kRead, (unsigned long long)t.gen, true});
+    for (const QueryRow &r : rows)
+        row(r);
+    return k;
 }
 
 int trace_footprint(const TracePlan &t, uint64_t rays, const uint64_t hit[4], Footprint *out, int max)
 {
-    int k = 0;
-    const auto row = [&](int res, int access, unsigned long long id) {
-        if (k < max)
-            out[k] = Footprint{res, access, id, 0, 1};
-        ++k;
-    };
-    row(kResSceneGen, kRead, (unsigned long long)t.gen);
-    row(kResRays, kRead, rays);
-    for (int b = 0; b < 4; ++b)
-        if (hit[b])
-            row(kResHit, kWrite, hit[b]);
-    return k;
-}
-
-void plan_trace_paths(const State &s, TracePlan &t)
-{
-    memset(&t, 0, sizeof t);
-    t.after = s; /* nothing the planner keeps changes */
-    t.gen = s.gen;
-    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKTracePaths};
+    return query_footprint(t,
+                           {{kResRays, kRead, rays, true},
+                            {kResHit, kWrite, hit[0], hit[0] != 0},
+                            {kResHit, kWrite, hit[1], hit[1] != 0},
+                            {kResHit, kWrite, hit[2], hit[2] != 0},
+                            {kResHit, kWrite, hit[3], hit[3] != 0}},
+                           out, max);
 }
 
 int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t radiance, uint64_t seedsOut, bool segments,
                     bool readRadiance, Footprint *out, int max)
 {
-    int k = 0;
-    const auto row = [&](int res, int access, unsigned long long id) {
-        if (k < max)
-            out[k] = Footprint{res, access, id, 0, 1};
-        ++k;
-    };
-    row(kResSceneGen, kRead, (unsigned long long)t.gen);
-    row(kResRays, kRead, rays);
-    row(kResSeeds, kRead, seeds);
-    if (readRadiance)
-        row(kResRadiance, kRead, radiance);
-    row(kResRadiance, kWrite, radiance);
-    if (seedsOut)
-        row(kResSeeds, kWrite, seedsOut);
-    if (segments)
-        row(kResCallerSegments, kAtomic, 0);
-    return k;
-}
-
-void plan_occluded(const State &s, TracePlan &t)
-{
-    memset(&t, 0, sizeof t);
-    t.after = s; /* nothing the planner keeps changes */
-    t.gen = s.gen;
-    t.ops[t.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKOccluded};
+    return query_footprint(t,
+                           {{kResRays, kRead, rays, true},
+                            {kResSeeds, kRead, seeds, true},
+                            {kResRadiance, kRead, radiance, readRadiance},
+                            {kResRadiance, kWrite, radiance, true},
+                            {kResSeeds, kWrite, seedsOut, seedsOut != 0},
+                            {kResCallerSegments, kAtomic, 0, segments}},
+                           out, max);
 }
 
 int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_t occluded, bool count, Footprint *out,
                        int max)
 {
-    int k = 0;
-    const auto row = [&](int res, int access, unsigned long long id) {
-        if (k < max)
-            out[k] = Footprint{res, access, id, 0, 1};
-        ++k;
-    };
-    row(kResSceneGen, kRead, (unsigned long long)t.gen);
-    row(kResRays, kRead, rays);
-    if (tMax)
-        row(kResTMax, kRead, tMax);
-    if (occluded)
-        row(kResOccluded, kWrite, occluded);
-    if (count)
-        row(kResCallerSegments, kAtomic, 0);
-    return k;
+    return query_footprint(t,
+                           {{kResRays, kRead, rays, true},
+                            {kResTMax, kRead, tMax, tMax != 0},
+                            {kResOccluded, kWrite, occluded, occluded != 0},
+                            {kResCallerSegments, kAtomic, 0, count}},
+                           out, max);
 }
 
 } // namespace rtcplan
@@ -610,6 +587,50 @@ struct RtcPlanSim {
     uint64_t hit[4];
     bool drawCache;  /* rtc_plan_sim_set_draw_cache: the scene has a draw cache and may use it in every launch shape */
 };
+
+namespace {
+/* What every rtc_plan_sim_* hook hands back.  ops: 4 ints each (kind, stream, event, kernel), at most maxOps of them.  fp:
+ * 6 u64 per row, at most maxFp rows, none when fp is null -- per kernel op written, its footprint entries (op index, res,
+ * access, id, lo, hi: `footprint` fills at most `max` Footprints and returns how many there are), then the hook's trailer
+ * (~0 and its five values).  Returns nOps | (rows, the trailer included) << 8, whatever fitted. */
+template <class FootprintOf>
+int serialise(const rtcplan::Op *o, int nOps, int *ops, int maxOps, unsigned long long *fp, int maxFp,
+              const unsigned long long (&trailer)[5], FootprintOf footprint)
+{
+    int nf = 0;
+    for (int i = 0; i < nOps && i < maxOps; ++i) {
+        ops[4 * i] = o[i].kind, ops[4 * i + 1] = o[i].stream, ops[4 * i + 2] = o[i].event, ops[4 * i + 3] = o[i].kernel;
+        if (o[i].kind != rtcplan::kOpKernel)
+            continue;
+        rtcplan::Footprint f[24];
+        const int k = std::min(footprint(o[i], f, 24), 24);
+        for (int j = 0; j < k; ++j, ++nf)
+            if (fp && nf < maxFp) {
+                unsigned long long *q = fp + 6 * (size_t)nf;
+                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
+                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
+            }
+    }
+    if (fp && nf < maxFp) {
+        unsigned long long *q = fp + 6 * (size_t)nf;
+        q[0] = ~0ull;
+        std::copy(trailer, trailer + 5, q + 1);
+    }
+    return nOps | ((nf + 1) << 8);
+}
+
+/* a query, once its hook has refused what its entry point refuses: planned, the state adopted, and handed back with the
+ * trailer (~0, nothing regrown, the generation read, -, -, -) */
+template <class FootprintOf>
+int sim_query(RtcPlanSim *s, int kernel, int *ops, int maxOps, unsigned long long *fp, int maxFp, FootprintOf footprint)
+{
+    rtcplan::TracePlan t;
+    rtcplan::plan_query(s->st, kernel, t);
+    s->st = t.after;
+    return serialise(t.ops, t.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)t.gen, 0, 0, 0},
+                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) { return footprint(t, f, max); });
+}
+} // namespace
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
 {
@@ -695,32 +716,14 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
     rtcplan::Plan &p = s->last;
     rtcplan::plan_launch(s->st, r, p);
     s->st = p.after;
-    /* ops: 4 ints each (kind, stream, event, kernel); per kernel op, its footprint entries (5 u64 each: op index, res,
-     * access, id, lo, hi -> 6) in fp */
-    int nf = 0;
-    for (int i = 0; i < p.nOps && i < maxOps; ++i) {
-        const rtcplan::Op &o = p.ops[i];
-        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
-        if (o.kind != rtcplan::kOpKernel)
-            continue;
-        rtcplan::Footprint f[24];
-        const int k = rtcplan::kernel_footprint(p, r, o.kernel, f, 24);
-        for (int j = 0; j < k && j < 24; ++j, ++nf)
-            if (fp && nf < maxFp) {
-                unsigned long long *q = fp + 6 * (size_t)nf;
-                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
-                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
-            }
-    }
-    /* the scratch regrowth (hipFree + hipMalloc: the device is synchronised first; so it is before the draw cache is
-     * cleared or its item-draw arrays regrown) and the plan's shape, after the ops */
-    if (fp && nf < maxFp) {
-        unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = p.scratchGrow || p.samplesGrow || p.drawReset || p.itemDrawGrow,
-        q[2] = (unsigned long long)p.half, q[3] = p.chainOnCs,
-        q[4] = p.overlap, q[5] = p.slotOffset;
-    }
-    return p.nOps | ((nf + 1) << 8);
+    /* the trailer: the scratch regrowth (hipFree + hipMalloc: the device is synchronised first; so it is before the draw
+     * cache is cleared or its item-draw arrays regrown) and the plan's shape */
+    return serialise(p.ops, p.nOps, ops, maxOps, fp, maxFp,
+                     {p.scratchGrow || p.samplesGrow || p.drawReset || p.itemDrawGrow, (unsigned long long)p.half,
+                      p.chainOnCs, p.overlap, p.slotOffset},
+                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
+                         return rtcplan::kernel_footprint(p, r, o.kernel, f, max);
+                     });
 }
 
 extern "C" int rtc_plan_sim_set_update_fault(RtcPlanSim *s, int mode)
@@ -740,26 +743,11 @@ extern "C" int rtc_plan_sim_update(RtcPlanSim *s, unsigned long long stream, int
     rtcplan::UpdatePlan u;
     rtcplan::plan_update(s->st, s->updateFault, u);
     s->st = u.after;
-    int nf = 0;
-    for (int i = 0; i < u.nOps && i < maxOps; ++i) {
-        const rtcplan::Op &o = u.ops[i];
-        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
-        if (o.kind != rtcplan::kOpKernel)
-            continue;
-        rtcplan::Footprint f[2];
-        const int k = rtcplan::update_footprint(u, f, 2);
-        for (int j = 0; j < k; ++j, ++nf)
-            if (fp && nf < maxFp) {
-                unsigned long long *q = fp + 6 * (size_t)nf;
-                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
-                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
-            }
-    }
-    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation written, -, -, -) */
-        unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)u.writes, q[3] = q[4] = q[5] = 0;
-    }
-    return u.nOps | ((nf + 1) << 8);
+    /* the trailer: (~0, nothing regrown, the generation written, -, -, -) */
+    return serialise(u.ops, u.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)u.writes, 0, 0, 0},
+                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) {
+                         return rtcplan::update_footprint(u, f, max);
+                     });
 }
 
 extern "C" int rtc_plan_sim_trace_rays(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,
@@ -770,28 +758,11 @@ extern "C" int rtc_plan_sim_trace_rays(RtcPlanSim *s, unsigned long long stream,
     if (!s || !ops || !rays || !hit || !(hit[0] | hit[1] | hit[2] | hit[3]) || (flags & ~RTC_F_NO_CLUSTER_CULL))
         return RTC_EINVAL;
     (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
-    rtcplan::TracePlan t;
-    rtcplan::plan_trace_rays(s->st, t);
-    s->st = t.after;
     const uint64_t ids[4] = {hit[0], hit[1], hit[2], hit[3]};
-    int nf = 0;
-    for (int i = 0; i < t.nOps && i < maxOps; ++i) {
-        const rtcplan::Op &o = t.ops[i];
-        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
-        rtcplan::Footprint f[6];
-        const int k = rtcplan::trace_footprint(t, rays, ids, f, 6);
-        for (int j = 0; j < k; ++j, ++nf)
-            if (fp && nf < maxFp) {
-                unsigned long long *q = fp + 6 * (size_t)nf;
-                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
-                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
-            }
-    }
-    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation read, -, -, -) */
-        unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)t.gen, q[3] = q[4] = q[5] = 0;
-    }
-    return t.nOps | ((nf + 1) << 8);
+    return sim_query(s, rtcplan::kKTraceRays, ops, maxOps, fp, maxFp,
+                     [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                         return rtcplan::trace_footprint(t, rays, ids, f, max);
+                     });
 }
 
 extern "C" int rtc_plan_sim_trace_paths(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,
@@ -803,27 +774,11 @@ extern "C" int rtc_plan_sim_trace_paths(RtcPlanSim *s, unsigned long long stream
     if (!s || !ops || !rays || !seeds || !radiance || sampleFirst < 0 || (flags & ~RTC_F_NO_CLUSTER_CULL))
         return RTC_EINVAL;
     (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
-    rtcplan::TracePlan t;
-    rtcplan::plan_trace_paths(s->st, t);
-    s->st = t.after;
-    int nf = 0;
-    for (int i = 0; i < t.nOps && i < maxOps; ++i) {
-        const rtcplan::Op &o = t.ops[i];
-        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
-        rtcplan::Footprint f[7];
-        const int k = rtcplan::paths_footprint(t, rays, seeds, radiance, seedsOut, segments != 0, sampleFirst > 0, f, 7);
-        for (int j = 0; j < k; ++j, ++nf)
-            if (fp && nf < maxFp) {
-                unsigned long long *q = fp + 6 * (size_t)nf;
-                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
-                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
-            }
-    }
-    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation read, -, -, -) */
-        unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)t.gen, q[3] = q[4] = q[5] = 0;
-    }
-    return t.nOps | ((nf + 1) << 8);
+    return sim_query(s, rtcplan::kKTracePaths, ops, maxOps, fp, maxFp,
+                     [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                         return rtcplan::paths_footprint(t, rays, seeds, radiance, seedsOut, segments != 0, sampleFirst > 0,
+                                                         f, max);
+                     });
 }
 
 extern "C" int rtc_plan_sim_occluded(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,
@@ -834,27 +789,10 @@ extern "C" int rtc_plan_sim_occluded(RtcPlanSim *s, unsigned long long stream, u
     if (!s || !ops || !rays || !(occluded | count) || (flags & ~RTC_F_NO_CLUSTER_CULL))
         return RTC_EINVAL;
     (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
-    rtcplan::TracePlan t;
-    rtcplan::plan_occluded(s->st, t);
-    s->st = t.after;
-    int nf = 0;
-    for (int i = 0; i < t.nOps && i < maxOps; ++i) {
-        const rtcplan::Op &o = t.ops[i];
-        ops[4 * i] = o.kind, ops[4 * i + 1] = o.stream, ops[4 * i + 2] = o.event, ops[4 * i + 3] = o.kernel;
-        rtcplan::Footprint f[5];
-        const int k = rtcplan::occluded_footprint(t, rays, tMax, occluded, count != 0, f, 5);
-        for (int j = 0; j < k; ++j, ++nf)
-            if (fp && nf < maxFp) {
-                unsigned long long *q = fp + 6 * (size_t)nf;
-                q[0] = (unsigned long long)i, q[1] = (unsigned long long)f[j].res, q[2] = (unsigned long long)f[j].access;
-                q[3] = f[j].id, q[4] = f[j].lo, q[5] = f[j].hi;
-            }
-    }
-    if (fp && nf < maxFp) { /* (~0, nothing regrown, the generation read, -, -, -) */
-        unsigned long long *q = fp + 6 * (size_t)nf;
-        q[0] = ~0ull, q[1] = 0, q[2] = (unsigned long long)t.gen, q[3] = q[4] = q[5] = 0;
-    }
-    return t.nOps | ((nf + 1) << 8);
+    return sim_query(s, rtcplan::kKOccluded, ops, maxOps, fp, maxFp,
+                     [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                         return rtcplan::occluded_footprint(t, rays, tMax, occluded, count != 0, f, max);
+                     });
 }
 
 extern "C" int rtc_plan_sim_regions(const RtcPlanSim *s, unsigned long long *out, int maxRows)

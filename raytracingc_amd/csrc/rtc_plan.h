@@ -20,6 +20,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 
 #include "../../include/rtc.h"
 
@@ -62,9 +63,9 @@ enum Event : int {
 enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kKOrder, kKRender, kKReduce,
                     kKRefit /* rtc_scene_update_async's kernel (plan_update); never part of a launch */,
                     kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */,
-                    kKTraceRays /* rtc_trace_rays_async's kernel (plan_trace_rays); never part of a launch */,
-                    kKTracePaths /* rtc_trace_paths_async's kernel (plan_trace_paths); never part of a launch */,
-                    kKOccluded /* rtc_occluded_async's kernel (plan_occluded); never part of a launch */ };
+                    kKTraceRays /* rtc_trace_rays_async's kernel (plan_query); never part of a launch */,
+                    kKTracePaths /* rtc_trace_paths_async's kernel (plan_query); never part of a launch */,
+                    kKOccluded /* rtc_occluded_async's kernel (plan_query); never part of a launch */ };
 static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12 && kKOccluded == 13,
               "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
@@ -284,40 +285,40 @@ void plan_update(const State &s, int fault, UpdatePlan &u);
 /* the refit kernel's footprint: the generation it writes and the one it may copy from */
 int update_footprint(const UpdatePlan &u, Footprint *out, int max);
 
-/* One rtc_trace_rays_async: one kernel on the caller's stream that reads the current generation of the
- * scene records and the caller's rays and writes the caller's hit buffers.  It uses no scratch slot, primary record,
- * counter set, stream or event of the scene's, so it waits for nothing and arms nothing: stream order alone places it
- * after the update that wrote its generation and before the one that will rewrite it (an update writes the generation no
- * launch binds, on the caller's stream).  `after` equals the state it was planned from. */
+/* One query for caller-supplied rays -- rtc_trace_rays_async (kKTraceRays), rtc_trace_paths_async
+ * (kKTracePaths, §3.12) or rtc_occluded_async (kKOccluded, §3.13): one kernel on the caller's stream that reads the current
+ * generation of the scene records and the caller's buffers and writes the caller's buffers.  It uses no scratch slot,
+ * primary record, counter set, stream or event of the scene's, so it waits for nothing and arms nothing: stream order
+ * alone places it after the update that wrote its generation and before the one that will rewrite it (an update writes
+ * the generation no launch binds, on the caller's stream).  `after` equals the state it was planned from. */
 struct TracePlan {
     int gen; /* the generation the kernel reads */
     int nOps;
     Op ops[1];
     State after;
 };
-void plan_trace_rays(const State &s, TracePlan &t);
-/* the kernel's footprint: the generation read, the rays read (id: the buffer), one write per hit buffer asked for
+void plan_query(const State &s, int kernel, TracePlan &t);
+/* A query kernel's footprint: the generation read, then the query's own rows in the order given, those that are present
+ * (a buffer not asked for has no row); every row is one unit, [0, 1) */
+struct QueryRow {
+    int res, access;
+    unsigned long long id;
+    bool present;
+};
+int query_footprint(const TracePlan &t, std::initializer_list<QueryRow> rows, Footprint *out, int max);
+
+/* rtc_trace_rays_async: the generation read, the rays read (id: the buffer), one write per hit buffer asked for
  * (hit[k] == 0: not asked for), in that order */
 int trace_footprint(const TracePlan &t, uint64_t rays, const uint64_t hit[4], Footprint *out, int max);
-
-/* One rtc_trace_paths_async: plan_trace_rays's plan with the path kernel -- one kernel on the caller's
- * stream, nothing of the scene's beyond the records of the current generation, `after` equal to the state it was planned
- * from. */
-void plan_trace_paths(const State &s, TracePlan &t);
-/* the kernel's footprint, in this order: the generation read, the rays read, the seeds read (ids: the buffers), the
+/* rtc_trace_paths_async, in this order: the generation read, the rays read, the seeds read (ids: the buffers), the
  * radiance read only when the call continues an accumulation (readRadiance: sampleFirst > 0), the radiance written, the
  * seeds written (id: the out buffer; 0: not asked for) and the caller's segment counter added to atomically (when asked
  * for; id 0 as in a launch's footprint) */
 int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t radiance, uint64_t seedsOut, bool segments,
                     bool readRadiance, Footprint *out, int max);
-
-/* One rtc_occluded_async: plan_trace_rays's plan with the occlusion kernel -- one kernel on the caller's
- * stream, nothing of the scene's beyond the records of the current generation, `after` equal to the state it was planned
- * from. */
-void plan_occluded(const State &s, TracePlan &t);
-/* the kernel's footprint, in this order: the generation read, the rays read, the limits read (ids: the buffers; tMax 0:
- * none given), the bytes written (id: the buffer; 0: not asked for) and the caller's counter added to atomically (when
- * asked for; resource 7 with id 0, as in a launch's footprint) */
+/* rtc_occluded_async, in this order: the generation read, the rays read, the limits read (ids: the buffers; tMax 0: none
+ * given), the bytes written (id: the buffer; 0: not asked for) and the caller's counter added to atomically (when asked
+ * for; resource 7 with id 0, as in a launch's footprint) */
 int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_t occluded, bool count, Footprint *out,
                        int max);
 

@@ -668,23 +668,125 @@ extern "C" int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCame
     return render_rows(s, nullptr, cam, d, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr, out);
 }
 
-/* ---- caller-supplied rays ----------------------------------------------------------------------- */
-/* the refusals of rtc_trace_rays_async and rtc_trace_rays, before any device call and before `s` is read */
-static int check_trace_rays(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
-                            const void *const out[4], bool haveOut)
+/* ---- caller-supplied rays: closest hit, radiance, occlusion -------------------------------------- */
+/* The three queries share everything on the host but their arguments.  A query supplies: its args struct (whose record
+ * part, `rays` and `n` carry these names), its <SPHERES, CULL> kernel table and kernel number, its own refusals, its
+ * footprint rows (rtc_plan.h) and, for the host entry, the table of what is staged. */
+
+static int no_refusal() { return 0; }
+
+/* The refusals of a query's two entries, before any device call and before `s` is read, in the order every query keeps:
+ * the scene, the entry's own arguments (nullArgument; noneAsked: the text when no output is asked for, else null), the
+ * ray count, whatever else is the query's own (`own`), the flags.  `noun`: "a ray", "a path", "an occlusion". */
+template <class Own>
+static int refuse_query(const char *who, const char *noun, const RtcDeviceScene *s, bool nullArgument,
+                        const char *noneAsked, size_t n, int flags, Own own)
 {
     if (!s)
         return rtc_fail(RTC_EINVAL, "%s: null scene", who);
-    if (!rays || !haveOut)
+    if (nullArgument)
         return rtc_fail(RTC_EINVAL, "%s: null argument", who);
-    if (!out[0] && !out[1] && !out[2] && !out[3])
-        return rtc_fail(RTC_EINVAL, "%s: no buffer asked for (prim, depth, normal and albedo are all null)", who);
+    if (noneAsked)
+        return rtc_fail(RTC_EINVAL, "%s: %s", who, noneAsked);
     if (n > (size_t)0x7fffffff)
         return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
+    if (const int rc = own())
+        return rc;
     if (flags & ~RTC_F_NO_CLUSTER_CULL)
-        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (a ray query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who,
-                        flags);
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (%s query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who, flags,
+                        noun);
     return 0;
+}
+
+static void set_mats(OccludedArgs &, const DevMat *) {} /* (an occlusion query reads no material) */
+template <class Args>
+static void set_mats(Args &a, const DevMat *mats)
+{
+    a.mats = mats;
+}
+
+/* From a query's args, its own fields filled, to its kernel enqueued on `stream` (n > 0).  The planner names the generation
+ * and the one operation (rtc_plan.h plan_query); the ordering state stays as it is (TracePlan::after == s->plan), and so do
+ * the hooks, the timing events, the chain report and the draw cache. */
+template <class Args>
+static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, void (*const (&table)[2][2])(Args), Args &a,
+                         const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream)
+{
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    rtcplan::TracePlan tp;
+    rtcplan::plan_query(s->plan, kernel, tp);
+    const SceneRecords &g = s->gen[tp.gen];
+    a.tris = g.tris, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters, a.chunks = g.chunks;
+    set_mats(a, g.mats);
+    a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
+    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
+    a.rays = (const float *)dRays, a.n = (unsigned)n;
+    for (int i = 0; i < tp.nOps; ++i) {
+        const rtcplan::Op &op = tp.ops[i];
+        if (op.kind != rtcplan::kOpKernel || op.kernel != kernel || op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
+        hipLaunchKernelGGL(table[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
+                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+/* One buffer of a host entry: `bytes` of device memory when wanted (else the query gets a null pointer), filled from `in`
+ * first (null: left as allocated) and copied to `out` afterwards (null: an input) */
+struct Staged {
+    const void *in;
+    void *out;
+    size_t bytes;
+    bool want;
+};
+
+/* A query's host entry (n > 0, nothing refused): staged through device buffers on the null stream, like
+ * rtc_scene_update.  `call` gets the device pointers in the items' order and issues the asynchronous entry. */
+template <int N, class Call>
+static int staged_query(const char *who, const RtcDeviceScene *s, const Staged (&items)[N], Call call)
+{
+    int devices = 0;
+    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
+        return rc;
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    void *dev[N] = {};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < N; ++k) {
+        if (e == hipSuccess && items[k].want)
+            e = hipMalloc(&dev[k], items[k].bytes);
+        if (e == hipSuccess && items[k].want && items[k].in)
+            e = hipMemcpy(dev[k], items[k].in, items[k].bytes, hipMemcpyHostToDevice);
+    }
+    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    int rc = e == hipSuccess ? call(dev) : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
+    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (int k = 0; k < N; ++k)
+        if (rc == 0 && dev[k] && items[k].out &&
+            (e = hipMemcpy(items[k].out, dev[k], items[k].bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
+    for (void *p : dev)
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
+/* ---- closest hit */
+static int check_trace_rays(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
+                            const void *const out[4], bool haveOut)
+{
+    return refuse_query(who, "a ray", s, !rays || !haveOut,
+                        out[0] || out[1] || out[2] || out[3]
+                            ? nullptr
+                            : "no buffer asked for (prim, depth, normal and albedo are all null)",
+                        n, flags, no_refusal);
 }
 
 extern "C" int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, int trianglesOnly, int flags,
@@ -697,96 +799,46 @@ extern "C" int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, s
         return rc;
     if (n == 0)
         return 0;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* the planner names the generation and the one operation (rtc_plan.h plan_trace_rays); the ordering state stays as it
-     * is (TracePlan::after == s->plan), and so do the hooks, the timing events and the chain report */
-    rtcplan::TracePlan tp;
-    rtcplan::plan_trace_rays(s->plan, tp);
-    const SceneRecords &g = s->gen[tp.gen];
     TraceRaysArgs a{};
-    a.tris = g.tris, a.mats = g.mats, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters;
-    a.chunks = g.chunks;
-    a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
-    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
-    a.rays = (const float *)dRays, a.n = (unsigned)n;
     a.prim = out->prim, a.depth = out->depth, a.normal = out->normal, a.albedo = out->albedo;
     /* <SPHERES, CULL> */
     static void (*const kTraceRays[2][2])(TraceRaysArgs) = {{rtc_trace_rays<false, false>, rtc_trace_rays<false, true>},
                                                             {rtc_trace_rays<true, false>, rtc_trace_rays<true, true>}};
-    for (int i = 0; i < tp.nOps; ++i) {
-        const rtcplan::Op &op = tp.ops[i];
-        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKTraceRays || op.stream != rtcplan::kStCaller)
-            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
-        hipLaunchKernelGGL(kTraceRays[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
-                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return enqueue_query(who, s, rtcplan::kKTraceRays, kTraceRays, a, dRays, n, trianglesOnly, flags, stream);
 }
 
 extern "C" int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trianglesOnly, int flags, int *prim,
                               float *depth, float *normal, float *albedo)
 {
     const char *const who = "rtc_trace_rays";
-    void *const host[4] = {prim, depth, normal, albedo};
+    const void *const host[4] = {prim, depth, normal, albedo};
     if (const int rc = check_trace_rays(who, s, rays, n, flags, host, true))
         return rc;
     if (n == 0)
         return 0;
-    int devices = 0;
-    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
-        return rc;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* staged through device buffers on the null stream, like rtc_scene_update */
-    const size_t bytes[4] = {n * sizeof(int), n * sizeof(float), n * 3 * sizeof(float), n * 3 * sizeof(float)};
-    void *dRays = nullptr, *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipMalloc(&dRays, n * sizeof(Ray));
-    if (e == hipSuccess)
-        e = hipMemcpy(dRays, rays, n * sizeof(Ray), hipMemcpyHostToDevice);
-    for (int k = 0; k < 4; ++k)
-        if (e == hipSuccess && host[k])
-            e = hipMalloc(&dev[k], bytes[k]);
-    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    const RtcHitBuffers out{(int *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3]};
-    int rc = e == hipSuccess ? rtc_trace_rays_async(s, (const Ray *)dRays, n, trianglesOnly, flags, &out, nullptr)
-                             : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
-    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
-        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (int k = 0; k < 4; ++k)
-        if (rc == 0 && dev[k] && (e = hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
-            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (void *p : {dRays, dev[0], dev[1], dev[2], dev[3]})
-        if (p)
-            (void)hipFree(p);
-    return rc;
+    const Staged items[5] = {{rays, nullptr, n * sizeof(Ray), true},
+                             {nullptr, prim, n * sizeof(int), prim != nullptr},
+                             {nullptr, depth, n * sizeof(float), depth != nullptr},
+                             {nullptr, normal, n * 3 * sizeof(float), normal != nullptr},
+                             {nullptr, albedo, n * 3 * sizeof(float), albedo != nullptr}};
+    return staged_query(who, s, items, [&](void *const *dev) {
+        const RtcHitBuffers out{(int *)dev[1], (float *)dev[2], (float *)dev[3], (float *)dev[4]};
+        return rtc_trace_rays_async(s, (const Ray *)dev[0], n, trianglesOnly, flags, &out, nullptr);
+    });
 }
 
-/* ---- caller-supplied rays: radiance --------------------------------------------------------------- */
-/* the refusals of rtc_trace_paths_async and rtc_trace_paths, before any device call and before `s` is read */
+/* ---- radiance */
 static int check_trace_paths(const char *who, const RtcDeviceScene *s, const Scene *scene, const void *rays,
                              const void *seeds, size_t n, const RtcPathDesc *d, const void *radiance)
 {
-    if (!s)
-        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
-    if (!scene || !rays || !seeds || !d || !radiance)
-        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
-    if (n > (size_t)0x7fffffff)
-        return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
-    if (d->spp <= 0)
-        return rtc_fail(RTC_EINVAL, "%s: spp %d", who, d->spp);
-    if (d->sampleFirst < 0 || d->sampleCount <= 0 || d->sampleFirst > d->spp - d->sampleCount)
-        return rtc_fail(RTC_EINVAL, "%s: samples [%d, %d + %d) of spp %d", who, d->sampleFirst, d->sampleFirst,
-                        d->sampleCount, d->spp);
-    if (d->flags & ~RTC_F_NO_CLUSTER_CULL)
-        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (a path query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who,
-                        d->flags);
-    return 0;
+    return refuse_query(who, "a path", s, !scene || !rays || !seeds || !d || !radiance, nullptr, n, d ? d->flags : 0, [&] {
+        if (d->spp <= 0)
+            return rtc_fail(RTC_EINVAL, "%s: spp %d", who, d->spp);
+        if (d->sampleFirst < 0 || d->sampleCount <= 0 || d->sampleFirst > d->spp - d->sampleCount)
+            return rtc_fail(RTC_EINVAL, "%s: samples [%d, %d + %d) of spp %d", who, d->sampleFirst, d->sampleFirst,
+                            d->sampleCount, d->spp);
+        return 0;
+    });
 }
 
 extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene, const Ray *dRays,
@@ -798,37 +850,16 @@ extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene
         return rc;
     if (n == 0)
         return 0;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* as rtc_trace_rays_async: the planner names the generation and the one operation (rtc_plan.h plan_trace_paths), and
-     * the ordering state, the hooks, the timing events, the chain report and the draw cache stay as they are */
-    rtcplan::TracePlan tp;
-    rtcplan::plan_trace_paths(s->plan, tp);
-    const SceneRecords &g = s->gen[tp.gen];
     TracePathsArgs a{};
-    a.tris = g.tris, a.mats = g.mats, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters;
-    a.chunks = g.chunks;
-    a.triPadded = s->triPadded, a.sphereCount = d->trianglesOnly ? 0 : s->sphereCount;
-    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
     a.env = env_of(*scene);
     a.invSpp = (float)(1. / d->spp); /* main.c:99 */
     a.sampleFirst = d->sampleFirst, a.sampleCount = d->sampleCount, a.maxBounce = d->maxBounce;
-    a.rays = (const float *)dRays, a.n = (unsigned)n;
     a.seeds = dSeeds, a.radiance = dRadiance, a.seedsOut = dSeedsOut, a.segments = dSegments;
     /* <SPHERES, CULL> */
     static void (*const kTracePaths[2][2])(TracePathsArgs) = {
         {rtc_trace_paths<false, false>, rtc_trace_paths<false, true>},
         {rtc_trace_paths<true, false>, rtc_trace_paths<true, true>}};
-    for (int i = 0; i < tp.nOps; ++i) {
-        const rtcplan::Op &op = tp.ops[i];
-        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKTracePaths || op.stream != rtcplan::kStCaller)
-            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
-        hipLaunchKernelGGL(kTracePaths[a.sphereCount > 0][!(d->flags & RTC_F_NO_CLUSTER_CULL)],
-                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return enqueue_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags, stream);
 }
 
 extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds,
@@ -840,62 +871,26 @@ extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, cons
         return rc;
     if (n == 0)
         return 0;
-    int devices = 0;
-    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
-        return rc;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* staged through device buffers on the null stream, like rtc_trace_rays; the radiance goes in too when the call
-     * continues an accumulation, and the segment counter starts at the caller's value */
-    const size_t bytes[5] = {n * sizeof(Ray), n * sizeof(unsigned), n * 3 * sizeof(float), n * sizeof(unsigned),
-                             sizeof(unsigned long long)};
-    const void *const in[5] = {rays, seeds, d->sampleFirst > 0 ? radiance : nullptr, nullptr, segments};
-    void *const out[5] = {nullptr, nullptr, radiance, seedsOut, segments};
-    const bool want[5] = {true, true, true, seedsOut != nullptr, segments != nullptr};
-    void *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 5; ++k) {
-        if (e == hipSuccess && want[k])
-            e = hipMalloc(&dev[k], bytes[k]);
-        if (e == hipSuccess && want[k] && in[k])
-            e = hipMemcpy(dev[k], in[k], bytes[k], hipMemcpyHostToDevice);
-    }
-    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    int rc = e == hipSuccess
-                 ? rtc_trace_paths_async(s, scene, (const Ray *)dev[0], (const unsigned *)dev[1], n, d, (float *)dev[2],
-                                         (unsigned *)dev[3], (unsigned long long *)dev[4], nullptr)
-                 : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
-    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
-        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (int k = 0; k < 5; ++k)
-        if (rc == 0 && dev[k] && out[k] && (e = hipMemcpy(out[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
-            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (void *p : dev)
-        if (p)
-            (void)hipFree(p);
-    return rc;
+    /* the radiance goes in too when the call continues an accumulation, and the segment counter starts at the caller's
+     * value */
+    const Staged items[5] = {{rays, nullptr, n * sizeof(Ray), true},
+                             {seeds, nullptr, n * sizeof(unsigned), true},
+                             {d->sampleFirst > 0 ? radiance : nullptr, radiance, n * 3 * sizeof(float), true},
+                             {nullptr, seedsOut, n * sizeof(unsigned), seedsOut != nullptr},
+                             {segments, segments, sizeof(unsigned long long), segments != nullptr}};
+    return staged_query(who, s, items, [&](void *const *dev) {
+        return rtc_trace_paths_async(s, scene, (const Ray *)dev[0], (const unsigned *)dev[1], n, d, (float *)dev[2],
+                                     (unsigned *)dev[3], (unsigned long long *)dev[4], nullptr);
+    });
 }
 
-/* ---- caller-supplied rays: occlusion within a distance limit -------------------------------------- */
-/* the refusals of rtc_occluded_async and rtc_occluded, before any device call and before `s` is read */
+/* ---- occlusion within a distance limit */
 static int check_occluded(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
                           const void *occluded, const void *count)
 {
-    if (!s)
-        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
-    if (!rays)
-        return rtc_fail(RTC_EINVAL, "%s: null argument", who);
-    if (!occluded && !count)
-        return rtc_fail(RTC_EINVAL, "%s: no output asked for (occluded and count are both null)", who);
-    if (n > (size_t)0x7fffffff)
-        return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
-    if (flags & ~RTC_F_NO_CLUSTER_CULL)
-        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (an occlusion query takes RTC_F_NO_CLUSTER_CULL and no other flag)",
-                        who, flags);
-    return 0;
+    return refuse_query(who, "an occlusion", s, !rays,
+                        occluded || count ? nullptr : "no output asked for (occluded and count are both null)", n, flags,
+                        no_refusal);
 }
 
 extern "C" int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *dTMax, size_t n,
@@ -907,32 +902,12 @@ extern "C" int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, con
         return rc;
     if (n == 0)
         return 0;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* as rtc_trace_rays_async: the planner names the generation and the one operation (rtc_plan.h plan_occluded), and
-     * the ordering state, the hooks, the timing events, the chain report and the draw cache stay as they are */
-    rtcplan::TracePlan tp;
-    rtcplan::plan_occluded(s->plan, tp);
-    const SceneRecords &g = s->gen[tp.gen];
     OccludedArgs a{};
-    a.tris = g.tris, a.spheres = g.spheres, a.clTris = g.clTris, a.clusters = g.clusters, a.chunks = g.chunks;
-    a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
-    a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
-    a.rays = (const float *)dRays, a.tMax = dTMax, a.n = (unsigned)n;
-    a.occluded = dOccluded, a.count = dCount;
+    a.tMax = dTMax, a.occluded = dOccluded, a.count = dCount;
     /* <SPHERES, CULL> */
     static void (*const kOccluded[2][2])(OccludedArgs) = {{rtc_occluded<false, false>, rtc_occluded<false, true>},
                                                           {rtc_occluded<true, false>, rtc_occluded<true, true>}};
-    for (int i = 0; i < tp.nOps; ++i) {
-        const rtcplan::Op &op = tp.ops[i];
-        if (op.kind != rtcplan::kOpKernel || op.kernel != rtcplan::kKOccluded || op.stream != rtcplan::kStCaller)
-            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
-        hipLaunchKernelGGL(kOccluded[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
-                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return enqueue_query(who, s, rtcplan::kKOccluded, kOccluded, a, dRays, n, trianglesOnly, flags, stream);
 }
 
 extern "C" int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly,
@@ -943,40 +918,15 @@ extern "C" int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const floa
         return rc;
     if (n == 0)
         return 0;
-    int devices = 0;
-    if (const int rc = rtc_device_count(&devices)) /* (RTC_ENODEV before the handle is read) */
-        return rc;
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
-    /* staged through device buffers on the null stream, like rtc_trace_rays; the counter starts at the caller's value */
-    const size_t bytes[4] = {n * sizeof(Ray), n * sizeof(float), n, sizeof(unsigned long long)};
-    const void *const in[4] = {rays, tMax, nullptr, count};
-    void *const out[4] = {nullptr, nullptr, occluded, count};
-    const bool want[4] = {true, tMax != nullptr, occluded != nullptr, count != nullptr};
-    void *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 4; ++k) {
-        if (e == hipSuccess && want[k])
-            e = hipMalloc(&dev[k], bytes[k]);
-        if (e == hipSuccess && want[k] && in[k])
-            e = hipMemcpy(dev[k], in[k], bytes[k], hipMemcpyHostToDevice);
-    }
-    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the query */
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    int rc = e == hipSuccess ? rtc_occluded_async(s, (const Ray *)dev[0], (const float *)dev[1], n, trianglesOnly, flags,
-                                                  (unsigned char *)dev[2], (unsigned long long *)dev[3], nullptr)
-                             : rtc_fail(-(int)e, "%s: staging failed: %s", who, hipGetErrorString(e));
-    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
-        rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (int k = 0; k < 4; ++k)
-        if (rc == 0 && dev[k] && out[k] && (e = hipMemcpy(out[k], dev[k], bytes[k], hipMemcpyDeviceToHost)) != hipSuccess)
-            rc = rtc_fail(-(int)e, "%s: %s", who, hipGetErrorString(e));
-    for (void *p : dev)
-        if (p)
-            (void)hipFree(p);
-    return rc;
+    /* the counter starts at the caller's value */
+    const Staged items[4] = {{rays, nullptr, n * sizeof(Ray), true},
+                             {tMax, nullptr, n * sizeof(float), tMax != nullptr},
+                             {nullptr, occluded, n, occluded != nullptr},
+                             {count, count, sizeof(unsigned long long), count != nullptr}};
+    return staged_query(who, s, items, [&](void *const *dev) {
+        return rtc_occluded_async(s, (const Ray *)dev[0], (const float *)dev[1], n, trianglesOnly, flags,
+                                  (unsigned char *)dev[2], (unsigned long long *)dev[3], nullptr);
+    });
 }
 
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,

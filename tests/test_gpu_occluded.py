@@ -347,6 +347,30 @@ def test_entry_points_and_inputs_agree(gpu_available):
     assert ds.occluded(rays[:100], 1.0, True).shape == (100,)
 
 
+@pytest.mark.parametrize("limits", [False, True])
+@pytest.mark.parametrize("outputs", ["bytes", "count"])
+def test_host_entry_single_outputs(outputs, limits, gpu_available):
+    """rtc_occluded itself (the Python method always asks for the bytes) with the bytes alone and with the count alone, with
+    limits and with a null tMax, 65 rays -- a wave and one lane -- on the default scene: the device-tensor entry's answers
+    for the same rays; the counter is added to, and left alone when not asked for."""
+    import ctypes as C
+
+    import torch
+
+    ptr = rt._abi._ptr
+    rays, ds = np.ascontiguousarray(tr.replay("default")[:65]), _scene("default")
+    lim = np.ascontiguousarray(oc.case_limits("replay", "default", "above")[:65], F) if limits else None
+    for flags in FLAGS:
+        dev, dc = ds.occluded(_dev(rays), torch.from_numpy(lim.copy()).cuda() if limits else None, False, flags, count=True)
+        occ, cnt = np.full(65, GUARD, np.uint8), C.c_ulonglong(1000)
+        rc = rt.lib().rtc_occluded(ds._h, ptr(rays), ptr(lim), 65, 0, flags, ptr(occ) if outputs == "bytes" else None,
+                                   C.cast(C.pointer(cnt), C.c_void_p) if outputs == "count" else None)
+        assert rc == 0, flags
+        assert np.array_equal(occ, dev.astype(np.uint8) if outputs == "bytes" else np.full(65, GUARD, np.uint8)), flags
+        assert cnt.value == 1000 + (dc if outputs == "count" else 0), flags
+        assert 0 < dc == int(dev.sum())
+
+
 def test_refusals_on_a_scene(gpu_available):
     """On a real handle: an unknown flag and two null outputs are RTC_EINVAL with nothing enqueued; n == 0 writes nothing;
     no entry point takes 0x8000 (the deleted RTC_F_NO_REACH_CULL's bit)."""

@@ -326,3 +326,32 @@ def test_host_entry(gpu_available):
             assert tp.differing(two["radiance"], want[0]) == 0 and np.array_equal(two["seeds"], want[1])
             assert h1["segments"] + two["segments"] == want[2]
     assert "segments" not in ds.trace_paths(rays[:10], seeds[:10], SCENE, 1, 1)
+
+
+@pytest.mark.parametrize("with_seeds, with_segments", [(False, False), (True, False), (False, True), (True, True)])
+def test_host_entry_optional_outputs(with_seeds, with_segments, gpu_available):
+    """rtc_trace_paths itself (the Python method always asks for the states) continuing an accumulation (sampleFirst > 0:
+    the radiance is staged in) with and without seedsOut and segments, 65 rays -- a wave and one lane -- on the default
+    scene: the radiance, and the states and the count where asked for, are the device-tensor entry's for the same
+    continuation; an output not asked for is left alone, the counter is added to."""
+    import ctypes as C
+
+    import torch
+
+    ptr = rt._abi._ptr
+    rays, seeds, ds = np.ascontiguousarray(tr.replay("default")[:65]), tp.hash_seeds(65), _scene("default")
+    for flags in FLAGS:
+        first = ds.trace_paths(_dev(rays), _words(seeds), SCENE, 5, tp.MAX_BOUNCE, False, flags, 0, 2)
+        dev = ds.trace_paths(_dev(rays), _words(first["seeds"]), SCENE, 5, tp.MAX_BOUNCE, False, flags, 2, 3,
+                             _words(first["radiance"]).view(torch.float32).reshape(-1, 3), segments=True)
+        rad, sd = first["radiance"].copy(), np.ascontiguousarray(first["seeds"], np.uint32)
+        out, seg = np.full(65, GUARD, np.uint32), C.c_ulonglong(1000)
+        d = rt.RtcPathDesc(5, tp.MAX_BOUNCE, 0, flags, 2, 3)
+        rc = rt.lib().rtc_trace_paths(ds._h, C.byref(SCENE), ptr(rays), ptr(sd), 65, C.byref(d), ptr(rad),
+                                      ptr(out) if with_seeds else None,
+                                      C.cast(C.pointer(seg), C.c_void_p) if with_segments else None)
+        assert rc == 0, flags
+        assert np.array_equal(rad.view(np.uint32), dev["radiance"].view(np.uint32)), flags
+        assert np.array_equal(out, dev["seeds"] if with_seeds else np.full(65, GUARD, np.uint32)), flags
+        assert seg.value == 1000 + (dev["segments"] if with_segments else 0), flags
+        assert np.array_equal(sd, first["seeds"]) and dev["segments"] > 0

@@ -286,6 +286,19 @@ def test_entry_points_and_inputs_agree(gpu_available):
     assert set(ds.trace_rays(rays[:100], True, ("depth",))) == {"depth"}
 
 
+@pytest.mark.parametrize("only", tr.NAMES)
+def test_host_entry_single_buffers(only, gpu_available):
+    """rtc_trace_rays with one buffer asked for and the other three null (staged: no device buffer for them), 65 rays -- a
+    wave and one lane, where a wrong byte count or a buffer in another's place shows -- on the default scene (the smallest
+    fixture whose rays hit triangles and a sphere, so normal and albedo differ): the device-tensor entry's words."""
+    rays, ds = tr.replay("default")[:65], _scene("default")
+    for flags in FLAGS:
+        host, dev = ds.trace_rays(rays, False, (only,), flags), _trace(ds, rays, 0, flags)
+        assert set(host) == {only} and host[only].dtype == dev[only].dtype and host[only].shape == dev[only].shape
+        assert np.array_equal(host[only].view(np.uint32), dev[only].view(np.uint32)), flags
+    assert (dev["prim"] >= 0).any() and (dev["prim"] <= -2).any()
+
+
 def test_refusals_on_a_scene(gpu_available):
     """On a real handle: an unknown flag and four null buffers are RTC_EINVAL with nothing enqueued; n == 0 is fine."""
     import torch

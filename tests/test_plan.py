@@ -23,8 +23,11 @@ from raytracingc_amd._abi import RtcRenderDesc
 
 KERNEL, RECORD, WAIT = 0, 1, 2
 KEYED_WRITE, READ, WRITE, ATOMIC = 3, 0, 1, 2
-RES_NAMES = ["scratch", "prim", "geoset", "samples", "segslots", "colors", "accum", "caller_segments"]
-KNAMES = ["prep", "super_cull", "tile_cull", "sky", "chain", "accum", "order", "render", "reduce"]
+# rtc_plan.h Res and Kernel, in full and in their order: every tests/test_plan_*.py names resources and kernels from these
+RES_NAMES = ["scratch", "prim", "geoset", "samples", "segslots", "colors", "accum", "caller_segments", "rng_state",
+             "scene_gen", "hit", "rays", "draw_table", "item_draw", "seeds", "radiance", "tmax", "occluded"]
+KNAMES = ["prep", "super_cull", "tile_cull", "sky", "chain", "accum", "order", "render", "reduce", "refit", "first_hit",
+          "trace_rays", "trace_paths", "occluded"]
 REGIONS = ["mask", "pixMask", "weight", "order", "geoList", "superMask", "pixItem", "geoColor"]  # rtc_plan.h Buf
 N_EVENTS = 5 + 2 * 8
 EV_FRAME, EV_GEOMETRY = 3 + 16, 4 + 16

@@ -14,12 +14,10 @@ import pytest
 
 import raytracingc_amd as rt
 from raytracingc_amd._abi import RTC_EINVAL
-from test_plan import (ATOMIC, CAMS, ENVS, KERNEL, KEYED_WRITE, KNAMES, OVERLAP, READ, RES_NAMES, WAIT, WRITE, Scenario,
-                       StreamModel, _check_bound_regions, _desc, _random_launch)
+from test_plan import CAMS, ENVS, KERNEL, KNAMES as KN, OVERLAP, READ, RES_NAMES as RES, WAIT, WRITE, Scenario
+from test_plan import _check_bound_regions, _desc, _random_launch
 from test_plan_update import UpdateScenario
 
-RES = RES_NAMES + ["rng_state", "scene_gen", "hit"]  # rtc_plan.h Res
-KN = KNAMES + ["refit", "first_hit"]                 # rtc_plan.h Kernel
 R_SCRATCH, R_PRIM, R_GEOSET, R_SAMPLES, R_COLORS, R_ACCUM = (RES.index(k) for k in
                                                              ("scratch", "prim", "geoset", "samples", "colors", "accum"))
 R_GEN, R_HIT = RES.index("scene_gen"), RES.index("hit")
@@ -40,10 +38,6 @@ class HitScenario(UpdateScenario):
         self.stale, self.updates = set(), 0
         self.first_hits = set()  # launch numbers
 
-    def kernel_order(self):
-        names = {0: "caller", 1: "cull0", 2: "cull1", 3: "side"}
-        return [(KN[k], names[st]) for kind, st, _, k in self.last_ops if kind == KERNEL]
-
     def first_hit(self, d, stream, ids, cam):
         assert self.L.rtc_plan_sim_set_first_hit(self.h, *ids) == 0
         self.first_hits.add(self.n)
@@ -57,28 +51,6 @@ class HitScenario(UpdateScenario):
         """The footprint rows (resource, access, id, lo, hi) of one launch, of one of its kernels."""
         return [(a[1], a[2], a[3], a[4], a[5]) for a in self.accesses
                 if a[7] == launch and (kernel is None or a[8] == kernel)]
-
-    def hazards(self, limit=5):
-        """test_plan.Scenario.hazards, naming the kernels and resources from this file's lists."""
-        found, by_res = [], {}
-        for a in self.accesses:
-            by_res.setdefault((a[1], a[3]), []).append(a)
-        for lst in by_res.values():
-            for j, b in enumerate(lst):
-                for a in lst[:j]:
-                    if a[0] is b[0] or a[5] <= b[4] or b[5] <= a[4]:
-                        continue
-                    ka, kb = a[2], b[2]
-                    if (ka == READ and kb == READ) or (ka == ATOMIC and kb == ATOMIC):
-                        continue
-                    if ka == KEYED_WRITE and kb == KEYED_WRITE and a[6] == b[6]:
-                        continue
-                    if StreamModel.before(a[0], b[0]):
-                        continue
-                    found.append((RES[a[1]], a[3], (a[7], KN[a[8]]), (b[7], KN[b[8]])))
-                    if len(found) >= limit:
-                        return found
-        return found
 
 
 def _kernels(sc):

@@ -1,4 +1,4 @@
-"""The planner's side of an occlusion query (rtc_occluded_async; rtc_plan.h plan_occluded), on the CPU through
+"""The planner's side of an occlusion query (rtc_occluded_async; rtc_plan.h plan_query), on the CPU through
 rtc_plan_sim_occluded: one kernel (number 13) on the caller's stream that reads the current generation of the scene
 records, the caller's rays and limits and writes the bytes and the counter asked for, and a planner state that is the same
 afterwards.  tests/test_plan.py's checker (vector clocks over the planned operations, unchanged) covers it beside pipelined
@@ -15,13 +15,11 @@ import pytest
 
 import raytracingc_amd as rt
 from raytracingc_amd._abi import RTC_EINVAL
-from test_plan import ATOMIC, CAMS, ENVS, KERNEL, KEYED_WRITE, OVERLAP, READ, WRITE, StreamModel, _desc, _random_launch
+from test_plan import ATOMIC, CAMS, ENVS, KERNEL, KNAMES as KN, OVERLAP, READ, RES_NAMES as RES, WRITE, _desc, _random_launch
 from test_plan_first_hit import HitScenario, _random_first_hit
-from test_plan_trace_paths import KN as KN_PATHS, RES as RES_PATHS, PathScenario, _random_paths
+from test_plan_trace_paths import PathScenario, _random_paths
 from test_plan_trace_rays import RAYS, STREAM, _random_query
 
-RES = RES_PATHS + ["tmax", "occluded"]  # rtc_plan.h Res
-KN = KN_PATHS + ["occluded"]             # rtc_plan.h Kernel
 R_SEG, R_GEN, R_RAYS = RES.index("caller_segments"), RES.index("scene_gen"), RES.index("rays")
 R_TMAX, R_OCC = RES.index("tmax"), RES.index("occluded")
 K_RAYS, K_PATHS, K_OCC = KN.index("trace_rays"), KN.index("trace_paths"), KN.index("occluded")
@@ -82,28 +80,6 @@ class OccScenario(PathScenario):
                KN[a[8]] not in ("refit", "trace_rays", "trace_paths", "occluded")}
         assert len(ids) == 1, ids
         return ids.pop()
-
-    def hazards(self, limit=5):
-        """test_plan.Scenario.hazards, naming the kernels and resources from this file's lists."""
-        found, by_res = [], {}
-        for a in self.accesses:
-            by_res.setdefault((a[1], a[3]), []).append(a)
-        for lst in by_res.values():
-            for j, b in enumerate(lst):
-                for a in lst[:j]:
-                    if a[0] is b[0] or a[5] <= b[4] or b[5] <= a[4]:
-                        continue
-                    ka, kb = a[2], b[2]
-                    if (ka == READ and kb == READ) or (ka == ATOMIC and kb == ATOMIC):
-                        continue
-                    if ka == KEYED_WRITE and kb == KEYED_WRITE and a[6] == b[6]:
-                        continue
-                    if StreamModel.before(a[0], b[0]):
-                        continue
-                    found.append((RES[a[1]], a[3], (a[7], KN[a[8]]), (b[7], KN[b[8]])))
-                    if len(found) >= limit:
-                        return found
-        return found
 
 
 def _random_occluded(rng):

@@ -1,4 +1,4 @@
-"""The planner's side of a ray query (rtc_trace_rays_async; rtc_plan.h plan_trace_rays), on the CPU through
+"""The planner's side of a ray query (rtc_trace_rays_async; rtc_plan.h plan_query), on the CPU through
 rtc_plan_sim_trace_rays: one kernel (number 11) on the caller's stream that reads the current generation of the scene
 records and the caller's rays and writes the caller's hit buffers, and a planner state that is the same afterwards.
 tests/test_plan.py's checker (vector clocks over the planned operations, unchanged) covers it beside pipelined and joined
@@ -16,11 +16,9 @@ import pytest
 
 import raytracingc_amd as rt
 from raytracingc_amd._abi import RTC_EINVAL
-from test_plan import ATOMIC, CAMS, ENVS, KERNEL, KEYED_WRITE, OVERLAP, READ, WRITE, StreamModel, _desc, _random_launch
-from test_plan_first_hit import IDS, KN as KN_HIT, RES as RES_HIT, HitScenario, _random_first_hit
+from test_plan import CAMS, ENVS, KERNEL, KNAMES as KN, OVERLAP, READ, RES_NAMES as RES, WRITE, _desc, _random_launch
+from test_plan_first_hit import IDS, HitScenario, _random_first_hit
 
-RES = RES_HIT + ["rays"]   # rtc_plan.h Res
-KN = KN_HIT + ["trace_rays"]  # rtc_plan.h Kernel
 R_GEN, R_HIT, R_RAYS = RES.index("scene_gen"), RES.index("hit"), RES.index("rays")
 K_TRACE = KN.index("trace_rays")
 assert (R_GEN, R_HIT, R_RAYS, K_TRACE) == (9, 10, 11, 11)
@@ -77,28 +75,6 @@ class TraceScenario(HitScenario):
         ids = {a[3] for a in self.accesses if a[7] == self.n - 1 and a[1] == R_GEN and KN[a[8]] not in ("refit", "trace_rays")}
         assert len(ids) == 1, ids
         return ids.pop()
-
-    def hazards(self, limit=5):
-        """test_plan.Scenario.hazards, naming the kernels and resources from this file's lists."""
-        found, by_res = [], {}
-        for a in self.accesses:
-            by_res.setdefault((a[1], a[3]), []).append(a)
-        for lst in by_res.values():
-            for j, b in enumerate(lst):
-                for a in lst[:j]:
-                    if a[0] is b[0] or a[5] <= b[4] or b[5] <= a[4]:
-                        continue
-                    ka, kb = a[2], b[2]
-                    if (ka == READ and kb == READ) or (ka == ATOMIC and kb == ATOMIC):
-                        continue
-                    if ka == KEYED_WRITE and kb == KEYED_WRITE and a[6] == b[6]:
-                        continue
-                    if StreamModel.before(a[0], b[0]):
-                        continue
-                    found.append((RES[a[1]], a[3], (a[7], KN[a[8]]), (b[7], KN[b[8]])))
-                    if len(found) >= limit:
-                        return found
-        return found
 
 
 def _random_query(rng):

@@ -15,12 +15,9 @@ import random
 import numpy as np
 import pytest
 
-from test_plan import (CAMS, ENVS, KERNEL, KEYED_WRITE, KNAMES, OVERLAP, READ, RES_NAMES, WAIT, ATOMIC, Scenario,
-                       StreamModel, _desc, _random_launch)
+from test_plan import CAMS, ENVS, KERNEL, KNAMES as KN, OVERLAP, RES_NAMES as RES, WAIT, Scenario, _desc, _random_launch
 
-RES = RES_NAMES + ["rng_state", "scene_gen"]  # rtc_plan.h Res
 RES_SCENE_GEN = RES.index("scene_gen")
-KN = KNAMES + ["refit"]
 K_REFIT = KN.index("refit")
 EV_SKY_DONE0, EV_GEO_DONE0, SLOTS = 3, 3 + 8, 8
 
@@ -74,28 +71,6 @@ class UpdateScenario(Scenario):
         ids = {a[3] for a in self.accesses if a[7] == self.n - 1 and a[1] == RES_SCENE_GEN and a[8] != K_REFIT}
         assert len(ids) == 1, ids
         return ids.pop()
-
-    def hazards(self, limit=5):
-        """test_plan.Scenario.hazards with this file's resource and kernel names (the refit kernel, the generations)."""
-        found, by_res = [], {}
-        for a in self.accesses:
-            by_res.setdefault((a[1], a[3]), []).append(a)
-        for (res, ident), lst in by_res.items():
-            for j, b in enumerate(lst):
-                for a in lst[:j]:
-                    if a[0] is b[0] or a[5] <= b[4] or b[5] <= a[4]:
-                        continue
-                    ka, kb = a[2], b[2]
-                    if (ka == READ and kb == READ) or (ka == ATOMIC and kb == ATOMIC):
-                        continue
-                    if ka == KEYED_WRITE and kb == KEYED_WRITE and a[6] == b[6]:
-                        continue
-                    if StreamModel.before(a[0], b[0]):
-                        continue
-                    found.append((RES[res], ident, (a[7], KN[a[8]]), (b[7], KN[b[8]])))
-                    if len(found) >= limit:
-                        return found
-        return found
 
 
 def _sequences(seed, fault=0):
