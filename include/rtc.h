@@ -97,6 +97,11 @@ typedef struct RtcRenderDesc {
 #define RTC_F_NO_DRAW_CACHE 0x4000 /* the launch neither reads nor fills the scene's draw cache (rtc_scene_set_draw_cache):
                                       rtc_render_chain computes every hit draw as before the cache.  A/B timing and
                                       tests.  Same frame bit for bit. */
+#define RTC_F_WAVE_PER_RAY  0x20000 /* rtc_trace_paths_async / rtc_trace_paths only (every other entry: RTC_EINVAL): one
+                                       wave per ray, the ray's samples on the wave's lanes at RNG offsets 7 draws apart
+                                       (lane j starts 7 j draws after the ray's state), instead of one
+                                       lane per ray.  Same radiance, seeds and segment count bit for bit; for few rays
+                                       with many samples.  The choice is the caller's. */
 #define RTC_F_OVERLAP       0x800 /* frame pipelining (device-resident split only): the launch does not make
                                      `stream` wait for its sky pass, so the next launches on the same scene render
                                      (scratch in 8 slots) while this one's sky pass still runs.  A later overlapped
@@ -394,14 +399,19 @@ int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trian
  * normalised, dst in units of dir, the EPSILON tests at the caller's scale; bounce directions come out of the reference's
  * own lerp.  dSegments, where not null, is one device u64 to which the launch atomically adds its number of
  * calculateRayCollision calls.
- * The samples of one ray are sequential: they form one RNG chain, and the kernel is one lane per ray.  A caller who wants
- * many samples of one ray quickly passes that ray many times with different seeds and averages.
+ * The samples of one ray form one RNG chain.  By default the kernel is one lane per ray and runs them one after the
+ * other.  With RTC_F_WAVE_PER_RAY it is one wave per ray: a hit draws exactly 7 values and a miss none, so every sample
+ * starts at the seed advanced by a multiple of 7 draws; 64 lanes evaluate the candidates at 64 consecutive such offsets
+ * and the wave adds, in the reference's order, those the chain really reaches.  The outputs are the same
+ * bit for bit; only the kernel differs, and a frame's passes may mix calls with and without the flag.  It is meant for
+ * few rays with many samples (DESIGN §3.14 has the measurements); no choice is made for the caller.
  * `scene` and `d` are host pointers, borrowed for the call.  dRays (n Rays), dSeeds (n) and dRadiance (3 n floats) are
  * required DEVICE pointers on the scene's device; dSeedsOut (n) may be null and may be dSeeds (in place); dRays aliases
  * no output.  With sampleFirst > 0 the caller passes the previous call's dSeedsOut as dSeeds and the same dRadiance:
  * calls over [0, a), [a, b), .., [z, spp) leave the radiance, the seeds and the segment count of one call of spp samples,
  * bit for bit.
- * d->flags: 0 (the cluster hierarchy) or RTC_F_NO_CLUSTER_CULL (every record in reference order, the same values).
+ * d->flags: 0 (the cluster hierarchy), RTC_F_NO_CLUSTER_CULL (every record in reference order, the same values),
+ * RTC_F_WAVE_PER_RAY (above), or both.
  * Asynchronous on `stream` and complete there, under rtc_trace_rays_async's rules word for word: it reads the generation
  * current when it is enqueued, may come between RTC_F_OVERLAP launches, between passes and after an update, uses no
  * scratch, primary record, counter set, stream or event of the scene's, leaves the one-shot events,
@@ -409,12 +419,13 @@ int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trian
  * device.  n == 0: returns 0, nothing enqueued.
  * RTC_EINVAL, with nothing enqueued, checked before any device call and before `s` is read: a null s, scene, dRays,
  * dSeeds, d or dRadiance; n > 0x7fffffff; spp <= 0; sampleFirst < 0, sampleCount <= 0 or sampleFirst + sampleCount > spp;
- * a flag other than RTC_F_NO_CLUSTER_CULL (RTC_F_DEBUG_BOUNCES included: calcDebugColor is not offered for caller rays). */
+ * a flag other than RTC_F_NO_CLUSTER_CULL and RTC_F_WAVE_PER_RAY (RTC_F_DEBUG_BOUNCES included: calcDebugColor is not
+ * offered for caller rays). */
 typedef struct RtcPathDesc {
     int spp;            /* the weight's accumulationCount: every sample is weighted (float)(1. / spp) (main.c:99) */
     int maxBounce;      /* calcColor's maxBounce; <= 0: no segment is traced, a sample is +0 and draws nothing */
     int trianglesOnly;
-    int flags;          /* 0 or RTC_F_NO_CLUSTER_CULL */
+    int flags;          /* 0, RTC_F_NO_CLUSTER_CULL, RTC_F_WAVE_PER_RAY or both */
     int sampleFirst, sampleCount; /* this call evaluates samples [sampleFirst, sampleFirst + sampleCount) of spp */
 } RtcPathDesc;
 int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene, const Ray *dRays, const unsigned int *dSeeds,
@@ -549,7 +560,9 @@ int rtc_plan_sim_trace_rays(RtcPlanSim *sim, unsigned long long stream, unsigned
  * (resource 15, id = `radiance`), writes the radiance and, where asked for (an identity that is not 0), the seeds
  * (resource 14, id = `seedsOut`) and the caller's segment counter (resource 7, an atomic add), in that order -- then one
  * u64 record (~0, 0, the generation read, 0, 0, 0).  The planner's state is left as it was.  RTC_EINVAL where the entry
- * point refuses: `rays`, `seeds` or `radiance` 0, sampleFirst < 0, a flag other than RTC_F_NO_CLUSTER_CULL. */
+ * point refuses: `rays`, `seeds` or `radiance` 0, sampleFirst < 0, a flag other than RTC_F_NO_CLUSTER_CULL and
+ * RTC_F_WAVE_PER_RAY (which plans the same operation and the same records: only the kernel behind the number
+ * differs). */
 int rtc_plan_sim_trace_paths(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays,
                              unsigned long long seeds, unsigned long long radiance, unsigned long long seedsOut,
                              unsigned long long segments, int sampleFirst, int flags, int *ops, int maxOps,

@@ -36,6 +36,7 @@ from ._abi import (  # noqa: F401
     RTC_F_NO_DRAW_CACHE,
     RTC_F_NO_REORDER,
     RTC_F_NO_TILE_CULL,
+    RTC_F_WAVE_PER_RAY,
     RTC_SEGMENT_COUNTERS,
     RTC_EBUSY,
     RTC_EINVAL,
@@ -422,8 +423,10 @@ class DeviceScene:
         with the ray given -- acc = acc + calcColor(ray, trianglesOnly, maxBounce, scene) * (float)(1. / spp) -- into
         radiance_ptr (float32 [n, 3]; read first when first > 0), the RNG states into seeds_out_ptr (0: not wanted; may be
         seeds_ptr) and the number of calculateRayCollision calls added to the u64 at segments_ptr (0: not wanted).  The
-        samples of one ray are sequential.  Asynchronous on `stream`, complete there; the scene's ordering state and
-        events stay as they were."""
+        samples of one ray are one RNG chain: one lane per ray runs them in turn, or with flags=RTC_F_WAVE_PER_RAY (alone
+        or with RTC_F_NO_CLUSTER_CULL) one wave per ray runs 64 candidate samples at a time -- the same values bit for bit,
+        meant for few rays with many samples; the choice is the caller's.  Asynchronous on `stream`, complete there; the
+        scene's ordering state and events stay as they were."""
         d = RtcPathDesc(int(spp), int(max_bounce), int(bool(triangles_only)), int(flags), int(first),
                         int(spp) - int(first) if count is None else int(count))
         check(lib().rtc_trace_paths_async(self._h, C.byref(scene), _vp(rays_ptr), _vp(seeds_ptr), n, C.byref(d),
@@ -436,7 +439,8 @@ class DeviceScene:
         """The radiance along `rays` as host arrays: {"radiance": float32 [n, 3], "seeds": uint32 [n]} (the RNG states
         after the samples) plus "segments": int (the calculateRayCollision calls) when asked for -- trace_paths_async's
         values for samples [first, first + count) of spp (count None: the rest).  With first > 0 `radiance` is the
-        accumulator so far and `seeds` the states the previous call returned.  `rays` and `seeds` (and `radiance`):
+        accumulator so far and `seeds` the states the previous call returned.  flags: 0, RTC_F_NO_CLUSTER_CULL,
+        RTC_F_WAVE_PER_RAY (a wave per ray instead of a lane; the same values) or both.  `rays` and `seeds` (and `radiance`):
         numpy arrays (RAY_DT [n] or float32 [n, 6]; uint32 [n]; float32 [n, 3]), which take the synchronous host entry
         rtc_trace_paths; or torch tensors on the scene's device, read in place by rtc_trace_paths_async on torch's
         current stream there (the inputs are left as they were) -- the results are numpy arrays in both cases."""

@@ -120,6 +120,7 @@ RTC_F_OVERLAP = 0x800
 RTC_F_HOST_ROWS = 0x1000
 RTC_F_SPLIT_SPHERES = 0x2000  # sphere launches take the split launch whatever the scene's gate says (A/B, tests)
 RTC_F_NO_DRAW_CACHE = 0x4000  # the launch neither reads nor fills the scene's draw cache (A/B, tests)
+RTC_F_WAVE_PER_RAY = 0x20000  # trace_paths only: one wave per ray, its samples on the lanes (same values bit for bit)
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007

@@ -770,8 +770,10 @@ extern "C" int rtc_plan_sim_trace_paths(RtcPlanSim *s, unsigned long long stream
                                         unsigned long long seedsOut, unsigned long long segments, int sampleFirst,
                                         int flags, int *ops, int maxOps, unsigned long long *fp, int maxFp)
 {
-    /* refused as rtc_trace_paths_async refuses it */
-    if (!s || !ops || !rays || !seeds || !radiance || sampleFirst < 0 || (flags & ~RTC_F_NO_CLUSTER_CULL))
+    /* refused as rtc_trace_paths_async refuses it.  RTC_F_WAVE_PER_RAY changes the kernel alone: the same operation, the
+     * same footprint */
+    if (!s || !ops || !rays || !seeds || !radiance || sampleFirst < 0 ||
+        (flags & ~(RTC_F_NO_CLUSTER_CULL | RTC_F_WAVE_PER_RAY)))
         return RTC_EINVAL;
     (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
     return sim_query(s, rtcplan::kKTracePaths, ops, maxOps, fp, maxFp,

@@ -677,10 +677,11 @@ static int no_refusal() { return 0; }
 
 /* The refusals of a query's two entries, before any device call and before `s` is read, in the order every query keeps:
  * the scene, the entry's own arguments (nullArgument; noneAsked: the text when no output is asked for, else null), the
- * ray count, whatever else is the query's own (`own`), the flags.  `noun`: "a ray", "a path", "an occlusion". */
+ * ray count, whatever else is the query's own (`own`), the flags (`allowed`: the query's own whitelist, `allowedNames` its
+ * text).  `noun`: "a ray", "a path", "an occlusion". */
 template <class Own>
 static int refuse_query(const char *who, const char *noun, const RtcDeviceScene *s, bool nullArgument,
-                        const char *noneAsked, size_t n, int flags, Own own)
+                        const char *noneAsked, size_t n, int flags, int allowed, const char *allowedNames, Own own)
 {
     if (!s)
         return rtc_fail(RTC_EINVAL, "%s: null scene", who);
@@ -692,11 +693,12 @@ static int refuse_query(const char *who, const char *noun, const RtcDeviceScene 
         return rtc_fail(RTC_EINVAL, "%s: %zu rays (at most 2147483647 in one call)", who, n);
     if (const int rc = own())
         return rc;
-    if (flags & ~RTC_F_NO_CLUSTER_CULL)
-        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (%s query takes RTC_F_NO_CLUSTER_CULL and no other flag)", who, flags,
-                        noun);
+    if (flags & ~allowed)
+        return rtc_fail(RTC_EINVAL, "%s: flags 0x%x (%s query takes %s and no other flag)", who, flags, noun, allowedNames);
     return 0;
 }
+/* the whitelist of a query that has one kernel */
+static const char *const kCullFlagOnly = "RTC_F_NO_CLUSTER_CULL";
 
 static void set_mats(OccludedArgs &, const DevMat *) {} /* (an occlusion query reads no material) */
 template <class Args>
@@ -707,10 +709,12 @@ static void set_mats(Args &a, const DevMat *mats)
 
 /* From a query's args, its own fields filled, to its kernel enqueued on `stream` (n > 0).  The planner names the generation
  * and the one operation (rtc_plan.h plan_query); the ordering state stays as it is (TracePlan::after == s->plan), and so do
- * the hooks, the timing events, the chain report and the draw cache. */
+ * the hooks, the timing events, the chain report and the draw cache.  `raysPerGroup`: how many rays a workgroup of the
+ * table's kernels takes (kBlock: a lane each; kBlock / 64: a wave each, at most 2^29 workgroups for 2^31 - 1 rays). */
 template <class Args>
 static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, void (*const (&table)[2][2])(Args), Args &a,
-                         const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream)
+                         const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream,
+                         size_t raysPerGroup = kBlock)
 {
     RtcDeviceGuard guard(s->device);
     if (!guard.ok())
@@ -728,7 +732,8 @@ static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, v
         if (op.kind != rtcplan::kOpKernel || op.kernel != kernel || op.stream != rtcplan::kStCaller)
             return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
         hipLaunchKernelGGL(table[a.sphereCount > 0][!(flags & RTC_F_NO_CLUSTER_CULL)],
-                           dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, a);
+                           dim3((unsigned)((n + raysPerGroup - 1) / raysPerGroup)), dim3(kBlock), 0, (hipStream_t)stream,
+                           a);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -786,7 +791,7 @@ static int check_trace_rays(const char *who, const RtcDeviceScene *s, const void
                         out[0] || out[1] || out[2] || out[3]
                             ? nullptr
                             : "no buffer asked for (prim, depth, normal and albedo are all null)",
-                        n, flags, no_refusal);
+                        n, flags, RTC_F_NO_CLUSTER_CULL, kCullFlagOnly, no_refusal);
 }
 
 extern "C" int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, int trianglesOnly, int flags,
@@ -831,7 +836,8 @@ extern "C" int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n
 static int check_trace_paths(const char *who, const RtcDeviceScene *s, const Scene *scene, const void *rays,
                              const void *seeds, size_t n, const RtcPathDesc *d, const void *radiance)
 {
-    return refuse_query(who, "a path", s, !scene || !rays || !seeds || !d || !radiance, nullptr, n, d ? d->flags : 0, [&] {
+    return refuse_query(who, "a path", s, !scene || !rays || !seeds || !d || !radiance, nullptr, n, d ? d->flags : 0,
+                        RTC_F_NO_CLUSTER_CULL | RTC_F_WAVE_PER_RAY, "RTC_F_NO_CLUSTER_CULL, RTC_F_WAVE_PER_RAY", [&] {
         if (d->spp <= 0)
             return rtc_fail(RTC_EINVAL, "%s: spp %d", who, d->spp);
         if (d->sampleFirst < 0 || d->sampleCount <= 0 || d->sampleFirst > d->spp - d->sampleCount)
@@ -859,6 +865,13 @@ extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene
     static void (*const kTracePaths[2][2])(TracePathsArgs) = {
         {rtc_trace_paths<false, false>, rtc_trace_paths<false, true>},
         {rtc_trace_paths<true, false>, rtc_trace_paths<true, true>}};
+    /* RTC_F_WAVE_PER_RAY: the same operation, outputs and ordering; a wave per ray (rtc_trace_paths.h) */
+    static void (*const kTracePathsWave[2][2])(TracePathsArgs) = {
+        {rtc_trace_paths_wave<false, false>, rtc_trace_paths_wave<false, true>},
+        {rtc_trace_paths_wave<true, false>, rtc_trace_paths_wave<true, true>}};
+    if (d->flags & RTC_F_WAVE_PER_RAY)
+        return enqueue_query(who, s, rtcplan::kKTracePaths, kTracePathsWave, a, dRays, n, d->trianglesOnly, d->flags,
+                             stream, kBlock / 64);
     return enqueue_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags, stream);
 }
 
@@ -890,7 +903,7 @@ static int check_occluded(const char *who, const RtcDeviceScene *s, const void *
 {
     return refuse_query(who, "an occlusion", s, !rays,
                         occluded || count ? nullptr : "no output asked for (occluded and count are both null)", n, flags,
-                        no_refusal);
+                        RTC_F_NO_CLUSTER_CULL, kCullFlagOnly, no_refusal);
 }
 
 extern "C" int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *dTMax, size_t n,
@@ -1091,3 +1104,8 @@ template __global__ void rtc_occluded<false, true>(OccludedArgs);
 template __global__ void rtc_occluded<true, true>(OccludedArgs);
 template __global__ void rtc_occluded<false, false>(OccludedArgs);
 template __global__ void rtc_occluded<true, false>(OccludedArgs);
+/* caller-supplied rays: radiance, a wave per ray */
+template __global__ void rtc_trace_paths_wave<false, true>(TracePathsArgs);
+template __global__ void rtc_trace_paths_wave<true, true>(TracePathsArgs);
+template __global__ void rtc_trace_paths_wave<false, false>(TracePathsArgs);
+template __global__ void rtc_trace_paths_wave<true, false>(TracePathsArgs);
