@@ -471,6 +471,50 @@ int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *d
  * (each nullable, not both; *count += the occluded rays).  The same refusals; RTC_ENODEV without a GPU. */
 int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly, int flags,
                  unsigned char *occluded, unsigned long long *count);
+/* A coherent order for caller-supplied rays.  The three queries above put 64 consecutive rays of the
+ * caller's buffer in one wave, so their speed depends on the order the rays are stored in; these entries sort rays by a
+ * 30-bit coherence key on the device and apply the order.  No query kernel and no value changes: an ordered query is
+ * rtc_ray_order_async, rtc_gather_async of its inputs, the query on the gathered buffers, rtc_scatter_async of its
+ * outputs -- a ray's result depends on the ray (and its seed) alone, so every output is the same bit for bit.
+ * The key, all arithmetic f32, operation by operation, no contraction; bounds lo[3], hi[3] (the caller's, or the scene's:
+ * the box of the upload's triangle vertices and sphere extents centre -+ r, rtc_scene_bounds; a refit does not move it):
+ *   per axis a: scale_a = 32.f / (hi_a - lo_a) when hi_a > lo_a and the quotient is finite, else 0.f (host, once);
+ *               t = (pos_a - lo_a) * scale_a;  c_a = !(t >= 0) ? 0 : t >= 31.f ? 31 : (int)t
+ *   cell (15 bits, Morton): bit b of c_x, c_y, c_z at bits 3 b, 3 b + 1, 3 b + 2
+ *   ax, ay, az = fabsf(dir.*);  L = (ax + ay) + az;  px = ax / L, py = ay / L (correctly rounded)
+ *   q(p) = !(p >= 0) ? 0 : p * 64.f >= 63.f ? 63 : (int)(p * 64.f)
+ *   oct = (dir.x < 0) | (dir.y < 0) << 1 | (dir.z < 0) << 2          (-0 and NaN: not negative)
+ *   key = cell << 15 | oct << 12 | q(py) << 6 | q(px)                  (< 2^30)
+ * rtc_ray_keys_host states it on the host (no GPU); the device's keys are the same bits.
+ * rtc_ray_order_async: dOrder[0, n) becomes the permutation of [0, n) that sorts dRays by key, STABLE (equal keys keep
+ * ascending index) -- a function of the rays and bounds alone; dKeys (nullable) receives key(dRays[i]) at i.  bounds: 6
+ * HOST floats lo, hi, or NULL for the scene's.  dScratch: rtc_ray_order_scratch_bytes(n) bytes of device memory, 16-byte
+ * aligned; all temporary storage.  An LSD radix sort of (key, index) pairs over the 30 bits, 8 bits a pass, without atomics.
+ * Asynchronous on `stream`, complete there: no allocation, no synchronisation, no host read of device memory; nothing is
+ * written outside dOrder[0, n), dKeys[0, n) and the scratch's stated size; the rays are only read.  It reads nothing of
+ * the scene on the device (only its device number and bounds on the host), takes no part in the launch planner, leaves
+ * the scene's ordering state, hooks, chain report and draw cache alone and restores the caller's current device.
+ * n == 0: returns 0, nothing enqueued.  RTC_EINVAL, checked before any device call and before `s` is read: a null s,
+ * dRays, dOrder or dScratch; n > 0x7fffffff; scratchBytes too small; dScratch not 16-byte aligned. */
+int rtc_scene_bounds(const RtcDeviceScene *s, float lo[3], float hi[3]);
+size_t rtc_ray_order_scratch_bytes(size_t n); /* a multiple of 16, monotone in n */
+/* The sort's shape (host only): the keys a sort workgroup takes (B) and the workgroup counts one scan workgroup takes per
+ * step of its loop (G) -- n = B +- 1, 2 B + 1 and G B + 1 are the sizes at which the sort takes another path. */
+int rtc_ray_order_shape(int *keysPerGroup, int *scanGroups);
+int rtc_ray_order_async(const RtcDeviceScene *s, const Ray *dRays, size_t n, const float *bounds,
+                        unsigned *dOrder, unsigned *dKeys, void *dScratch, size_t scratchBytes, void *stream);
+/* The same for HOST arrays, synchronous, staged like rtc_trace_rays (keys nullable).  RTC_ENODEV without a GPU. */
+int rtc_ray_order(const RtcDeviceScene *s, const Ray *rays, size_t n, const float *bounds, unsigned *order,
+                  unsigned *keys);
+int rtc_ray_keys_host(const Ray *rays, size_t n, const float lo[3], const float hi[3], unsigned *keys);
+/* Apply an order on the current device (like rtc_copy_async), asynchronously on `stream`: n elements of elemBytes each,
+ * gather dst[i] = src[order[i]], scatter dst[order[i]] = src[i]; dOrder holds values below n (a permutation, for a scatter
+ * that leaves no element unwritten).  elemBytes is 1 -- byte loads and stores, any alignment, as rtc_occluded_async's byte
+ * buffer -- or a multiple of 4 up to 64 -- dword copies, consecutive lanes on consecutive dwords; 4-byte aligned buffers.
+ * dst must not alias src.  RTC_EINVAL: another elemBytes, a null pointer, n > 0x7fffffff, dDst == dSrc, a misaligned
+ * dword buffer.  n == 0: returns 0, nothing enqueued. */
+int rtc_gather_async(void *dDst, const void *dSrc, const unsigned *dOrder, size_t n, size_t elemBytes, void *stream);
+int rtc_scatter_async(void *dDst, const void *dSrc, const unsigned *dOrder, size_t n, size_t elemBytes, void *stream);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */

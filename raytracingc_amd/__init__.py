@@ -68,6 +68,7 @@ __all__ = [
     "render", "render_multi", "DeviceScene", "vec3ToColor", "write_bmp", "rayTriangle", "raySphere",
     "getEnvironmentLight", "random_sequences", "device_count", "lib", "TRIANGLE_DT", "SPHERE_DT", "RAY_DT",
     "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress", "scene_records_host", "RECORD_ARRAYS",
+    "ray_keys_host", "ray_order_scratch_bytes", "gather_async", "scatter_async",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -231,6 +232,43 @@ def _current_stream_of(device):
         st.synchronize()
 
 
+def _host_order(who: str, order, n: int) -> np.ndarray:
+    """A caller's precomputed order as host indices [n] (every value below n: numpy's indexing would refuse others).  That
+    it is a permutation is not checked: the scatters start from zeros, so a repeated index costs values, not safety."""
+    if hasattr(order, "data_ptr"):
+        order = order.detach().cpu().numpy()
+    idx = np.ascontiguousarray(np.asarray(order).reshape(-1)).astype(np.intp)
+    if len(idx) != n or (n and (idx.min() < 0 or idx.max() >= n)):
+        raise ValueError(f"{who}: order must hold {n} indices below {n}")
+    return idx
+
+
+def _device_order(who: str, order, n: int, device):
+    """A caller's precomputed order as a contiguous int32 tensor [n] on `device`, every value below n (the permutation
+    kernels index device memory with it, so it is checked here: one reduction and a host read)."""
+    import torch
+
+    if not hasattr(order, "data_ptr"):
+        order = torch.from_numpy(_host_order(who, order, n).astype(np.int32))
+    order = order.reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+    if order.numel() != n or (n and (int(order.min()) < 0 or int(order.max()) >= n)):
+        raise ValueError(f"{who}: order must hold {n} indices below {n}")
+    return order
+
+
+def _permuted(scatter: bool, src, order, n: int, elem_bytes: int, stream):
+    """A new tensor like `src` (contiguous, on the device, n elements of elem_bytes) holding src[order] (gather), or with
+    src[i] at order[i] (scatter), enqueued on `stream`.  A scatter's destination starts zeroed: an order that is no
+    permutation leaves zeros, not stale memory, in the elements it never names."""
+    import torch
+
+    dst = torch.zeros_like(src) if scatter else torch.empty_like(src)
+    if n:
+        (scatter_async if scatter else gather_async)(dst.data_ptr(), src.data_ptr(), order.data_ptr(), n, elem_bytes,
+                                                     stream)
+    return dst
+
+
 RECORD_ARRAYS = ("tris", "mats", "spheres", "clTris", "clusters", "chunks")  # 64, 32, 48, 64, 32, 32 bytes per record
 _RECORD_WORDS = (16, 8, 12, 16, 8, 8)
 
@@ -386,12 +424,17 @@ class DeviceScene:
                                          _vp(stream)), "rtc_trace_rays_async")
 
     def trace_rays(self, rays, triangles_only: bool = False, want=("prim", "depth", "normal", "albedo"),
-                   flags: int = 0) -> dict:
+                   flags: int = 0, order=None) -> dict:
         """The closest hits of `rays` as host arrays, {name: numpy array} for the names in `want`: prim int32 [n], depth
         float32 [n], normal and albedo float32 [n, 3] (trace_rays_async's values).  `rays`: a numpy array of RAY_DT [n]
         or float32 [n, 6] (pos, dir), which takes the synchronous host entry rtc_trace_rays; or a torch tensor on the
         scene's device (float32 [n, 6], or any contiguous tensor of n x 24 bytes), which is read in place by
-        rtc_trace_rays_async on torch's current stream there -- the results are numpy arrays in both cases."""
+        rtc_trace_rays_async on torch's current stream there -- the results are numpy arrays in both cases.
+        `order`: None, the rays are traced in the order given, 64 consecutive rays a wave; True, they are
+        first put in the coherent order of ray_order (the same values, element for element: the rays are gathered, traced
+        and the results scattered back); or a precomputed order (ray_order's, an array or tensor of n indices below n, checked
+        here).  It is meant to be a permutation: with repeated indices the elements no index names come back as zeros and
+        those named twice hold either result."""
         shapes = {"prim": ((), np.int32), "depth": ((), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32)}
         want = tuple(want)
@@ -404,14 +447,26 @@ class DeviceScene:
             kinds = {np.int32: torch.int32, np.float32: torch.float32}
             bufs = {k: torch.zeros((n,) + shapes[k][0], dtype=kinds[shapes[k][1]], device=rays.device) for k in want}
             if n:
+                perm = self._order_for("DeviceScene.trace_rays", order, rays, n)
                 with _current_stream_of(rays.device) as st:
-                    self.trace_rays_async(rays.data_ptr(), n, triangles_only, flags,
+                    src = rays if perm is None else _permuted(False, rays, perm, n, 24, st)
+                    self.trace_rays_async(src.data_ptr(), n, triangles_only, flags,
                                           *(bufs[k].data_ptr() if k in bufs else 0 for k in shapes), stream=st)
+                    if perm is not None:
+                        bufs = {k: _permuted(True, b, perm, n, b.element_size() * (b.numel() // n), st)
+                                for k, b in bufs.items()}
             return {k: bufs[k].cpu().numpy() for k in want}
         out = {k: np.zeros((n,) + shapes[k][0], shapes[k][1]) for k in want}
         if n:
+            perm = self._order_for("DeviceScene.trace_rays", order, a, n)
+            if perm is not None:
+                a = np.ascontiguousarray(a[perm])
             check(lib().rtc_trace_rays(self._h, _ptr(a), n, int(bool(triangles_only)), flags,
                                        *(_ptr(out[k]) if k in out else None for k in shapes)), "rtc_trace_rays")
+            if perm is not None:
+                for k, got in out.items():
+                    out[k] = np.zeros_like(got)
+                    out[k][perm] = got
         return out
 
     def trace_paths_async(self, scene: Scene, rays_ptr: int, seeds_ptr: int, n: int, spp: int, max_bounce: int,
@@ -435,7 +490,7 @@ class DeviceScene:
 
     def trace_paths(self, rays, seeds, scene: Scene, spp: int, max_bounce: int, triangles_only: bool = False,
                     flags: int = 0, first: int = 0, count: int | None = None, radiance=None,
-                    segments: bool = False) -> dict:
+                    segments: bool = False, order=None) -> dict:
         """The radiance along `rays` as host arrays: {"radiance": float32 [n, 3], "seeds": uint32 [n]} (the RNG states
         after the samples) plus "segments": int (the calculateRayCollision calls) when asked for -- trace_paths_async's
         values for samples [first, first + count) of spp (count None: the rest).  With first > 0 `radiance` is the
@@ -443,7 +498,11 @@ class DeviceScene:
         RTC_F_WAVE_PER_RAY (a wave per ray instead of a lane; the same values) or both.  `rays` and `seeds` (and `radiance`):
         numpy arrays (RAY_DT [n] or float32 [n, 6]; uint32 [n]; float32 [n, 3]), which take the synchronous host entry
         rtc_trace_paths; or torch tensors on the scene's device, read in place by rtc_trace_paths_async on torch's
-        current stream there (the inputs are left as they were) -- the results are numpy arrays in both cases."""
+        current stream there (the inputs are left as they were) -- the results are numpy arrays in both cases.
+        `order`: as trace_rays' -- None, True (ray_order of these rays) or a precomputed order, which the passes of one
+        accumulation can share since their rays do not change; the rays, the seeds and (first > 0) the radiance are
+        gathered, the radiance and the seeds scattered back: the same values element for element, and the same segment
+        count (a sum)."""
         count = int(spp) - int(first) if count is None else int(count)
         if first > 0 and radiance is None:
             raise ValueError("DeviceScene.trace_paths: first > 0 continues an accumulation: pass its radiance")
@@ -464,10 +523,18 @@ class DeviceScene:
             out = torch.zeros(n, dtype=torch.int32, device=rays.device)
             seg = torch.zeros(1, dtype=torch.int64, device=rays.device)
             if n:
+                perm = self._order_for("DeviceScene.trace_paths", order, rays, n)
                 with _current_stream_of(rays.device) as st:
-                    self.trace_paths_async(scene, rays.data_ptr(), seeds.data_ptr(), n, spp, max_bounce, rad.data_ptr(),
+                    src, sds = rays, seeds
+                    if perm is not None:
+                        src, sds = _permuted(False, rays, perm, n, 24, st), _permuted(False, seeds, perm, n, 4, st)
+                        if first > 0:
+                            rad = _permuted(False, rad, perm, n, 12, st)
+                    self.trace_paths_async(scene, src.data_ptr(), sds.data_ptr(), n, spp, max_bounce, rad.data_ptr(),
                                            triangles_only, flags, first, count, out.data_ptr(),
                                            seg.data_ptr() if segments else 0, stream=st)
+                    if perm is not None:
+                        rad, out = _permuted(True, rad, perm, n, 12, st), _permuted(True, out, perm, n, 4, st)
             res = {"radiance": rad.cpu().numpy(), "seeds": out.cpu().numpy().view(np.uint32)}
             if segments:
                 res["segments"] = int(seg.cpu().numpy()[0])
@@ -485,9 +552,16 @@ class DeviceScene:
         out = np.zeros(n, np.uint32)
         seg = C.c_ulonglong(0)
         if n:
+            perm = self._order_for("DeviceScene.trace_paths", order, a, n)
+            if perm is not None:
+                a, sd, rad = np.ascontiguousarray(a[perm]), np.ascontiguousarray(sd[perm]), np.ascontiguousarray(rad[perm])
             d = RtcPathDesc(int(spp), int(max_bounce), int(bool(triangles_only)), int(flags), int(first), count)
             check(lib().rtc_trace_paths(self._h, C.byref(scene), _ptr(a), _ptr(sd), n, C.byref(d), _ptr(rad), _ptr(out),
                                         C.cast(C.pointer(seg), C.c_void_p) if segments else None), "rtc_trace_paths")
+            if perm is not None:
+                rad_g, out_g = rad, out
+                rad, out = np.zeros_like(rad_g), np.zeros_like(out_g)
+                rad[perm], out[perm] = rad_g, out_g
         res = {"radiance": rad, "seeds": out}
         if segments:
             res["segments"] = int(seg.value)
@@ -504,12 +578,15 @@ class DeviceScene:
         check(lib().rtc_occluded_async(self._h, _vp(rays_ptr), _vp(tmax_ptr), n, int(bool(triangles_only)), int(flags),
                                        _vp(occluded_ptr), _vp(count_ptr), _vp(stream)), "rtc_occluded_async")
 
-    def occluded(self, rays, tmax=None, triangles_only: bool = False, flags: int = 0, count: bool = False):
+    def occluded(self, rays, tmax=None, triangles_only: bool = False, flags: int = 0, count: bool = False,
+                 order=None):
         """occluded_async's answers as a numpy bool [n], or (bool [n], int) with count=True (the number of occluded rays,
         counted by the kernel).  `rays`: a numpy array of RAY_DT [n] or float32 [n, 6] (pos, dir), which takes the
         synchronous host entry rtc_occluded; or a torch tensor on the scene's device (float32 [n, 6], or any contiguous
         tensor of n x 24 bytes), read in place by rtc_occluded_async on torch's current stream there.  `tmax`: None (no
-        limit), a Python float (the same limit for every ray) or an array / tensor of n float32."""
+        limit), a Python float (the same limit for every ray) or an array / tensor of n float32.  `order`: as trace_rays' --
+        None, True or a precomputed order; the rays and limits are gathered and the bytes scattered back (the same answers
+        element for element; the count is a sum)."""
         who = "DeviceScene.occluded"
         on_device, a, n = _query_rays(who, rays)
         lim = None
@@ -531,6 +608,7 @@ class DeviceScene:
         if on_device:
             import torch
 
+            perm = self._order_for(who, order, rays, n)
             with _current_stream_of(rays.device) as st:
                 if lim is not None:
                     if isinstance(lim, np.ndarray):
@@ -538,15 +616,88 @@ class DeviceScene:
                     lim = lim.to(device=rays.device, dtype=torch.float32).contiguous()
                 occ = torch.zeros(n, dtype=torch.uint8, device=rays.device)
                 cnt = torch.zeros(1, dtype=torch.int64, device=rays.device)
-                self.occluded_async(rays.data_ptr(), n, lim.data_ptr() if lim is not None else 0, triangles_only, flags,
+                src = rays
+                if perm is not None:
+                    src = _permuted(False, rays, perm, n, 24, st)
+                    lim = _permuted(False, lim, perm, n, 4, st) if lim is not None else None
+                self.occluded_async(src.data_ptr(), n, lim.data_ptr() if lim is not None else 0, triangles_only, flags,
                                     occ.data_ptr(), cnt.data_ptr() if count else 0, stream=st)
+                if perm is not None:
+                    occ = _permuted(True, occ, perm, n, 1, st)
             res = occ.cpu().numpy().astype(bool)
             return (res, int(cnt.cpu().numpy()[0])) if count else res
         occ = np.zeros(n, np.uint8)
         cnt = C.c_ulonglong(0)
+        perm = self._order_for(who, order, a, n)
+        if perm is not None:
+            a, lim = np.ascontiguousarray(a[perm]), None if lim is None else np.ascontiguousarray(lim[perm])
         check(lib().rtc_occluded(self._h, _ptr(a), _ptr(lim), n, int(bool(triangles_only)), int(flags), _ptr(occ),
                                  C.cast(C.pointer(cnt), C.c_void_p) if count else None), "rtc_occluded")
+        if perm is not None:
+            occ_g, occ = occ, np.zeros_like(occ)
+            occ[perm] = occ_g
         return (occ.astype(bool), int(cnt.value)) if count else occ.astype(bool)
+
+    def bounds(self):
+        """rtc_scene_bounds: (lo, hi), float32 [3] each -- the box of the upload's triangle vertices and sphere extents
+        (centre -+ r), the default bounds of the ray order's key.  An update does not move it."""
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(lib().rtc_scene_bounds(self._h, _ptr(lo), _ptr(hi)), "rtc_scene_bounds")
+        return lo, hi
+
+    def ray_order_async(self, rays_ptr: int, n: int, order_ptr: int, scratch_ptr: int, scratch_bytes: int, bounds=None,
+                        keys_ptr: int = 0, stream: int | None = None):
+        """rtc_ray_order_async: the stable order of n Rays (device memory at rays_ptr) by their coherence key (DESIGN
+        3.15) into order_ptr (uint32 [n]: the permutation that sorts the rays by key, equal keys in ascending index) and,
+        where wanted, the keys in input order into keys_ptr (uint32 [n]).  scratch_ptr: ray_order_scratch_bytes(n) bytes
+        of device memory, 16-byte aligned.  bounds: None (the scene's, bounds()) or (lo, hi) / six floats, on the host.
+        Asynchronous on `stream`, complete there; nothing of the scene's state is touched."""
+        b = None if bounds is None else np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(-1)
+                                                                             for v in bounds]), np.float32)
+        if b is not None and b.size != 6:
+            raise ValueError("DeviceScene.ray_order_async: bounds are (lo, hi): six floats")
+        check(lib().rtc_ray_order_async(self._h, _vp(rays_ptr), n, _ptr(b), _vp(order_ptr), _vp(keys_ptr),
+                                        _vp(scratch_ptr), scratch_bytes, _vp(stream)), "rtc_ray_order_async")
+
+    def ray_order(self, rays, bounds=None, keys: bool = False):
+        """The coherent order of `rays` (ray_order_async's): the permutation that sorts them by key, stably -- equal to
+        np.argsort(ray_keys_host(rays, lo, hi), kind="stable") -- or (order, keys) with keys=True.  numpy rays (RAY_DT [n]
+        or float32 [n, 6]) take the synchronous host entry rtc_ray_order and give numpy uint32 arrays; a torch tensor on
+        the scene's device is sorted in place of residence on torch's current stream there and gives int32 tensors on that
+        device.  Pass the result as `order=` to trace_rays, trace_paths or occluded."""
+        on_device, a, n = _query_rays("DeviceScene.ray_order", rays)
+        b = None if bounds is None else np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(-1)
+                                                                             for v in bounds]), np.float32)
+        if b is not None and b.size != 6:
+            raise ValueError("DeviceScene.ray_order: bounds are (lo, hi): six floats")
+        if on_device:
+            import torch
+
+            order = torch.zeros(n, dtype=torch.int32, device=rays.device)
+            kt = torch.zeros(n, dtype=torch.int32, device=rays.device) if keys else None
+            if n:
+                nbytes = ray_order_scratch_bytes(n)
+                scratch = torch.empty(nbytes, dtype=torch.uint8, device=rays.device)
+                with _current_stream_of(rays.device) as st:
+                    self.ray_order_async(rays.data_ptr(), n, order.data_ptr(), scratch.data_ptr(), nbytes, b,
+                                         kt.data_ptr() if keys else 0, stream=st)
+            return (order, kt) if keys else order
+        order = np.zeros(n, np.uint32)
+        ks = np.zeros(n, np.uint32) if keys else None
+        if n:
+            check(lib().rtc_ray_order(self._h, _ptr(a), n, _ptr(b), _ptr(order), _ptr(ks)), "rtc_ray_order")
+        return (order, ks) if keys else order
+
+    def _order_for(self, who: str, order, rays, n: int):
+        """A query's `order=` as what its path permutes with: None (no order); for device rays an int32 tensor there, for
+        host rays numpy indices.  True computes ray_order(rays)."""
+        if order is None or order is False:
+            return None
+        on_device = hasattr(rays, "data_ptr")
+        if order is True:
+            got = self.ray_order(rays)
+            return got if on_device else got.astype(np.intp)
+        return _device_order(who, order, n, rays.device) if on_device else _host_order(who, order, n)
 
     def render_progressive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, state: "ProgressState | None" = None):
         """A generator over the passes of one frame: `passes` is a list of sample counts summing to cfg.spp (or, with
@@ -780,6 +931,37 @@ def copy_async(dst_ptr: int, src_ptr: int, nbytes: int, blocks: int = 32, stream
     """rtc_copy_async: a copy with a small CU footprint (e.g. Color[] into pinned host memory)."""
     check(lib().rtc_copy_async(C.c_void_p(dst_ptr), C.c_void_p(src_ptr), C.c_size_t(nbytes), int(blocks),
                                C.c_void_p(stream) if stream else None), "rtc_copy_async")
+
+
+def ray_keys_host(rays, lo, hi) -> np.ndarray:
+    """rtc_ray_keys_host (no GPU): the 30-bit coherence keys of `rays` (RAY_DT [n] or float32 [n, 6]) in the box lo, hi
+    (three floats each) as uint32 [n] -- the host statement of the key the device sort uses."""
+    _, a, n = _query_rays("ray_keys_host", np.asarray(rays))
+    lo, hi = (np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)) for v in (lo, hi))
+    if lo.size != 3 or hi.size != 3:
+        raise ValueError("ray_keys_host: lo and hi are three floats each")
+    keys = np.zeros(n, np.uint32)
+    check(lib().rtc_ray_keys_host(_ptr(a) if n else None, n, _ptr(lo), _ptr(hi), _ptr(keys) if n else None),
+          "rtc_ray_keys_host")
+    return keys
+
+
+def ray_order_scratch_bytes(n: int) -> int:
+    """rtc_ray_order_scratch_bytes: the device scratch rtc_ray_order_async needs for n rays."""
+    return int(lib().rtc_ray_order_scratch_bytes(int(n)))
+
+
+def gather_async(dst_ptr: int, src_ptr: int, order_ptr: int, n: int, elem_bytes: int, stream: int | None = None) -> None:
+    """rtc_gather_async: dst[i] = src[order[i]] for n elements of elem_bytes (1, or a multiple of 4 up to 64) on the
+    current device; dst must not alias src."""
+    check(lib().rtc_gather_async(_vp(dst_ptr), _vp(src_ptr), _vp(order_ptr), n, elem_bytes, _vp(stream)),
+          "rtc_gather_async")
+
+
+def scatter_async(dst_ptr: int, src_ptr: int, order_ptr: int, n: int, elem_bytes: int, stream: int | None = None) -> None:
+    """rtc_scatter_async: dst[order[i]] = src[i], the inverse of gather_async with the same order."""
+    check(lib().rtc_scatter_async(_vp(dst_ptr), _vp(src_ptr), _vp(order_ptr), n, elem_bytes, _vp(stream)),
+          "rtc_scatter_async")
 
 
 def copy_d2h_dma(host_ptr: int, dev_ptr: int, nbytes: int) -> None:

@@ -121,6 +121,10 @@ RTC_F_HOST_ROWS = 0x1000
 RTC_F_SPLIT_SPHERES = 0x2000  # sphere launches take the split launch whatever the scene's gate says (A/B, tests)
 RTC_F_NO_DRAW_CACHE = 0x4000  # the launch neither reads nor fills the scene's draw cache (A/B, tests)
 RTC_F_WAVE_PER_RAY = 0x20000  # trace_paths only: one wave per ray, its samples on the lanes (same values bit for bit)
+# the ray sort's shape (rtc_ray_order_shape): keys per workgroup, and the
+# workgroup counts one scan workgroup takes per step of its loop -- the sizes at which the sort takes another path
+RAY_ORDER_KEYS_PER_GROUP = 4096
+RAY_ORDER_SCAN_GROUPS = 256
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007
@@ -173,6 +177,8 @@ EXPORTS = [
     "rtc_plan_sim_set_draw_cache",
     "rtc_trace_paths_async", "rtc_trace_paths", "rtc_plan_sim_trace_paths",
     "rtc_occluded_async", "rtc_occluded", "rtc_plan_sim_occluded",
+    "rtc_scene_bounds", "rtc_ray_order_shape", "rtc_ray_order_scratch_bytes", "rtc_ray_order_async", "rtc_ray_order", "rtc_ray_keys_host",
+    "rtc_gather_async", "rtc_scatter_async",
 ]
 
 _lib = None
@@ -304,6 +310,16 @@ def lib() -> C.CDLL:
         L.rtc_occluded.argtypes = [vp, vp, vp, sz, ip, ip, vp, vp]
         L.rtc_plan_sim_occluded.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
                                             C.c_ulonglong, ip, vp, ip, vp, ip]
+    if hasattr(L, "rtc_ray_order_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_bounds.argtypes = [vp, vp, vp]
+        L.rtc_ray_order_shape.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rtc_ray_order_scratch_bytes.argtypes = [sz]
+        L.rtc_ray_order_scratch_bytes.restype = sz
+        L.rtc_ray_order_async.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz, vp]
+        L.rtc_ray_order.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.rtc_ray_keys_host.argtypes = [vp, sz, vp, vp, vp]
+        L.rtc_gather_async.argtypes = [vp, vp, vp, sz, sz, vp]
+        L.rtc_scatter_async.argtypes = [vp, vp, vp, sz, sz, vp]
     _lib = L
     return L
 

@@ -276,6 +276,9 @@ struct RtcDeviceScene {
     int triCount, triPadded, sphereCount; /* triPadded: multiple of kUnroll, zero (never-hit) records */
     int clusterCount;   /* ceil(triCount / kClusterSize) */
     int chunkCount;
+    /* the box of the upload's triangle vertices and sphere extents (centre -+ r), kept on the host for the ray order's key
+     * (rtc_scene_bounds); an update does not move it: the key only affects speed.  An empty scene: zeros. */
+    float boundsLo[3], boundsHi[3];
     SceneRecords gen[2]; /* by generation; a launch binds gen[Plan::gen] */
     /* the generation a launch enqueued now would read (probes, rtc_cull_items) */
     const SceneRecords &current() const { return gen[plan.gen]; }

@@ -837,6 +837,34 @@ extern "C" float rtc_upload_hit_share_all(const Triangle *tris, int triCount, co
     return (float)bounce_hit_share(tris, triCount, spheres, sphereCount);
 }
 
+/* The box of the triangles' vertices and the spheres' extents centre -+ r, in f32 (a NaN coordinate takes no part); zeros
+ * for a scene without primitives.  The default bounds of the ray order's key. */
+static void scene_bounds(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, float lo[3], float hi[3])
+{
+    for (int a = 0; a < 3; ++a)
+        lo[a] = INFINITY, hi[a] = -INFINITY;
+    const auto take = [&](const float l[3], const float h[3]) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = l[a] < lo[a] ? l[a] : lo[a];
+            hi[a] = h[a] > hi[a] ? h[a] : hi[a];
+        }
+    };
+    for (int i = 0; i < triCount; ++i)
+        for (const vec3 *v : {&tris[i].posA, &tris[i].posB, &tris[i].posC}) {
+            const float p[3] = {v->x, v->y, v->z};
+            take(p, p);
+        }
+    for (int i = 0; i < sphereCount; ++i) {
+        const Sphere &sp = spheres[i];
+        const float l[3] = {sp.pos.x - sp.r, sp.pos.y - sp.r, sp.pos.z - sp.r};
+        const float h[3] = {sp.pos.x + sp.r, sp.pos.y + sp.r, sp.pos.z + sp.r};
+        take(l, h);
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] <= hi[a]))
+            lo[a] = hi[a] = 0.f;
+}
+
 extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount,
                                            int device, float hitShare, float hitShareAll, RtcDeviceScene **out)
 {
@@ -867,6 +895,7 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
     s->triPadded = (triCount + 7) / 8 * 8; /* whole pairs of batches; arrays hold 8 more records for prefetch */
     s->sphereCount = sphereCount;
     s->maskWords = (s->triPadded + 63) / 64;
+    scene_bounds(tris, triCount, spheres, sphereCount, s->boundsLo, s->boundsHi);
     s->clusterCount = (triCount + kClusterSize - 1) / kClusterSize;
     s->chunkCount = (s->clusterCount + kChunkClusters - 1) / kChunkClusters;
     { /* the draw cache's capacity in blocks: RTC_DRAW_CACHE_BLOCKS (0: off), else the default (rtc_scene_set_draw_cache) */

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Compare the device code of rtc_render.hip between two source trees, kernel by kernel, and list the resource use of
-the kernels only the second has.
+"""Compare the device code of the library's HIP translation units between two source trees, kernel by kernel, and list the
+resource use of the kernels only the second has.
 
     tools/kernel_diff.py OLD_TREE NEW_TREE
 
-Each tree's raytracingc_amd/csrc/rtc_render.hip is compiled for gfx950 with the Makefile's flags to assembly
+Each raytracingc_amd/csrc/*.hip of NEW_TREE (rtc_render.hip first; a unit OLD_TREE lacks has only new kernels) is
+compiled in both trees for gfx950 with the Makefile's flags to assembly
 (--cuda-device-only -S, with -Rpass-analysis=kernel-resource-usage).  A kernel's text is the lines between its label and
 its .Lfunc_end; local labels (.LBB<function>_<block>) are renumbered by the function's own order, so a kernel that moved
 in the file still compares equal.  A template parameter added at the END of a kernel template's list with the default
@@ -15,6 +16,8 @@ instantiation list at the end of rtc_render.hip, where new ones are appended).  
 missing from NEW or differs, or when that order changed.  Needs only hipcc (no GPU)."""
 from __future__ import annotations
 
+import glob
+import os
 import re
 import subprocess
 import sys
@@ -23,9 +26,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectoriz
          "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", "-"]
 
 
-def compile_tree(tree):
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, f"{tree}/raytracingc_amd/csrc/rtc_render.hip"],
-                       capture_output=True, text=True)
+def compile_tree(tree, unit="rtc_render.hip"):
+    src = f"{tree}/raytracingc_amd/csrc/{unit}"
+    if not os.path.exists(src):
+        return "", ""
+    r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, src], capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-4000:])
     return r.stdout, r.stderr
@@ -68,6 +73,8 @@ def resources(remarks):
 
 
 def demangle(names):
+    if not names:  # (c++filt without arguments would read its standard input)
+        return {}
     try:
         r = subprocess.run(["c++filt", *names], capture_output=True, text=True)
     except OSError:
@@ -76,8 +83,19 @@ def demangle(names):
 
 
 def main():
-    old_asm, _ = compile_tree(sys.argv[1])
-    new_asm, new_rem = compile_tree(sys.argv[2])
+    units = sorted((os.path.basename(f) for f in glob.glob(f"{sys.argv[2]}/raytracingc_amd/csrc/*.hip")),
+                   key=lambda u: (u != "rtc_render.hip", u))
+    bad = 0
+    for unit in units:
+        print(f"==== {unit}")
+        bad += diff_unit(unit)
+        print()
+    sys.exit(1 if bad else 0)
+
+
+def diff_unit(unit):
+    old_asm, _ = compile_tree(sys.argv[1], unit)
+    new_asm, new_rem = compile_tree(sys.argv[2], unit)
     old, new = kernels(old_asm), kernels(new_asm)
     by_old_name = {}
     for n in new:
@@ -108,7 +126,7 @@ def main():
         print(f"  {dm[n]}: VGPRs {r.get('VGPRs')}, SGPRs {r.get('TotalSGPRs', r.get('SGPRs'))}, scratch {r.get('ScratchSize [bytes/lane]')} B/lane, "
               f"spills {r.get('SGPRs Spill')} SGPR / {r.get('VGPRs Spill')} VGPR, waves/SIMD "
               f"{r.get('Occupancy [waves/SIMD]')}, LDS {r.get('LDS Size [bytes/block]')} B")
-    sys.exit(1 if bad else 0)
+    return bad
 
 
 if __name__ == "__main__":
