@@ -199,13 +199,14 @@ int rtc_scene_release(RtcDeviceScene *s);
  * kernel on `stream` (a refit), no host work, no synchronisation (no reference counterpart: main.c:229-243 builds its
  * arrays once).  dTris / dSpheres are DEVICE pointers on the scene's device in the reference's own layouts (68 / 36 bytes
  * per primitive); a null pointer leaves that kind unchanged, and its count is then 0; a count given equals the upload's --
- * the number of primitives and the grouping of the triangles into clusters are fixed at upload.  The kernel rewrites what
+ * the number of primitives is fixed at upload, and an update keeps the grouping of the triangles into clusters (the
+ * upload's, or the last rtc_scene_regroup_async's).  The kernel rewrites what
  * the upload derived from the primitives: the packed triangles (A, AB = B - A, AC = C - A in f32, the normal), the
  * materials, the spheres, the triangles in cluster order with their aligned-normal flags, and every cluster's and chunk's
  * bounding ball and cull margins, byte for byte what an upload of the new primitives with the old grouping would hold.
  * The culling is exact for any ball that contains its vertices and carries its margins, so the frames are the new
  * geometry's bit for bit, however far it moved; geometry that drifts far from the upload's clusters is only culled worse
- * (larger, overlapping balls) and is a reason to upload again -- an update never regroups.
+ * (larger, overlapping balls) and is a reason to regroup (rtc_scene_regroup_async below) -- an update never regroups.
  * Ordering: asynchronous on `stream`, under rtc_render_rows_async's contract (a scene serves one stream at a time; a
  * caller that changes streams orders them).  Every launch enqueued on the scene after the call renders the new geometry,
  * every launch enqueued before it the old one, overlapped launches (RTC_F_OVERLAP) whose kernels or sky pass are still in
@@ -222,6 +223,38 @@ int rtc_scene_release(RtcDeviceScene *s);
 int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
                            int sphereCount, void *stream);
 int rtc_scene_update(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount);
+/* rtc_scene_update_async with the grouping of the triangles into clusters decided anew from dTris, on the device: a few
+ * short kernels on `stream` before the refit -- the centroids, one kernel per level of the upload's median split, the
+ * membership --, no host work, no host read of device memory, no allocation, no synchronisation (no
+ * reference counterpart).  Once `stream` has passed the call the six record arrays of the current generation are, byte for
+ * byte, those of a fresh rtc_scene_upload of dTris (rtc_scene_records_host(dTris, n, NULL, spheres, ..)), and a later
+ * rtc_scene_update_async(tris2) refits THAT grouping (rtc_scene_records_host(dTris, n, tris2, ..)).  The frames are the
+ * new geometry's bit for bit either way; the regroup restores the culling a drifted grouping lost.
+ * dTris is required, with the upload's count; dSpheres is as in an update (nullable: the spheres are kept).  dScratch:
+ * rtc_scene_regroup_scratch_bytes(s) bytes of device memory on the scene's device, 16-byte aligned, the caller's; it holds
+ * the centroids and two index buffers and may be reused, like the source arrays, once `stream` has passed the call.
+ * Ordering, generations and waits are exactly an update's.  The upload's hints (rtc_scene_chain_wgs, the sphere split's
+ * gate, rtc_scene_bounds, the HITS choice) keep their values; the draw cache, the caller's hooks and the chain report are
+ * untouched.
+ * The work is quadratic in the triangle count (a stable sort as a rank count: deterministic, no atomics), so it is offered
+ * up to rtc_scene_regroup_max_tris() triangles -- the largest power of two at which it was measured faster than the
+ * upload it replaces; above it, upload again.
+ * RTC_EINVAL, with nothing enqueued: whatever rtc_scene_update_async refuses; a null dTris; a null dScratch, one that is
+ * not 16-byte aligned or holds fewer than rtc_scene_regroup_scratch_bytes(s) bytes; more triangles than
+ * rtc_scene_regroup_max_tris().
+ * rtc_scene_regroup takes HOST arrays, staged like rtc_scene_update's, with a scratch of its own (synchronous; the same
+ * refusals; a null scene is refused before any device call).  rtc_scene_regroup_scratch_bytes: a multiple of 16; 0 for a
+ * null scene. */
+size_t rtc_scene_regroup_scratch_bytes(const RtcDeviceScene *s);
+int rtc_scene_regroup_max_tris(void);
+int rtc_scene_regroup_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
+                            int sphereCount, void *dScratch, size_t scratchBytes, void *stream);
+int rtc_scene_regroup(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount);
+/* The membership a regroup leaves, on the host and without a GPU: idx[k] = the index in tris of clustered record k
+ * (triCount ints).  It runs the device's formulation -- level by level, every element to its rank (rtc_regroup.h) -- in
+ * plain C++, and equals the membership of rtc_scene_upload (rtc_scene_records_host's clTris, dword 12) for every input,
+ * NaN, infinities and zeros of either sign included.  Quadratic: meant for tests. */
+int rtc_regroup_membership_host(const Triangle *tris, int triCount, int *idx);
 /* Number of rows d selects (ceil((height - rowStart) / rowStride) for single rows; with bands, the full bands' rows
  * plus the last band's rows inside the frame), 0 if none. */
 int rtc_rows_selected(const RtcRenderDesc *d);
@@ -589,6 +622,16 @@ int rtc_plan_sim_set_first_hit(RtcPlanSim *sim, unsigned long long prim, unsigne
 int rtc_plan_sim_update(RtcPlanSim *sim, unsigned long long stream, int *ops, int maxOps, unsigned long long *footprint,
                         int maxFootprint);
 int rtc_plan_sim_set_update_fault(RtcPlanSim *sim, int mode);
+/* Plans one rtc_scene_regroup_async on the caller's stream `stream`, in rtc_plan_sim_update's encodings: an update's waits,
+ * then on stream 0, without events, the centroid kernel (kernel 14: writes the caller's scratch, resource 19, id =
+ * `scratch`), one level kernel per level of the scene's triangle count (kernel 15: reads and writes the scratch), the index
+ * kernel (kernel 16: reads the scratch, writes the membership, resource 18, id 0) and the refit (kernel 9: an update's two
+ * records, then a read of the membership); then one u64 record (~0, 0, the generation written, the levels, 0, 0).
+ * rtc_plan_sim_update's output is unchanged: its refit names no membership.  RTC_EINVAL where the entry point would, as far
+ * as the planner sees it: a `scratch` of 0 or not a multiple of 16, a scene of no triangles or of more than
+ * rtc_scene_regroup_max_tris(). */
+int rtc_plan_sim_regroup(RtcPlanSim *sim, unsigned long long stream, unsigned long long scratch, int *ops, int maxOps,
+                         unsigned long long *footprint, int maxFootprint);
 /* Plans one rtc_trace_rays_async on the caller's stream `stream`, in rtc_plan_sim_update's encodings: one kernel op (kernel
  * 11, stream 0, no event) with its footprint records -- it reads the current generation (resource 9, id = the generation)
  * and the ray buffer (resource 11, id = `rays`) and writes each hit buffer asked for (resource 10, id = hit[k]; 0: not

@@ -69,6 +69,7 @@ __all__ = [
     "getEnvironmentLight", "random_sequences", "device_count", "lib", "TRIANGLE_DT", "SPHERE_DT", "RAY_DT",
     "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress", "scene_records_host", "RECORD_ARRAYS",
     "ray_keys_host", "ray_order_scratch_bytes", "gather_async", "scatter_async",
+    "regroup_membership_host", "regroup_max_tris",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -296,6 +297,21 @@ def scene_records_host(tris, new_tris=None, spheres=None) -> dict:
         raise ValueError("scene_records_host: new_tris must hold as many triangles as tris")
     return _records(lambda bufs, sizes: lib().rtc_scene_records_host(_ptr(t), nt, _ptr(n), _ptr(s), ns, *bufs, sizes),
                     "rtc_scene_records_host")
+
+
+def regroup_membership_host(tris) -> np.ndarray:
+    """The cluster membership a regroup leaves (rtc_regroup_membership_host), no GPU: int32 [n], the index in `tris` of
+    every clustered record.  The device's level-by-level rank count run in plain C++; equal to the upload's membership,
+    scene_records_host(tris)["clTris"][:n, 12]."""
+    t, nt = _arr(tris, TRIANGLE_DT)
+    idx = np.zeros(nt, np.int32)
+    check(lib().rtc_regroup_membership_host(_ptr(t), nt, _ptr(idx)), "rtc_regroup_membership_host")
+    return idx
+
+
+def regroup_max_tris() -> int:
+    """rtc_scene_regroup_max_tris: the most triangles a regroup takes (above it: upload again)."""
+    return int(lib().rtc_scene_regroup_max_tris())
 
 
 def render(tris, spheres, scene: Scene, cam: RtcCamera, cfg: RenderConfig, device: int = -1,
@@ -831,22 +847,46 @@ class DeviceScene:
         check(lib().rtc_scene_kernel_times(self._h, out), "rtc_scene_kernel_times")
         return None if out[0] < 0 else (float(out[0]), float(out[1]))
 
-    def update(self, tris=None, spheres=None, stream: int | None = None):
+    def regroup_scratch_bytes(self) -> int:
+        """rtc_scene_regroup_scratch_bytes: the device scratch regroup_async needs for this scene."""
+        return int(lib().rtc_scene_regroup_scratch_bytes(self._h))
+
+    def regroup_async(self, tris_ptr: int, spheres_ptr: int | None, scratch_ptr: int, scratch_bytes: int,
+                      stream: int | None = None):
+        """rtc_scene_regroup_async: an update from the device arrays at tris_ptr (required, the upload's count) and
+        spheres_ptr (0 / None: the spheres are kept) that first decides the clusters anew from those triangles, on the
+        device; afterwards the scene holds what a fresh upload of them would, byte for byte.  scratch_ptr:
+        regroup_scratch_bytes() bytes of device memory, 16-byte aligned.  Asynchronous on `stream`, ordered as an update."""
+        if not self._h:
+            raise RuntimeError("DeviceScene.regroup_async: the scene has been released")
+        check(lib().rtc_scene_regroup_async(self._h, _vp(tris_ptr), self.tri_count, _vp(spheres_ptr),
+                                            self.sphere_count if spheres_ptr else 0, _vp(scratch_ptr), scratch_bytes,
+                                            _vp(stream)), "rtc_scene_regroup_async")
+
+    def update(self, tris=None, spheres=None, stream: int | None = None, regroup: bool = False):
         """Replace the resident triangles and / or spheres in place (rtc_scene_update / rtc_scene_update_async): the
         counts are the upload's, None leaves that kind unchanged.  Numpy arrays of TRIANGLE_DT / SPHERE_DT take the
         synchronous host path.  Torch tensors on the scene's device (any dtype, count x 68 / 36 bytes, contiguous) take
         the asynchronous path on `stream` (a hipStream_t; None: torch's current stream): every launch enqueued on the
         scene afterwards renders the new geometry, every earlier one the old, and the tensors may be reused once the
-        stream has passed the call.  The upload's scheduling hints stay; the frames are the new geometry's bit for bit."""
+        stream has passed the call.  The upload's scheduling hints stay; the frames are the new geometry's bit for bit.
+        regroup=True also decides the clusters anew from `tris` (required then) on the device, as a fresh upload of them
+        would (rtc_scene_regroup / rtc_scene_regroup_async; at most regroup_max_tris() triangles): the frames are the
+        same, the culling is that of a fresh upload.  The device path allocates its scratch on torch's current stream."""
         if not self._h:
             raise RuntimeError("DeviceScene.update: the scene has been released")
         if tris is None and spheres is None:
             raise ValueError("DeviceScene.update: neither triangles nor spheres")
+        if regroup and tris is None:
+            raise ValueError("DeviceScene.update: regroup=True needs the triangles (the clusters are decided from them)")
         on_device = [hasattr(a, "data_ptr") for a in (tris, spheres) if a is not None]
         if not any(on_device):
             t, nt = _arr(tris, TRIANGLE_DT)
             s, ns = _arr(spheres, SPHERE_DT)
-            check(lib().rtc_scene_update(self._h, _ptr(t), nt, _ptr(s), ns), "rtc_scene_update")
+            if regroup:
+                check(lib().rtc_scene_regroup(self._h, _ptr(t), nt, _ptr(s), ns), "rtc_scene_regroup")
+            else:
+                check(lib().rtc_scene_update(self._h, _ptr(t), nt, _ptr(s), ns), "rtc_scene_update")
             return
         if not all(on_device):
             raise TypeError("DeviceScene.update: triangles and spheres both on the host or both on the device")
@@ -864,6 +904,15 @@ class DeviceScene:
         ps, ns = dev(spheres, SPHERE_DT.itemsize, "spheres")
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
+        if regroup:
+            # (torch's allocator hands the scratch back to its current stream: a caller on another `stream` orders the two)
+            nbytes = self.regroup_scratch_bytes()
+            scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=tris.device)
+            check(lib().rtc_scene_regroup_async(self._h, pt, nt, ps, ns, C.c_void_p(scratch.data_ptr()), nbytes,
+                                                C.c_void_p(stream) if stream else None), "rtc_scene_regroup_async")
+            if stream != torch.cuda.current_stream(tris.device).cuda_stream:
+                scratch.record_stream(torch.cuda.ExternalStream(stream, device=tris.device))
+            return
         check(lib().rtc_scene_update_async(self._h, pt, nt, ps, ns, C.c_void_p(stream) if stream else None),
               "rtc_scene_update_async")
 

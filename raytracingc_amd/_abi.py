@@ -179,6 +179,8 @@ EXPORTS = [
     "rtc_occluded_async", "rtc_occluded", "rtc_plan_sim_occluded",
     "rtc_scene_bounds", "rtc_ray_order_shape", "rtc_ray_order_scratch_bytes", "rtc_ray_order_async", "rtc_ray_order", "rtc_ray_keys_host",
     "rtc_gather_async", "rtc_scatter_async",
+    "rtc_scene_regroup_scratch_bytes", "rtc_scene_regroup_max_tris", "rtc_scene_regroup_async", "rtc_scene_regroup",
+    "rtc_regroup_membership_host", "rtc_plan_sim_regroup",
 ]
 
 _lib = None
@@ -320,6 +322,14 @@ def lib() -> C.CDLL:
         L.rtc_ray_keys_host.argtypes = [vp, sz, vp, vp, vp]
         L.rtc_gather_async.argtypes = [vp, vp, vp, sz, sz, vp]
         L.rtc_scatter_async.argtypes = [vp, vp, vp, sz, sz, vp]
+    if hasattr(L, "rtc_scene_regroup_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_regroup_scratch_bytes.argtypes = [vp]
+        L.rtc_scene_regroup_scratch_bytes.restype = sz
+        L.rtc_scene_regroup_max_tris.argtypes = []
+        L.rtc_scene_regroup_async.argtypes = [vp, vp, ip, vp, ip, vp, sz, vp]
+        L.rtc_scene_regroup.argtypes = [vp, vp, ip, vp, ip]
+        L.rtc_regroup_membership_host.argtypes = [vp, ip, vp]
+        L.rtc_plan_sim_regroup.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, vp, ip, vp, ip]
     _lib = L
     return L
 

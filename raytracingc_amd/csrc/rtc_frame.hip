@@ -187,7 +187,6 @@ extern "C" int rtc_render(const Triangle *tris, int triCount, const Sphere *sphe
     if (outAccum)
         HIP_TRY(dAccum.alloc(px * 3 * sizeof(float) + 16, device));
     HIP_TRY(dSeg.alloc(kSegBytes, device));
-    HIP_TRY(hipMemset(dSeg.p, 0, kSegBytes));
     HIP_TRY(hColors.alloc(px * 3));
     hipStream_t st = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -195,6 +194,10 @@ extern "C" int rtc_render(const Triangle *tris, int triCount, const Sphere *sphe
         hipStream_t st;
         ~StreamGuard() { (void)hipStreamDestroy(st); }
     } streamGuard{st};
+    /* on the launch's own stream: a hipMemset of device memory returns before it has run, on the null stream, which a
+     * non-blocking stream does not follow -- the zeroes could land after the kernels' counts (seen once: a frame with every
+     * pixel right and 0 segments) */
+    HIP_TRY(hipMemsetAsync(dSeg.p, 0, kSegBytes, st));
     Events evs;
     hipEvent_t e0, e1, e2;
     HIP_TRY(evs.make(&e0));

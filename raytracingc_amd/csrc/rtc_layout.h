@@ -282,8 +282,11 @@ struct RtcDeviceScene {
     SceneRecords gen[2]; /* by generation; a launch binds gen[Plan::gen] */
     /* the generation a launch enqueued now would read (probes, rtc_cull_items) */
     const SceneRecords &current() const { return gen[plan.gen]; }
-    /* clustered record -> reference index (-1: padding), clusterCount * kClusterSize ints: the cluster membership, fixed
-     * at upload (rtc_refit reads it) */
+    /* clustered record -> reference index (-1: padding), clusterCount * kClusterSize ints: the cluster membership, decided
+     * at upload and again by every rtc_scene_regroup_async.  One copy serves both generations: only refits
+     * read it (rtc_refit) and only a regroup's index kernel writes it, all of them on the caller's stream, and a scene serves
+     * one stream at a time (rtc.h), so stream order alone puts every read after the write it means and before the next.
+     * Launches in flight read the records of their generation, never this. */
     int *clIndex;
     size_t recBytes[6]; /* bytes of tris, mats, spheres, clTris, clusters, chunks (each generation) */
     /* per-launch primary records, one copy per scratch slot (primStride records each), written by rtc_prep_primary:

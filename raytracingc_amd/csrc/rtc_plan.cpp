@@ -3,6 +3,7 @@
  * Pure host C++; the HIP executor is rtc_render_rows_async (rtc_render.hip), the CPU test tests/test_plan.py.
  */
 #include "rtc_plan.h"
+#include "rtc_regroup.h"
 
 #include <algorithm>
 #include <cstring>
@@ -512,6 +513,46 @@ int update_footprint(const UpdatePlan &u, Footprint *out, int max)
     return 2;
 }
 
+void plan_regroup(const State &s, int levels, RegroupPlan &g)
+{
+    memset(&g, 0, sizeof g);
+    UpdatePlan u;
+    plan_update(s, 0, u);
+    g.reads = u.reads, g.writes = u.writes;
+    g.levels = levels < 0 ? 0 : levels > kRegroupMaxLevels ? kRegroupMaxLevels : levels;
+    for (int i = 0; i + 1 < u.nOps; ++i) /* the update's waits */
+        g.ops[g.nOps++] = u.ops[i];
+    g.ops[g.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKRegroupCentroids};
+    for (int l = 0; l < g.levels; ++l)
+        g.ops[g.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKRegroupLevel};
+    g.ops[g.nOps++] = Op{kOpKernel, kStCaller, kEvNone, kKRegroupIndex};
+    g.ops[g.nOps++] = u.ops[u.nOps - 1]; /* the refit */
+    g.after = u.after;
+}
+
+int regroup_footprint(const RegroupPlan &g, int kernel, uint64_t scratch, Footprint *out, int max)
+{
+    const Footprint sr{kResRegroupScratch, kRead, scratch, 0, 1}, sw{kResRegroupScratch, kWrite, scratch, 0, 1};
+    const Footprint mr{kResMembership, kRead, 0, 0, 1}, mw{kResMembership, kWrite, 0, 0, 1};
+    Footprint f[3];
+    int k = 0;
+    if (kernel == kKRegroupCentroids) {
+        f[k++] = sw;
+    } else if (kernel == kKRegroupLevel) {
+        f[k++] = sr, f[k++] = sw;
+    } else if (kernel == kKRegroupIndex) {
+        f[k++] = sr, f[k++] = mw;
+    } else if (kernel == kKRefit) {
+        UpdatePlan u{};
+        u.reads = g.reads, u.writes = g.writes;
+        k = update_footprint(u, f, 2);
+        f[k++] = mr;
+    }
+    for (int j = 0; j < k && j < max; ++j)
+        out[j] = f[j];
+    return k;
+}
+
 void plan_query(const State &s, int kernel, TracePlan &t)
 {
     memset(&t, 0, sizeof t);
@@ -747,6 +788,24 @@ extern "C" int rtc_plan_sim_update(RtcPlanSim *s, unsigned long long stream, int
     return serialise(u.ops, u.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)u.writes, 0, 0, 0},
                      [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) {
                          return rtcplan::update_footprint(u, f, max);
+                     });
+}
+
+extern "C" int rtc_plan_sim_regroup(RtcPlanSim *s, unsigned long long stream, unsigned long long scratch, int *ops,
+                                    int maxOps, unsigned long long *fp, int maxFp)
+{
+    /* refused as rtc_scene_regroup_async refuses it, as far as the planner sees it: no scratch, a misaligned one, a scene
+     * without triangles or of more than the regroup takes */
+    if (!s || !ops || !scratch || scratch % 16 || s->shape.triPadded <= 0 || s->shape.triPadded > kRegroupMaxTris)
+        return RTC_EINVAL;
+    (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
+    rtcplan::RegroupPlan g;
+    rtcplan::plan_regroup(s->st, regroup_levels(s->shape.triPadded), g);
+    s->st = g.after;
+    /* the trailer: (~0, nothing regrown, the generation written, the levels, -, -) */
+    return serialise(g.ops, g.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)g.writes, (unsigned long long)g.levels, 0, 0},
+                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
+                         return rtcplan::regroup_footprint(g, o.kernel, scratch, f, max);
                      });
 }
 

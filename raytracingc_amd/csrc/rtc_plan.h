@@ -65,8 +65,11 @@ enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kK
                     kKFirstHit /* rtc_render_first_hit_async's kernel (set_first_hit); of no other launch */,
                     kKTraceRays /* rtc_trace_rays_async's kernel (plan_query); never part of a launch */,
                     kKTracePaths /* rtc_trace_paths_async's kernel (plan_query); never part of a launch */,
-                    kKOccluded /* rtc_occluded_async's kernel (plan_query); never part of a launch */ };
-static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12 && kKOccluded == 13,
+                    kKOccluded /* rtc_occluded_async's kernel (plan_query); never part of a launch */,
+                    /* rtc_scene_regroup_async's kernels before its refit (plan_regroup); never part of a launch */
+                    kKRegroupCentroids, kKRegroupLevel, kKRegroupIndex };
+static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12 && kKOccluded == 13 &&
+                  kKRegroupCentroids == 14 && kKRegroupLevel == 15 && kKRegroupIndex == 16,
               "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
@@ -259,7 +262,9 @@ enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3,
                  kResHit = 10 /* id: the caller's buffer */, kResRays = 11 /* id: the caller's ray buffer */,
                  kResDrawTable = 12, kResItemDraw = 13 /* id: the slot */,
                  kResSeeds = 14 /* id: the caller's seed buffer */, kResRadiance = 15 /* id: the caller's buffer */,
-                 kResTMax = 16 /* id: the caller's limit buffer */, kResOccluded = 17 /* id: the caller's byte buffer */ };
+                 kResTMax = 16 /* id: the caller's limit buffer */, kResOccluded = 17 /* id: the caller's byte buffer */,
+                 kResMembership = 18 /* the scene's cluster membership (clIndex) */,
+                 kResRegroupScratch = 19 /* id: the caller's regroup scratch */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -284,6 +289,26 @@ struct UpdatePlan {
 void plan_update(const State &s, int fault, UpdatePlan &u);
 /* the refit kernel's footprint: the generation it writes and the one it may copy from */
 int update_footprint(const UpdatePlan &u, Footprint *out, int max);
+
+/* One rtc_scene_regroup_async: an update whose refit is preceded, on the caller's stream, by the kernels
+ * that decide the membership anew -- the centroids, one kernel per level of the median split (`levels` of them:
+ * regroup_levels of the scene's triangle count) and the one that writes the membership.  The waits, the generation
+ * written and the state afterwards are plan_update's own (the plan is made from one); the membership is read by refits
+ * alone, and refits are ordered on the caller's stream -- a scene serves one stream at a time --, so it needs no event and
+ * no second copy: launches in flight read the records of their generation, never the membership. */
+constexpr int kRegroupMaxLevels = 32;
+struct RegroupPlan {
+    int reads, writes; /* generations, as UpdatePlan's */
+    int levels;
+    int nOps;
+    Op ops[kSlots + 3 + kRegroupMaxLevels];
+    State after;
+};
+void plan_regroup(const State &s, int levels, RegroupPlan &g);
+/* One regroup kernel's footprint.  The centroids: the scratch written (id: the caller's buffer).  A level: the scratch
+ * read and written.  The index kernel: the scratch read, the membership written.  The refit: update_footprint's two rows,
+ * then the membership read. */
+int regroup_footprint(const RegroupPlan &g, int kernel, uint64_t scratch, Footprint *out, int max);
 
 /* One query for caller-supplied rays -- rtc_trace_rays_async (kKTraceRays), rtc_trace_paths_async
  * (kKTracePaths, §3.12) or rtc_occluded_async (kKOccluded, §3.13): one kernel on the caller's stream that reads the current

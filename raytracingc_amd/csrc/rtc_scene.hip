@@ -3,7 +3,8 @@
  * Triangle[] (objloader.c / main.c:229-243) packed into the HBM records of rtc_layout.h, grouped into clusters and chunks
  * for the bounce rays' culling, the scheduling hint bounce_hit_share, the scene's streams and ordering events, and the
  * per-scene hooks (frame / geometry events, kernel timing); and the same records rewritten in place for new primitives
- * by a kernel (rtc_scene_update_async, rtc_refit).
+ * by a kernel (rtc_scene_update_async, rtc_refit), after the clusters were decided anew on the device where
+ * asked (rtc_scene_regroup_async, the rtc_regroup_* kernels).
  */
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,8 @@
 #include "rtc_layout.h"
 #include "rtc_internal.h"
 #include "rtc_hip_util.h"
+#include "rtc_regroup.h"
+#include "rtc_staged.h"
 
 /* The share of diffuse bounce rays that hit the scene again, estimated at upload (host, a fixed-seed probe): rays from
  * area-weighted random points of the triangles, in directions normal + a random unit vector (the reference's diffuse
@@ -318,13 +321,76 @@ static bool aligned_normal(const DevTri &r)
 }
 
 /* The cluster membership: idx[k] = the reference index of clustered record k (idx holds triCount entries; the last
- * cluster's missing records are padding).  Decided once, at upload; an update keeps it (rtc_scene_update_async). */
+ * cluster's missing records are padding).  Decided at upload; an update keeps it (rtc_scene_update_async), a regroup
+ * decides it again on the device by regroup_membership's formulation (rtc_scene_regroup_async). */
 static void rtc_cluster_membership(const std::vector<DevTri> &dt, int triCount, std::vector<int> &idx)
 {
     idx.resize(triCount > 0 ? triCount : 0);
     for (int i = 0; i < triCount; ++i)
         idx[i] = i;
     split_clusters(dt, idx, 0, (size_t)triCount);
+}
+
+/* The same membership by the level-by-level rank count the device runs (rtc_regroup.h), in plain C++ and in
+ * the kernels' own structure: per level, every sorting segment by its path -- the axis from its extents, each element to
+ * its rank --, then every position no segment of the level sorts copied across.  rtc_cluster_membership stays the
+ * definition; tests/test_regroup_host.py holds the two equal. */
+static void regroup_membership(const std::vector<DevTri> &dt, int n, std::vector<int> &idx)
+{
+    std::vector<double> cent[3];
+    for (int a = 0; a < 3; ++a)
+        cent[a].resize((size_t)(n > 0 ? n : 0));
+    std::vector<int> buf[2];
+    buf[0].resize(cent[0].size()), buf[1].resize(cent[0].size());
+    for (int i = 0; i < n; ++i) { /* rtc_regroup_centroids */
+        const DevTri &t = dt[i];
+        cent[0][i] = regroup_centroid(t.ax, t.abx, t.acx);
+        cent[1][i] = regroup_centroid(t.ay, t.aby, t.acy);
+        cent[2][i] = regroup_centroid(t.az, t.abz, t.acz);
+        buf[0][i] = i;
+    }
+    const int levels = regroup_levels(n);
+    for (int level = 0; level < levels; ++level) { /* rtc_regroup_level */
+        const std::vector<int> &in = buf[level & 1];
+        std::vector<int> &out = buf[(level & 1) ^ 1];
+        for (unsigned path = 0; path < 1u << level; ++path) {
+            int lo, hi;
+            if (!regroup_segment_of_path(n, level, path, lo, hi))
+                continue;
+            RegroupExtent e[3] = {regroup_extent_init(), regroup_extent_init(), regroup_extent_init()};
+            for (int q = lo; q < hi; ++q)
+                for (int a = 0; a < 3; ++a)
+                    regroup_extent_take(e[a], cent[a][in[q]]);
+            const std::vector<double> &c = cent[regroup_axis(e)];
+            for (int p = lo; p < hi; ++p) {
+                const double kp = regroup_key(c[in[p]]);
+                int rank = 0;
+                for (int q = lo; q < hi; ++q)
+                    rank += regroup_rank(regroup_key(c[in[q]]), q, kp, p);
+                out[lo + rank] = in[p];
+            }
+        }
+        for (int p = 0; p < n; ++p) {
+            int lo, hi;
+            if (!regroup_segment_of_position(n, level, p, lo, hi))
+                out[p] = in[p];
+        }
+    }
+    idx = buf[levels & 1];
+}
+
+extern "C" int rtc_regroup_membership_host(const Triangle *tris, int triCount, int *idx)
+{
+    if (triCount < 0 || (triCount > 0 && (!tris || !idx)))
+        return rtc_fail(RTC_EINVAL, "rtc_regroup_membership_host: bad argument");
+    std::vector<DevTri> dt;
+    std::vector<DevMat> dm;
+    std::vector<DevSphere> ds;
+    pack_scene(tris, triCount, nullptr, 0, dt, dm, ds);
+    std::vector<int> m;
+    regroup_membership(dt, triCount, m);
+    std::copy(m.begin(), m.end(), idx);
+    return 0;
 }
 
 /* The one host statement of the clustered records for a membership `idx` (rtc_cluster_membership): upload builds them
@@ -625,6 +691,126 @@ __global__ __launch_bounds__(kRefitBlock) void rtc_refit(RefitArgs a)
             Rc = Rc < sR[k] ? sR[k] : Rc;
         a.to.chunks[h] = ball_finish(cb, cc, Rc);
     }
+}
+
+/* ---- the regroup on the device (rtc_scene_regroup_async) ------------------------------------------------
+ * The membership of a fresh upload of the caller's triangles, decided on the device before the refit: rtc_regroup.h's
+ * levels, operation for operation (-ffp-contract=off; IEEE divide).  The caller's scratch holds the centroids, one array
+ * of n doubles per axis, and two index buffers the levels alternate between.  Every position of a level's output is
+ * written exactly once: a sorting segment's ranks are a permutation of its positions, and the others are copied. */
+struct RegroupScratch {
+    double *cent; /* [3][n] */
+    int *idx[2];  /* position -> reference index, before and after a level */
+};
+static size_t regroup_round16(size_t b)
+{
+    return (b + 15) / 16 * 16;
+}
+static size_t regroup_scratch_bytes(int n)
+{
+    return regroup_round16(3 * sizeof(double) * (size_t)n) + 2 * regroup_round16(sizeof(int) * (size_t)n);
+}
+static RegroupScratch regroup_scratch(void *base, int n)
+{
+    unsigned char *p = static_cast<unsigned char *>(base);
+    RegroupScratch r;
+    r.cent = reinterpret_cast<double *>(p);
+    p += regroup_round16(3 * sizeof(double) * (size_t)n);
+    r.idx[0] = reinterpret_cast<int *>(p);
+    r.idx[1] = reinterpret_cast<int *>(p + regroup_round16(sizeof(int) * (size_t)n));
+    return r;
+}
+
+constexpr int kRegroupBlock = 256;
+__global__ __launch_bounds__(kRegroupBlock) void rtc_regroup_centroids(const Triangle *tris, double *cent, int *idx, int n)
+{
+    const int i = (int)(blockIdx.x * kRegroupBlock + threadIdx.x);
+    if (i >= n)
+        return;
+    const float *p = reinterpret_cast<const float *>(tris) + 17 * (size_t)i; /* posA, posB, posC, normal, mat */
+    for (int a = 0; a < 3; ++a) {
+        const float ab = p[3 + a] - p[a], ac = p[6 + a] - p[a]; /* pack_scene's f32 AB, AC */
+        cent[(size_t)a * n + i] = regroup_centroid(p[a], ab, ac);
+    }
+    idx[i] = i;
+}
+
+/* One level.  Workgroup (x, y): the positions [lo + 64 x, lo + 64 x + 64) of the segment reached by path y; its four waves
+ * each count a quarter of every tile of kRegroupBlock keys streamed through LDS (the reads of sKey are broadcasts), and
+ * the quarters are summed through LDS: ranks are sums of integers, any order.  The segment's extents are reduced by every
+ * workgroup of the segment for itself, lanes first, then waves (regroup_extent_merge: any order).  Before that the whole
+ * grid copies the positions this level does not sort. */
+constexpr int kRegroupLanes = 64, kRegroupSlices = kRegroupBlock / kRegroupLanes;
+__global__ __launch_bounds__(kRegroupBlock) void rtc_regroup_level(const double *cent, const int *in, int *out, int n,
+                                                                    int level)
+{
+    const int tid = (int)threadIdx.x, px = tid % kRegroupLanes, slice = tid / kRegroupLanes;
+    {
+        const size_t g = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRegroupBlock + tid;
+        const size_t stride = (size_t)gridDim.x * gridDim.y * kRegroupBlock;
+        for (size_t p = g; p < (size_t)n; p += stride) {
+            int l, h;
+            if (!regroup_segment_of_position(n, level, (int)p, l, h))
+                out[p] = in[p];
+        }
+    }
+    int lo, hi;
+    if (!regroup_segment_of_path(n, level, blockIdx.y, lo, hi) || lo + (int)blockIdx.x * kRegroupLanes >= hi)
+        return; /* (the same for every lane of the workgroup) */
+    __shared__ RegroupExtent sExt[kRegroupSlices][3];
+    __shared__ double sKey[kRegroupBlock];
+    __shared__ int sRank[kRegroupSlices][kRegroupLanes];
+    RegroupExtent e[3] = {regroup_extent_init(), regroup_extent_init(), regroup_extent_init()};
+    for (int q = lo + tid; q < hi; q += kRegroupBlock) {
+        const int i = in[q];
+        for (int a = 0; a < 3; ++a)
+            regroup_extent_take(e[a], cent[(size_t)a * n + i]);
+    }
+    for (int m = 1; m < kRegroupLanes; m <<= 1)
+        for (int a = 0; a < 3; ++a) {
+            const RegroupExtent o{__shfl_xor(e[a].mn, m, kRegroupLanes), __shfl_xor(e[a].mx, m, kRegroupLanes)};
+            regroup_extent_merge(e[a], o);
+        }
+    if (px == 0)
+        for (int a = 0; a < 3; ++a)
+            sExt[slice][a] = e[a];
+    __syncthreads();
+    for (int a = 0; a < 3; ++a) {
+        e[a] = sExt[0][a];
+        for (int w = 1; w < kRegroupSlices; ++w)
+            regroup_extent_merge(e[a], sExt[w][a]);
+    }
+    const double *key = cent + (size_t)regroup_axis(e) * n;
+    const int p = lo + (int)blockIdx.x * kRegroupLanes + px;
+    const bool mine = p < hi;
+    const int ip = mine ? in[p] : 0;
+    const double kp = mine ? regroup_key(key[ip]) : 0.0;
+    int rank = 0;
+    for (int base = lo; base < hi; base += kRegroupBlock) {
+        const int q = base + tid;
+        __syncthreads(); /* the tile before is counted */
+        sKey[tid] = q < hi ? regroup_key(key[in[q]]) : 0.0;
+        __syncthreads();
+        const int j0 = slice * kRegroupLanes, j1 = min(j0 + kRegroupLanes, hi - base);
+        if (mine)
+            for (int j = j0; j < j1; ++j)
+                rank += regroup_rank(sKey[j], base + j, kp, p);
+    }
+    sRank[slice][px] = rank;
+    __syncthreads();
+    if (slice == 0 && mine) {
+        for (int w = 1; w < kRegroupSlices; ++w)
+            rank += sRank[w][px];
+        out[lo + rank] = ip;
+    }
+}
+
+/* the membership as rtc_refit reads it: one int per clustered record, -1 for the last cluster's padding */
+__global__ __launch_bounds__(kRegroupBlock) void rtc_regroup_index(const int *idx, int *clIndex, int n, int slots)
+{
+    const int k = (int)(blockIdx.x * kRegroupBlock + threadIdx.x);
+    if (k < slots)
+        clIndex[k] = k < n ? idx[k] : -1;
 }
 
 extern "C" int rtc_bounce_hit_share(const Triangle *tris, int triCount, float *share)
@@ -1045,19 +1231,52 @@ extern "C" int rtc_scene_release(RtcDeviceScene *s)
     return 0;
 }
 
+/* what rtc_scene_update_async and rtc_scene_regroup_async refuse alike (0: fine) */
+static int update_arguments(const char *who, const RtcDeviceScene *s, const Triangle *dTris, int triCount,
+                            const Sphere *dSpheres, int sphereCount)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "%s: null scene", who);
+    if (!dTris && !dSpheres)
+        return rtc_fail(RTC_EINVAL, "%s: neither triangles nor spheres", who);
+    if (triCount != (dTris ? s->triCount : 0) || sphereCount != (dSpheres ? s->sphereCount : 0))
+        return rtc_fail(RTC_EINVAL, "%s: %d triangles / %d spheres for a scene uploaded with %d / %d "
+                                    "(a kind left out: a null pointer and 0)",
+                        who, triCount, sphereCount, s->triCount, s->sphereCount);
+    if ((dTris && s->triCount == 0) || (dSpheres && s->sphereCount == 0))
+        return rtc_fail(RTC_EINVAL, "%s: the scene was uploaded without that kind of primitive", who);
+    return 0;
+}
+
+/* the planned wait of an update or a regroup: the sky-done event of a slot (false: not one) */
+static bool update_wait(const RtcDeviceScene *s, const rtcplan::Op &op, hipStream_t st, hipError_t &e)
+{
+    const int slot = op.event - rtcplan::kEvSkyDone0;
+    if (op.kind != rtcplan::kOpWait || slot < 0 || slot >= kSkySlots)
+        return false;
+    e = hipStreamWaitEvent(st, s->evSkyDone[slot], 0);
+    return true;
+}
+
+static hipError_t launch_refit(const RtcDeviceScene *s, const Triangle *dTris, const Sphere *dSpheres, int reads, int writes,
+                               hipStream_t st)
+{
+    RefitArgs a{};
+    a.srcTris = dTris, a.srcSpheres = dSpheres;
+    a.from = s->gen[reads], a.to = s->gen[writes];
+    a.clIndex = s->clIndex;
+    a.clusterCount = s->clusterCount, a.sphereCount = s->sphereCount;
+    for (int k = 0; k < 6; ++k)
+        a.n16[k] = s->recBytes[k] / 16;
+    hipLaunchKernelGGL(rtc_refit, dim3((unsigned)std::max(s->chunkCount, 1)), dim3(kRefitBlock), 0, st, a);
+    return hipGetLastError();
+}
+
 extern "C" int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
                                       int sphereCount, void *stream)
 {
-    if (!s)
-        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: null scene");
-    if (!dTris && !dSpheres)
-        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: neither triangles nor spheres");
-    if (triCount != (dTris ? s->triCount : 0) || sphereCount != (dSpheres ? s->sphereCount : 0))
-        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: %d triangles / %d spheres for a scene uploaded with %d / %d "
-                                    "(a kind left out: a null pointer and 0)",
-                        triCount, sphereCount, s->triCount, s->sphereCount);
-    if ((dTris && s->triCount == 0) || (dSpheres && s->sphereCount == 0))
-        return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: the scene was uploaded without that kind of primitive");
+    if (const int rc = update_arguments("rtc_scene_update_async", s, dTris, triCount, dSpheres, sphereCount))
+        return rc;
     RtcDeviceGuard guard(s->device);
     if (!guard.ok())
         return rtc_fail(RTC_ENODEV, "rtc_scene_update_async: cannot select the scene's device %d", s->device);
@@ -1070,25 +1289,106 @@ extern "C" int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, 
         const rtcplan::Op &op = up.ops[i];
         if (op.stream != rtcplan::kStCaller)
             return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: an operation off the caller's stream");
-        const int slot = op.event - rtcplan::kEvSkyDone0;
-        if (op.kind == rtcplan::kOpWait && slot >= 0 && slot < kSkySlots) {
-            HIP_TRY(hipStreamWaitEvent(st, s->evSkyDone[slot], 0));
+        hipError_t e = hipSuccess;
+        if (update_wait(s, op, st, e)) {
+            HIP_TRY(e);
         } else if (op.kind == rtcplan::kOpKernel && op.kernel == rtcplan::kKRefit) {
-            RefitArgs a{};
-            a.srcTris = dTris, a.srcSpheres = dSpheres;
-            a.from = s->gen[up.reads], a.to = s->gen[up.writes];
-            a.clIndex = s->clIndex;
-            a.clusterCount = s->clusterCount, a.sphereCount = s->sphereCount;
-            for (int k = 0; k < 6; ++k)
-                a.n16[k] = s->recBytes[k] / 16;
-            hipLaunchKernelGGL(rtc_refit, dim3((unsigned)std::max(s->chunkCount, 1)), dim3(kRefitBlock), 0, st, a);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_refit(s, dTris, dSpheres, up.reads, up.writes, st));
         } else {
             return rtc_fail(RTC_EINVAL, "rtc_scene_update_async: unknown planned operation %d", op.kind);
         }
     }
     s->plan = up.after; /* every operation is enqueued */
     return 0;
+}
+
+extern "C" int rtc_scene_regroup_max_tris(void)
+{
+    return kRegroupMaxTris;
+}
+
+extern "C" size_t rtc_scene_regroup_scratch_bytes(const RtcDeviceScene *s)
+{
+    return s ? regroup_scratch_bytes(s->triCount) : 0;
+}
+
+extern "C" int rtc_scene_regroup_async(RtcDeviceScene *s, const Triangle *dTris, int triCount, const Sphere *dSpheres,
+                                       int sphereCount, void *dScratch, size_t scratchBytes, void *stream)
+{
+    const char *const who = "rtc_scene_regroup_async";
+    if (const int rc = update_arguments(who, s, dTris, triCount, dSpheres, sphereCount))
+        return rc;
+    if (!dTris)
+        return rtc_fail(RTC_EINVAL, "%s: no triangles (the membership is decided from them)", who);
+    if (triCount > kRegroupMaxTris)
+        return rtc_fail(RTC_EINVAL, "%s: %d triangles, a regroup takes at most %d (rtc_scene_regroup_max_tris): upload again",
+                        who, triCount, kRegroupMaxTris);
+    if (!dScratch || (uintptr_t)dScratch % 16 || scratchBytes < regroup_scratch_bytes(triCount))
+        return rtc_fail(RTC_EINVAL, "%s: the scratch must be %zu bytes of device memory, 16-byte aligned "
+                                    "(rtc_scene_regroup_scratch_bytes)", who, regroup_scratch_bytes(triCount));
+    RtcDeviceGuard guard(s->device);
+    if (!guard.ok())
+        return rtc_fail(RTC_ENODEV, "%s: cannot select the scene's device %d", who, s->device);
+    /* the planner's operations (rtc_plan.h plan_regroup: an update's waits and generation, the membership's kernels, the
+     * refit), executed in order; the level kernels take their levels in the order planned */
+    const int n = triCount;
+    rtcplan::RegroupPlan gp;
+    rtcplan::plan_regroup(s->plan, regroup_levels(n), gp);
+    const RegroupScratch sc = regroup_scratch(dScratch, n);
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n + kRegroupBlock - 1) / kRegroupBlock);
+    int level = 0;
+    for (int i = 0; i < gp.nOps; ++i) {
+        const rtcplan::Op &op = gp.ops[i];
+        if (op.stream != rtcplan::kStCaller)
+            return rtc_fail(RTC_EINVAL, "%s: an operation off the caller's stream", who);
+        hipError_t e = hipSuccess;
+        if (update_wait(s, op, st, e)) {
+            HIP_TRY(e);
+        } else if (op.kind != rtcplan::kOpKernel) {
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned operation %d", who, op.kind);
+        } else if (op.kernel == rtcplan::kKRegroupCentroids) {
+            hipLaunchKernelGGL(rtc_regroup_centroids, dim3(blocks), dim3(kRegroupBlock), 0, st, dTris, sc.cent, sc.idx[0], n);
+            HIP_TRY(hipGetLastError());
+        } else if (op.kernel == rtcplan::kKRegroupLevel && level < gp.levels) {
+            const unsigned tiles = (unsigned)((regroup_level_width(n, level) + kRegroupLanes - 1) / kRegroupLanes);
+            hipLaunchKernelGGL(rtc_regroup_level, dim3(tiles, 1u << level), dim3(kRegroupBlock), 0, st, sc.cent,
+                               sc.idx[level & 1], sc.idx[(level & 1) ^ 1], n, level);
+            HIP_TRY(hipGetLastError());
+            ++level;
+        } else if (op.kernel == rtcplan::kKRegroupIndex) {
+            const int slots = s->clusterCount * kClusterSize;
+            hipLaunchKernelGGL(rtc_regroup_index, dim3((unsigned)((slots + kRegroupBlock - 1) / kRegroupBlock)),
+                               dim3(kRegroupBlock), 0, st, sc.idx[gp.levels & 1], s->clIndex, n, slots);
+            HIP_TRY(hipGetLastError());
+        } else if (op.kernel == rtcplan::kKRefit) {
+            HIP_TRY(launch_refit(s, dTris, dSpheres, gp.reads, gp.writes, st));
+        } else {
+            return rtc_fail(RTC_EINVAL, "%s: unknown planned kernel %d", who, op.kernel);
+        }
+    }
+    s->plan = gp.after; /* every operation is enqueued */
+    return 0;
+}
+
+extern "C" int rtc_scene_regroup(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres,
+                                 int sphereCount)
+{
+    if (!s)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_regroup: null scene");
+    if (!tris || triCount <= 0)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_regroup: no triangles (the membership is decided from them)");
+    /* staged like rtc_scene_update, the scratch with them; the other arguments are checked by the asynchronous call */
+    const bool sph = spheres && sphereCount > 0;
+    const size_t scratch = regroup_scratch_bytes(triCount);
+    const Staged items[3] = {{tris, nullptr, (size_t)triCount * sizeof(Triangle), true},
+                             {spheres, nullptr, sph ? (size_t)sphereCount * sizeof(Sphere) : 0, sph},
+                             {nullptr, nullptr, scratch, true}};
+    return staged_query("rtc_scene_regroup", s, items, [&](void *const dev[3]) {
+        return rtc_scene_regroup_async(s, static_cast<const Triangle *>(dev[0]), triCount,
+                                       spheres ? static_cast<const Sphere *>(dev[1]) : nullptr, sphereCount, dev[2], scratch,
+                                       nullptr);
+    });
 }
 
 extern "C" int rtc_scene_update(RtcDeviceScene *s, const Triangle *tris, int triCount, const Sphere *spheres,
