@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "../../include/rtc.h"
 #include "rtc_device.h"
 #include "rtc_plan.h"
@@ -270,6 +272,28 @@ struct SceneRecords {
     DevCluster *clusters;
     DevCluster *chunks; /* chunkCount balls over kChunkClusters consecutive clusters */
 };
+/* The six arrays of a SceneRecords, named once: whatever allocates, copies, frees, sizes or reports them walks this table
+ * (the Python side's RECORD_ARRAYS has the same names in the same order). */
+enum SceneArrayId : int { kArrTris, kArrMats, kArrSpheres, kArrClTris, kArrClusters, kArrChunks, kSceneArrayCount };
+struct SceneArray {
+    const char *name;
+    size_t elem; /* bytes per record */
+    size_t at;   /* where the array's pointer lives in a SceneRecords */
+};
+constexpr SceneArray kSceneArrays[kSceneArrayCount] = {
+    {"tris", sizeof(DevTri), offsetof(SceneRecords, tris)},
+    {"mats", sizeof(DevMat), offsetof(SceneRecords, mats)},
+    {"spheres", sizeof(DevSphere), offsetof(SceneRecords, spheres)},
+    {"clTris", sizeof(DevTri), offsetof(SceneRecords, clTris)},
+    {"clusters", sizeof(DevCluster), offsetof(SceneRecords, clusters)},
+    {"chunks", sizeof(DevCluster), offsetof(SceneRecords, chunks)},
+};
+static_assert(sizeof(SceneRecords) == kSceneArrayCount * sizeof(void *), "every pointer of a SceneRecords is in the table");
+inline void *&scene_array(SceneRecords &g, int k)
+{
+    return *reinterpret_cast<void **>(reinterpret_cast<unsigned char *>(&g) + kSceneArrays[k].at);
+}
+inline void *scene_array(const SceneRecords &g, int k) { return scene_array(const_cast<SceneRecords &>(g), k); }
 struct RtcDeviceScene {
     int device;
     int cuCount; /* compute units of the device (the persistent chain kernel's workgroups are a multiple of it) */
@@ -288,7 +312,7 @@ struct RtcDeviceScene {
      * one stream at a time (rtc.h), so stream order alone puts every read after the write it means and before the next.
      * Launches in flight read the records of their generation, never this. */
     int *clIndex;
-    size_t recBytes[6]; /* bytes of tris, mats, spheres, clTris, clusters, chunks (each generation) */
+    size_t recBytes[kSceneArrayCount]; /* bytes of each array of kSceneArrays (each generation) */
     /* per-launch primary records, one copy per scratch slot (primStride records each), written by rtc_prep_primary:
      * an overlapped launch's preparation (on the cull stream) may run while the previous frame's geometry kernel still
      * reads its own copy */

@@ -8,8 +8,9 @@
  *     lo + #{q in [lo, hi) : key_q < key_p} + #{q in [lo, p) : key_q == key_p},
  * q over the segment's positions before the sort (regroup_rank).  The keys hold no NaN (regroup_key), so `<` on doubles is
  * a strict weak order and `==` is its equivalence, +0 and -0 together; the count needs no sort primitive, no atomics and
- * is the same whatever the order of evaluation.  These functions restate split_clusters operation for operation;
- * rtc_regroup_membership_host runs them in plain C++ and the regroup kernels on the device (rtc_scene.hip).
+ * is the same whatever the order of evaluation.  split_clusters takes its centroid, extent, axis, key and split point from
+ * these functions; rtc_regroup_membership_host runs the levels in plain C++ and the regroup kernels on the device
+ * (rtc_scene.hip).
  * Pure functions of their arguments; no HIP needed to compile them. */
 #pragma once
 

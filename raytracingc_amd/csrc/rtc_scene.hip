@@ -4,7 +4,9 @@
  * for the bounce rays' culling, the scheduling hint bounce_hit_share, the scene's streams and ordering events, and the
  * per-scene hooks (frame / geometry events, kernel timing); and the same records rewritten in place for new primitives
  * by a kernel (rtc_scene_update_async, rtc_refit), after the clusters were decided anew on the device where
- * asked (rtc_scene_regroup_async, the rtc_regroup_* kernels).
+ * asked (rtc_scene_regroup_async, the rtc_regroup_* kernels).  The records' arithmetic (packing, aligned
+ * normals, balls and margins) is rtc_records.h's and the membership's is rtc_regroup.h's, each stated once: here are the
+ * host's loops and the device's kernels over them, and the six record arrays are walked by rtc_layout.h's table.
  */
 #include <hip/hip_runtime.h>
 
@@ -17,6 +19,7 @@
 #include "rtc_layout.h"
 #include "rtc_internal.h"
 #include "rtc_hip_util.h"
+#include "rtc_records.h"
 #include "rtc_regroup.h"
 #include "rtc_staged.h"
 
@@ -152,172 +155,60 @@ static void pack_scene(const Triangle *tris, int triCount, const Sphere *sph, in
     dt.assign(padded, DevTri{});
     dm.assign(padded, DevMat{});
     for (int i = 0; i < triCount; ++i) {
-        const Triangle &t = tris[i];
-        DevTri &d = dt[i];
-        memset(&d, 0, sizeof d);
-        d.ax = t.posA.x;
-        d.ay = t.posA.y;
-        d.az = t.posA.z;
-        /* raytracing.c:191-192 minus(posB, posA), minus(posC, posA): same f32 ops */
-        d.abx = t.posB.x - t.posA.x;
-        d.aby = t.posB.y - t.posA.y;
-        d.abz = t.posB.z - t.posA.z;
-        d.acx = t.posC.x - t.posA.x;
-        d.acy = t.posC.y - t.posA.y;
-        d.acz = t.posC.z - t.posA.z;
-        d.nx = t.normal.x;
-        d.ny = t.normal.y;
-        d.nz = t.normal.z;
-        DevMat &m = dm[i];
-        memset(&m, 0, sizeof m);
-        m.r = t.mat.color.x;
-        m.g = t.mat.color.y;
-        m.b = t.mat.color.z;
-        m.emission = t.mat.emissionStrength;
-        m.smoothness = t.mat.smoothness;
+        const float *p = reinterpret_cast<const float *>(tris + i);
+        dt[i] = pack_tri(p);
+        dm[i] = pack_mat(p);
     }
     ds.resize(sphCount > 0 ? sphCount : 1);
-    for (int i = 0; i < sphCount; ++i) {
-        DevSphere &d = ds[i];
-        memset(&d, 0, sizeof d);
-        d.cx = sph[i].pos.x;
-        d.cy = sph[i].pos.y;
-        d.cz = sph[i].pos.z;
-        d.radius = sph[i].r;
-        d.r = sph[i].mat.color.x;
-        d.g = sph[i].mat.color.y;
-        d.b = sph[i].mat.color.z;
-        d.emission = sph[i].mat.emissionStrength;
-        d.smoothness = sph[i].mat.smoothness;
-    }
+    for (int i = 0; i < sphCount; ++i)
+        ds[i] = pack_sphere(reinterpret_cast<const float *>(sph + i));
 }
 
 /* Clusters of kClusterSize triangles: recursive splits of the centroids along their longest extent, each
- * split at a multiple of kClusterSize so that every leaf but the last is full (ceil(n / 8) clusters). */
+ * split at a multiple of kClusterSize so that every leaf but the last is full (ceil(n / 8) clusters).  The definition of
+ * the membership; its centroid, extent, axis, key and split point are rtc_regroup.h's, which the device's levels share. */
+static_assert(kRegroupLeaf == kClusterSize, "a leaf of the split is a cluster");
 static void split_clusters(const std::vector<DevTri> &dt, std::vector<int> &idx, size_t lo, size_t hi)
 {
-    const size_t n = hi - lo;
-    if (n <= (size_t)kClusterSize)
+    if (hi - lo <= (size_t)kClusterSize)
         return;
-    double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-    auto centroid = [&](int i, int a) {
-        const DevTri &t = dt[i];
-        const double A[3] = {t.ax, t.ay, t.az}, B[3] = {t.abx, t.aby, t.abz}, C[3] = {t.acx, t.acy, t.acz};
-        return A[a] + (B[a] + C[a]) / 3.0;
+    const auto centroid = [&](int i, int a) {
+        const float *f = &dt[i].ax; /* ax, ay, az, abx, aby, abz, acx, acy, acz */
+        return regroup_centroid(f[a], f[3 + a], f[6 + a]);
     };
+    RegroupExtent e[3] = {regroup_extent_init(), regroup_extent_init(), regroup_extent_init()};
     for (size_t k = lo; k < hi; ++k)
-        for (int a = 0; a < 3; ++a) {
-            const double c = centroid(idx[k], a);
-            if (c == c) {
-                mn[a] = std::min(mn[a], c);
-                mx[a] = std::max(mx[a], c);
-            }
-        }
-    int axis = 0;
-    for (int a = 1; a < 3; ++a)
-        if (mx[a] - mn[a] > mx[axis] - mn[axis])
-            axis = a;
-    std::stable_sort(idx.begin() + lo, idx.begin() + hi, [&](int p, int q) {
-        const double cp = centroid(p, axis), cq = centroid(q, axis);
-        return (cp == cp ? cp : 1e300) < (cq == cq ? cq : 1e300);
-    });
-    const size_t leaves = (n + kClusterSize - 1) / kClusterSize;
-    const size_t mid = lo + (leaves + 1) / 2 * kClusterSize;
+        for (int a = 0; a < 3; ++a)
+            regroup_extent_take(e[a], centroid(idx[k], a));
+    const int axis = regroup_axis(e);
+    std::stable_sort(idx.begin() + lo, idx.begin() + hi,
+                     [&](int p, int q) { return regroup_key(centroid(p, axis)) < regroup_key(centroid(q, axis)); });
+    const size_t mid = (size_t)regroup_mid((int)lo, (int)hi);
     split_clusters(dt, idx, lo, mid);
     split_clusters(dt, idx, mid, hi);
 }
 
-/* Bounding ball and cull margins (DevCluster) of the records ct[first, first + count) whose index (pad0) is
- * >= 0: the ball holds every vertex A, A + AB, A + AC; E is the longest AB / AC edge. */
+/* Bounding ball and cull margins (DevCluster) of the records ct[first, first + count) whose index (pad0) is >= 0, taken
+ * in sequence (rtc_records.h: the order decides the sign of a zero centre). */
 static DevCluster ball_of(const std::vector<DevTri> &ct, size_t first, size_t count)
 {
-    const double u = 0x1p-24, eps = 0.001; /* |det| >= 0.001f > 0.001 for every reported hit */
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, E = 0.0;
-    bool finite = true;
-    int n = 0;
-    auto real = [&](const DevTri &r) {
+    const auto real = [](const DevTri &r) {
         int i;
         memcpy(&i, &r.pad0, sizeof i);
         return i >= 0;
     };
-    for (size_t j = first; j < first + count; ++j) {
-        const DevTri &r = ct[j];
-        if (!real(r))
-            continue;
-        ++n;
-        const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
-        for (int a = 0; a < 3; ++a) {
-            const double v[3] = {A[a], A[a] + B[a], A[a] + C[a]};
-            for (double x : v) {
-                finite = finite && std::isfinite(x);
-                lo[a] = std::min(lo[a], x);
-                hi[a] = std::max(hi[a], x);
-            }
-        }
-        E = std::max(E, std::max(std::sqrt(B[0] * B[0] + B[1] * B[1] + B[2] * B[2]),
-                                 std::sqrt(C[0] * C[0] + C[1] * C[1] + C[2] * C[2])));
-    }
-    DevCluster k{};
-    const double ctr[3] = {(lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, (lo[2] + hi[2]) / 2};
-    k.cx = n ? (float)ctr[0] : 0.f;
-    k.cy = n ? (float)ctr[1] : 0.f;
-    k.cz = n ? (float)ctr[2] : 0.f;
+    BallAcc b;
+    acc_init(b);
+    for (size_t j = first; j < first + count; ++j)
+        if (real(ct[j]))
+            acc_record(b, ct[j]);
+    float c[3];
+    ball_centre(b, c);
     double R = 0.0;
-    for (size_t j = first; j < first + count; ++j) { /* radius about the rounded (float) centre */
-        const DevTri &r = ct[j];
-        if (!real(r))
-            continue;
-        const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
-        const double K[3] = {k.cx, k.cy, k.cz};
-        for (int w = 0; w < 3; ++w) {
-            double d2 = 0.0;
-            for (int a = 0; a < 3; ++a) {
-                const double x = A[a] + (w == 1 ? B[a] : w == 2 ? C[a] : 0.0) - K[a];
-                d2 += x * x;
-            }
-            R = std::max(R, std::sqrt(d2));
-        }
-    }
-    const double F = 4.0, edRatio = 8.0 * u * E * E * kClusterRhoMax / eps;
-    k.r = std::nextafter((float)(R * (1.0 + 1e-9)), INFINITY);
-    k.e = (float)E;
-    if (!finite || n == 0 || !(edRatio < 0.5) || !(k.r < 1e18f)) {
-        k.alpha = INFINITY; /* never culled */
-        k.beta = k.gammaE = 0.f;
-        return k;
-    }
-    const double kk = 1.0 / (1.0 - edRatio);
-    k.alpha = std::nextafter((float)(F * kk * 32.0 * u * E * E * E / eps), INFINITY);
-    k.beta = std::nextafter((float)(F * kk * 45.0 * u * E * E / eps), INFINITY);
-    k.gammaE = std::nextafter((float)(kClusterGamma * E), INFINITY);
-    return k;
-}
-
-/* A triangle whose stored normal N points along its geometric normal G' = AB x AC closely enough that, for every
- * ray of |dir|_1 <= kClusterRhoMax, rayTriangle's backface test (dot(dir, N) < 0, raytracing.c:189) forces
- * det = dot(AB, dir x AC) > -EPSILON (raytracing.c:195): then a hit needs det >= EPSILON, and since
- * dst = dot(AC, q) / det (q = (pos - A) x AB, raytracing.c:202-206) must be >= EPSILON, dot(AC, q) > 0.  For a
- * ray origin where the reference's own f32 dot(AC, q) is <= 0 (pos on or behind the plane), the triangle cannot
- * be hit from there in any direction (rtc_render_chain's first bounces).  Bound: with N = a G'/|G'| + e (e
- * orthogonal), fl(dot(dir, N)) < 0 gives dir.G'/|G'| < rho (3.01u |N|_inf + |e|) / a, and |det + dir.G'| <=
- * 5.1u |AB|_1 |AC|_1 rho; aligned when rho times their sum, with a factor 2, stays below EPSILON. */
-static bool aligned_normal(const DevTri &r)
-{
-    const double u = 0x1p-24;
-    const double AB[3] = {r.abx, r.aby, r.abz}, AC[3] = {r.acx, r.acy, r.acz}, N[3] = {r.nx, r.ny, r.nz};
-    const double G[3] = {AB[1] * AC[2] - AB[2] * AC[1], AB[2] * AC[0] - AB[0] * AC[2], AB[0] * AC[1] - AB[1] * AC[0]};
-    const double g = std::sqrt(G[0] * G[0] + G[1] * G[1] + G[2] * G[2]);
-    if (!(g > 0.0) || !std::isfinite(g))
-        return false;
-    const double a = (N[0] * G[0] + N[1] * G[1] + N[2] * G[2]) / g;
-    if (!(a > 0.0))
-        return false;
-    const double e[3] = {N[0] - a * G[0] / g, N[1] - a * G[1] / g, N[2] - a * G[2] / g};
-    const double en = std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + 1e-12 * (std::fabs(N[0]) + std::fabs(N[1]) + std::fabs(N[2]));
-    const double ninf = std::max(std::fabs(N[0]), std::max(std::fabs(N[1]), std::fabs(N[2])));
-    const double n1 = std::fabs(AB[0]) + std::fabs(AB[1]) + std::fabs(AB[2]), c1 = std::fabs(AC[0]) + std::fabs(AC[1]) + std::fabs(AC[2]);
-    const double K = g * (3.01 * u * ninf + en) / a + 5.1 * u * n1 * c1;
-    return std::isfinite(K) && 2.0 * kClusterRhoMax * K < 0.001;
+    for (size_t j = first; j < first + count; ++j)
+        if (real(ct[j]))
+            R = std::max(R, rec_radius(ct[j], c));
+    return ball_finish(b, c, R);
 }
 
 /* The cluster membership: idx[k] = the reference index of clustered record k (idx holds triCount entries; the last
@@ -395,7 +286,7 @@ extern "C" int rtc_regroup_membership_host(const Triangle *tris, int triCount, i
 
 /* The one host statement of the clustered records for a membership `idx` (rtc_cluster_membership): upload builds them
  * from the membership it has just decided, a refit (rtc_scene_records_host with new triangles; on the device rtc_refit,
- * operation for operation) from the upload's membership and the new packed records dt. */
+ * from the same functions of rtc_records.h) from the upload's membership and the new packed records dt. */
 static void rtc_cluster_records(const std::vector<DevTri> &dt, int triCount, const std::vector<int> &idx,
                                 std::vector<DevTri> &ct, std::vector<DevCluster> &cl, std::vector<DevCluster> &ch)
 {
@@ -438,6 +329,14 @@ struct HostRecords {
     std::vector<DevSphere> ds;
     std::vector<DevCluster> cl, ch;
     std::vector<int> idx;
+    /* the six record arrays in kSceneArrays' order: where each lies and its bytes */
+    void arrays(const void *data[kSceneArrayCount], size_t bytes[kSceneArrayCount]) const
+    {
+        const void *const d[kSceneArrayCount] = {dt.data(), dm.data(), ds.data(), ct.data(), cl.data(), ch.data()};
+        const size_t n[kSceneArrayCount] = {dt.size(), dm.size(), ds.size(), ct.size(), cl.size(), ch.size()};
+        for (int k = 0; k < kSceneArrayCount; ++k)
+            data[k] = d[k], bytes[k] = n[k] * kSceneArrays[k].elem;
+    }
 };
 static void host_records(const Triangle *tris, int triCount, const Sphere *spheres, int sphereCount, bool refit,
                          HostRecords &R)
@@ -455,64 +354,18 @@ static void host_records(const Triangle *tris, int triCount, const Sphere *spher
  * pack_scene and rtc_cluster_records produce for the upload's membership (clIndex), byte for byte.  One workgroup per
  * chunk, one lane per clustered record: the lane packs its triangle (tris / mats in reference order, clTris in cluster
  * order with the aligned-normal flag), its cluster's ball comes from reductions over the aligned group of 8 lanes, the
- * chunk's from those through LDS.  ball_of and aligned_normal are restated operation for operation in double
- * (-ffp-contract=off; IEEE divide; __dsqrt_rn; nextafter towards +inf of a non-negative float is a bit increment); the
- * min / max reductions are exact and skip NaN exactly as std::min / std::max with the accumulator first do, so their
- * order does not matter.  A kind of primitive the caller leaves out is copied from the current generation. */
+ * chunk's from those through LDS.  The packing, the aligned-normal flag and the ball are rtc_records.h's functions, the ones
+ * the host's loops run; the partial extents merged here hold no NaN and the merges keep the lower lane's and the lower
+ * cluster's value where two are equal, the one the host's sequence keeps.  A kind of primitive the caller leaves out is
+ * copied from the current generation. */
 struct RefitArgs {
     const Triangle *srcTris;  /* null: copy the triangles' records of `from` */
     const Sphere *srcSpheres; /* null: copy from's spheres */
     SceneRecords from, to;
     const int *clIndex;
     int clusterCount, sphereCount;
-    size_t n16[6]; /* 16-byte words of tris, mats, spheres, clTris, clusters, chunks */
+    size_t n16[kSceneArrayCount]; /* 16-byte words of each array (rtc_layout.h kSceneArrays) */
 };
-
-struct BallAcc {
-    double lo[3], hi[3], E;
-    int finite, n;
-};
-
-__device__ __forceinline__ void acc_init(BallAcc &b)
-{
-    for (int a = 0; a < 3; ++a)
-        b.lo[a] = 1e300, b.hi[a] = -1e300;
-    b.E = 0.0;
-    b.finite = 1;
-    b.n = 0;
-}
-
-/* ball_of's first loop for one real record */
-__device__ __forceinline__ void acc_record(BallAcc &b, const DevTri &r)
-{
-    ++b.n;
-    const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
-    for (int a = 0; a < 3; ++a) {
-        const double v[3] = {A[a], A[a] + B[a], A[a] + C[a]};
-        for (int w = 0; w < 3; ++w) {
-            const double x = v[w];
-            b.finite = b.finite && isfinite(x);
-            b.lo[a] = x < b.lo[a] ? x : b.lo[a];
-            b.hi[a] = b.hi[a] < x ? x : b.hi[a];
-        }
-    }
-    const double sb = __dsqrt_rn(B[0] * B[0] + B[1] * B[1] + B[2] * B[2]);
-    const double sc = __dsqrt_rn(C[0] * C[0] + C[1] * C[1] + C[2] * C[2]);
-    const double m = sb < sc ? sc : sb; /* std::max(sb, sc) */
-    b.E = b.E < m ? m : b.E;
-}
-
-/* two partial results of that loop (neither holds a NaN: the loop never stores one) */
-__device__ __forceinline__ void acc_merge(BallAcc &b, const BallAcc &o)
-{
-    for (int a = 0; a < 3; ++a) {
-        b.lo[a] = o.lo[a] < b.lo[a] ? o.lo[a] : b.lo[a];
-        b.hi[a] = b.hi[a] < o.hi[a] ? o.hi[a] : b.hi[a];
-    }
-    b.E = b.E < o.E ? o.E : b.E;
-    b.finite = b.finite && o.finite;
-    b.n += o.n;
-}
 
 __device__ __forceinline__ BallAcc acc_shfl_xor(const BallAcc &b, int mask)
 {
@@ -525,78 +378,6 @@ __device__ __forceinline__ BallAcc acc_shfl_xor(const BallAcc &b, int mask)
     o.finite = __shfl_xor(b.finite, mask, kClusterSize);
     o.n = __shfl_xor(b.n, mask, kClusterSize);
     return o;
-}
-
-__device__ __forceinline__ void ball_centre(const BallAcc &b, float c[3])
-{
-    for (int a = 0; a < 3; ++a)
-        c[a] = b.n ? (float)((b.lo[a] + b.hi[a]) / 2) : 0.f;
-}
-
-/* ball_of's second loop for one real record: the largest distance of its vertices from the (float) centre */
-__device__ __forceinline__ double rec_radius(const DevTri &r, const float c[3])
-{
-    const double A[3] = {r.ax, r.ay, r.az}, B[3] = {r.abx, r.aby, r.abz}, C[3] = {r.acx, r.acy, r.acz};
-    const double K[3] = {c[0], c[1], c[2]};
-    double R = 0.0;
-    for (int w = 0; w < 3; ++w) {
-        double d2 = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const double x = A[a] + (w == 1 ? B[a] : w == 2 ? C[a] : 0.0) - K[a];
-            d2 += x * x;
-        }
-        const double s = __dsqrt_rn(d2);
-        R = R < s ? s : R;
-    }
-    return R;
-}
-
-__device__ __forceinline__ float next_up(float x) /* nextafter(x, +inf) for x >= 0, +inf or NaN */
-{
-    if (!(x < INFINITY))
-        return x;
-    return __uint_as_float(x == 0.f ? 1u : __float_as_uint(x) + 1u);
-}
-
-/* ball_of's last part: the record from the reduced extent, the centre and the radius about it */
-__device__ __forceinline__ DevCluster ball_finish(const BallAcc &b, const float c[3], double R)
-{
-    const double u = 0x1p-24, eps = 0.001, E = b.E;
-    DevCluster k{};
-    k.cx = c[0], k.cy = c[1], k.cz = c[2];
-    const double F = 4.0, edRatio = 8.0 * u * E * E * kClusterRhoMax / eps;
-    k.r = next_up((float)(R * (1.0 + 1e-9)));
-    k.e = (float)E;
-    if (!b.finite || b.n == 0 || !(edRatio < 0.5) || !(k.r < 1e18f)) {
-        k.alpha = INFINITY; /* never culled */
-        k.beta = k.gammaE = 0.f;
-        return k;
-    }
-    const double kk = 1.0 / (1.0 - edRatio);
-    k.alpha = next_up((float)(F * kk * 32.0 * u * E * E * E / eps));
-    k.beta = next_up((float)(F * kk * 45.0 * u * E * E / eps));
-    k.gammaE = next_up((float)(kClusterGamma * E));
-    return k;
-}
-
-__device__ __forceinline__ bool aligned_normal_dev(const DevTri &r) /* aligned_normal */
-{
-    const double u = 0x1p-24;
-    const double AB[3] = {r.abx, r.aby, r.abz}, AC[3] = {r.acx, r.acy, r.acz}, N[3] = {r.nx, r.ny, r.nz};
-    const double G[3] = {AB[1] * AC[2] - AB[2] * AC[1], AB[2] * AC[0] - AB[0] * AC[2], AB[0] * AC[1] - AB[1] * AC[0]};
-    const double g = __dsqrt_rn(G[0] * G[0] + G[1] * G[1] + G[2] * G[2]);
-    if (!(g > 0.0) || !isfinite(g))
-        return false;
-    const double a = (N[0] * G[0] + N[1] * G[1] + N[2] * G[2]) / g;
-    if (!(a > 0.0))
-        return false;
-    const double e[3] = {N[0] - a * G[0] / g, N[1] - a * G[1] / g, N[2] - a * G[2] / g};
-    const double en = __dsqrt_rn(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + 1e-12 * (fabs(N[0]) + fabs(N[1]) + fabs(N[2]));
-    const double m12 = fabs(N[1]) < fabs(N[2]) ? fabs(N[2]) : fabs(N[1]);
-    const double ninf = fabs(N[0]) < m12 ? m12 : fabs(N[0]);
-    const double n1 = fabs(AB[0]) + fabs(AB[1]) + fabs(AB[2]), c1 = fabs(AC[0]) + fabs(AC[1]) + fabs(AC[2]);
-    const double K = g * (3.01 * u * ninf + en) / a + 5.1 * u * n1 * c1;
-    return isfinite(K) && 2.0 * kClusterRhoMax * K < 0.001;
 }
 
 __device__ __forceinline__ void copy16(void *dst, const void *src, size_t n16, size_t first, size_t stride)
@@ -613,19 +394,17 @@ __global__ __launch_bounds__(kRefitBlock) void rtc_refit(RefitArgs a)
     const int tid = (int)threadIdx.x, h = (int)blockIdx.x;
     const size_t gt = (size_t)h * kRefitBlock + tid, gstride = (size_t)gridDim.x * kRefitBlock;
     if (a.srcSpheres) { /* pack_scene's sphere loop */
-        for (size_t i = gt; i < (size_t)a.sphereCount; i += gstride) {
-            const float *p = reinterpret_cast<const float *>(a.srcSpheres) + 9 * i; /* pos, r, color, emission, smoothness */
-            a.to.spheres[i] = DevSphere{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], 0.f, 0.f, 0.f};
-        }
+        for (size_t i = gt; i < (size_t)a.sphereCount; i += gstride)
+            a.to.spheres[i] = pack_sphere(reinterpret_cast<const float *>(a.srcSpheres) + 9 * i);
     } else {
-        copy16(a.to.spheres, a.from.spheres, a.n16[2], gt, gstride);
+        copy16(a.to.spheres, a.from.spheres, a.n16[kArrSpheres], gt, gstride);
     }
     if (!a.srcTris) { /* (the same for every lane of the grid) */
-        copy16(a.to.tris, a.from.tris, a.n16[0], gt, gstride);
-        copy16(a.to.mats, a.from.mats, a.n16[1], gt, gstride);
-        copy16(a.to.clTris, a.from.clTris, a.n16[3], gt, gstride);
-        copy16(a.to.clusters, a.from.clusters, a.n16[4], gt, gstride);
-        copy16(a.to.chunks, a.from.chunks, a.n16[5], gt, gstride);
+        copy16(a.to.tris, a.from.tris, a.n16[kArrTris], gt, gstride);
+        copy16(a.to.mats, a.from.mats, a.n16[kArrMats], gt, gstride);
+        copy16(a.to.clTris, a.from.clTris, a.n16[kArrClTris], gt, gstride);
+        copy16(a.to.clusters, a.from.clusters, a.n16[kArrClusters], gt, gstride);
+        copy16(a.to.chunks, a.from.chunks, a.n16[kArrChunks], gt, gstride);
         return;
     }
     __shared__ BallAcc sAcc[kChunkClusters];
@@ -635,16 +414,12 @@ __global__ __launch_bounds__(kRefitBlock) void rtc_refit(RefitArgs a)
     const int i = valid ? a.clIndex[slot] : -1;
     DevTri r{};
     if (i >= 0) {
-        const float *p = reinterpret_cast<const float *>(a.srcTris) + 17 * (size_t)i; /* posA, posB, posC, normal, mat */
-        r.ax = p[0], r.ay = p[1], r.az = p[2];
-        /* raytracing.c:191-192 minus(posB, posA), minus(posC, posA): same f32 ops */
-        r.abx = p[3] - p[0], r.aby = p[4] - p[1], r.abz = p[5] - p[2];
-        r.acx = p[6] - p[0], r.acy = p[7] - p[1], r.acz = p[8] - p[2];
-        r.nx = p[9], r.ny = p[10], r.nz = p[11];
+        const float *p = reinterpret_cast<const float *>(a.srcTris) + 17 * (size_t)i;
+        r = pack_tri(p);
         a.to.tris[i] = r;
-        a.to.mats[i] = DevMat{p[12], p[13], p[14], p[15], p[16], 0.f, 0.f, 0.f};
+        a.to.mats[i] = pack_mat(p);
         r.pad0 = __int_as_float(i);
-        r.pad1 = __int_as_float(aligned_normal_dev(r) ? 1 : 0);
+        r.pad1 = __int_as_float(aligned_normal(r) ? 1 : 0);
     } else {
         r.pad0 = __int_as_float(-1); /* zero record: never hit */
     }
@@ -727,11 +502,9 @@ __global__ __launch_bounds__(kRegroupBlock) void rtc_regroup_centroids(const Tri
     const int i = (int)(blockIdx.x * kRegroupBlock + threadIdx.x);
     if (i >= n)
         return;
-    const float *p = reinterpret_cast<const float *>(tris) + 17 * (size_t)i; /* posA, posB, posC, normal, mat */
-    for (int a = 0; a < 3; ++a) {
-        const float ab = p[3 + a] - p[a], ac = p[6 + a] - p[a]; /* pack_scene's f32 AB, AC */
-        cent[(size_t)a * n + i] = regroup_centroid(p[a], ab, ac);
-    }
+    const float *p = reinterpret_cast<const float *>(tris) + 17 * (size_t)i;
+    for (int a = 0; a < 3; ++a)
+        cent[(size_t)a * n + i] = regroup_centroid(p[a], pack_edge(p, 1, a), pack_edge(p, 2, a));
     idx[i] = i;
 }
 
@@ -1107,22 +880,18 @@ extern "C" int rtc_scene_upload_with_share(const Triangle *tris, int triCount, c
                          s->hitShareAll <= rtcplan::kSplitMaxHitShare;
     /* two generations of the records (rtc_scene_update_async writes the one no launch binds); the upload's are
      * generation 0, generation 1 starts zeroed (its padding records stay zero: an update writes the real ones) */
-    const void *const host[6] = {R.dt.data(), R.dm.data(), R.ds.data(), R.ct.data(), R.cl.data(), R.ch.data()};
-    const size_t bytes[6] = {R.dt.size() * sizeof(DevTri),     R.dm.size() * sizeof(DevMat),
-                             R.ds.size() * sizeof(DevSphere),  R.ct.size() * sizeof(DevTri),
-                             R.cl.size() * sizeof(DevCluster), R.ch.size() * sizeof(DevCluster)};
+    const void *host[kSceneArrayCount];
+    R.arrays(host, s->recBytes);
     hipError_t e = hipSuccess;
-    for (int g = 0; g < 2; ++g) {
-        void **const dev[6] = {(void **)&s->gen[g].tris,   (void **)&s->gen[g].mats,     (void **)&s->gen[g].spheres,
-                               (void **)&s->gen[g].clTris, (void **)&s->gen[g].clusters, (void **)&s->gen[g].chunks};
-        for (int k = 0; k < 6; ++k) {
-            s->recBytes[k] = bytes[k];
+    for (int g = 0; g < 2; ++g)
+        for (int k = 0; k < kSceneArrayCount; ++k) {
+            void *&dev = scene_array(s->gen[g], k);
+            const size_t bytes = s->recBytes[k];
             if (e == hipSuccess)
-                e = hipMalloc(dev[k], bytes[k]);
+                e = hipMalloc(&dev, bytes);
             if (e == hipSuccess)
-                e = g == 0 ? hipMemcpy(*dev[k], host[k], bytes[k], hipMemcpyHostToDevice) : hipMemset(*dev[k], 0, bytes[k]);
+                e = g == 0 ? hipMemcpy(dev, host[k], bytes, hipMemcpyHostToDevice) : hipMemset(dev, 0, bytes);
         }
-    }
     /* the membership, one int per clustered record (-1: the last cluster's padding) */
     std::vector<int> clIndex(R.ct.size(), -1);
     std::copy(R.idx.begin(), R.idx.end(), clIndex.begin());
@@ -1187,9 +956,8 @@ extern "C" int rtc_scene_release(RtcDeviceScene *s)
     if (s->cst2)
         (void)hipStreamSynchronize(s->cst2);
     for (const SceneRecords &g : s->gen)
-        for (void *p : {(void *)g.tris, (void *)g.mats, (void *)g.spheres, (void *)g.clTris, (void *)g.clusters,
-                        (void *)g.chunks})
-            if (p)
+        for (int k = 0; k < kSceneArrayCount; ++k)
+            if (void *p = scene_array(g, k))
                 (void)hipFree(p);
     if (s->clIndex)
         (void)hipFree(s->clIndex);
@@ -1266,7 +1034,7 @@ static hipError_t launch_refit(const RtcDeviceScene *s, const Triangle *dTris, c
     a.from = s->gen[reads], a.to = s->gen[writes];
     a.clIndex = s->clIndex;
     a.clusterCount = s->clusterCount, a.sphereCount = s->sphereCount;
-    for (int k = 0; k < 6; ++k)
+    for (int k = 0; k < kSceneArrayCount; ++k)
         a.n16[k] = s->recBytes[k] / 16;
     hipLaunchKernelGGL(rtc_refit, dim3((unsigned)std::max(s->chunkCount, 1)), dim3(kRefitBlock), 0, st, a);
     return hipGetLastError();
@@ -1378,7 +1146,7 @@ extern "C" int rtc_scene_regroup(RtcDeviceScene *s, const Triangle *tris, int tr
         return rtc_fail(RTC_EINVAL, "rtc_scene_regroup: null scene");
     if (!tris || triCount <= 0)
         return rtc_fail(RTC_EINVAL, "rtc_scene_regroup: no triangles (the membership is decided from them)");
-    /* staged like rtc_scene_update, the scratch with them; the other arguments are checked by the asynchronous call */
+    /* staged as rtc_scene_update stages, the scratch with them; the other arguments are checked by the asynchronous call */
     const bool sph = spheres && sphereCount > 0;
     const size_t scratch = regroup_scratch_bytes(triCount);
     const Staged items[3] = {{tris, nullptr, (size_t)triCount * sizeof(Triangle), true},
@@ -1396,42 +1164,21 @@ extern "C" int rtc_scene_update(RtcDeviceScene *s, const Triangle *tris, int tri
 {
     if (!s)
         return rtc_fail(RTC_EINVAL, "rtc_scene_update: null scene");
-    RtcDeviceGuard guard(s->device);
-    if (!guard.ok())
-        return rtc_fail(RTC_ENODEV, "rtc_scene_update: cannot select the scene's device %d", s->device);
-    /* staged through two device buffers on the null stream; the arguments are checked by the asynchronous call */
-    Triangle *dT = nullptr;
-    Sphere *dS = nullptr;
-    hipError_t e = hipSuccess;
-    if (tris && triCount > 0) {
-        e = hipMalloc(&dT, (size_t)triCount * sizeof(Triangle));
-        if (e == hipSuccess)
-            e = hipMemcpy(dT, tris, (size_t)triCount * sizeof(Triangle), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && spheres && sphereCount > 0) {
-        e = hipMalloc(&dS, (size_t)sphereCount * sizeof(Sphere));
-        if (e == hipSuccess)
-            e = hipMemcpy(dS, spheres, (size_t)sphereCount * sizeof(Sphere), hipMemcpyHostToDevice);
-    }
-    /* a host caller names no stream: every launch enqueued so far, on whichever stream, ends before the update */
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    int rc = e == hipSuccess ? rtc_scene_update_async(s, tris ? dT : nullptr, triCount, spheres ? dS : nullptr,
-                                                      sphereCount, nullptr)
-                             : rtc_fail(-(int)e, "rtc_scene_update: staging failed: %s", hipGetErrorString(e));
-    if (rc == 0 && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
-        rc = rtc_fail(-(int)e, "rtc_scene_update: %s", hipGetErrorString(e));
-    if (dT)
-        (void)hipFree(dT);
-    if (dS)
-        (void)hipFree(dS);
-    return rc;
+    /* staged through two device buffers (a kind left out, or given with no count: a null pointer and the caller's count);
+     * the arguments are checked by the asynchronous call */
+    const bool tri = tris && triCount > 0, sph = spheres && sphereCount > 0;
+    const Staged items[2] = {{tris, nullptr, tri ? (size_t)triCount * sizeof(Triangle) : 0, tri},
+                             {spheres, nullptr, sph ? (size_t)sphereCount * sizeof(Sphere) : 0, sph}};
+    return staged_query("rtc_scene_update", s, items, [&](void *const dev[2]) {
+        return rtc_scene_update_async(s, static_cast<const Triangle *>(dev[0]), triCount,
+                                      static_cast<const Sphere *>(dev[1]), sphereCount, nullptr);
+    });
 }
 
 /* copies `bytes` of `src` (host or device) into out when the caller gave a buffer, and reports the size */
-static int give_records(void *const out[6], size_t cap[6], const void *const src[6], const size_t bytes[6], bool device)
+static int give_records(void *const out[], size_t cap[], const void *const src[], const size_t bytes[], bool device)
 {
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < kSceneArrayCount; ++k) {
         if (out[k] && cap[k] < bytes[k])
             return rtc_fail(RTC_EINVAL, "scene records: buffer %d holds %zu bytes of %zu", k, cap[k], bytes[k]);
         if (out[k] && device)
@@ -1453,11 +1200,10 @@ extern "C" int rtc_scene_records_host(const Triangle *tris, int triCount, const 
     host_records(tris, triCount, spheres, sphereCount, false, R);
     if (newTris)
         host_records(newTris, triCount, spheres, sphereCount, true, R);
-    void *const out[6] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
-    const void *const src[6] = {R.dt.data(), R.dm.data(), R.ds.data(), R.ct.data(), R.cl.data(), R.ch.data()};
-    const size_t have[6] = {R.dt.size() * sizeof(DevTri),     R.dm.size() * sizeof(DevMat),
-                            R.ds.size() * sizeof(DevSphere),  R.ct.size() * sizeof(DevTri),
-                            R.cl.size() * sizeof(DevCluster), R.ch.size() * sizeof(DevCluster)};
+    void *const out[kSceneArrayCount] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
+    const void *src[kSceneArrayCount];
+    size_t have[kSceneArrayCount];
+    R.arrays(src, have);
     return give_records(out, bytes, src, have, false);
 }
 
@@ -1471,8 +1217,10 @@ extern "C" int rtc_probe_scene_records(const RtcDeviceScene *s, void *outTris, v
         return rtc_fail(RTC_ENODEV, "rtc_probe_scene_records: cannot select the scene's device %d", s->device);
     HIP_TRY(hipDeviceSynchronize()); /* the scene's streams and the caller's: every update enqueued so far has run */
     const SceneRecords &g = s->current();
-    void *const out[6] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
-    const void *const src[6] = {g.tris, g.mats, g.spheres, g.clTris, g.clusters, g.chunks};
+    void *const out[kSceneArrayCount] = {outTris, outMats, outSpheres, outClTris, outClusters, outChunks};
+    const void *src[kSceneArrayCount];
+    for (int k = 0; k < kSceneArrayCount; ++k)
+        src[k] = scene_array(g, k);
     return give_records(out, bytes, src, s->recBytes, true);
 }
 

@@ -1,5 +1,6 @@
 /* rtc_staged.h -- the host path of the entries that take HOST arrays (rtc_trace_rays, rtc_trace_paths, rtc_occluded,
- * rtc_ray_order): staged through device buffers around the asynchronous entry, stated once (C++ only). */
+ * rtc_ray_order, rtc_scene_update, rtc_scene_regroup): staged through device buffers around the asynchronous entry, stated
+ * once (C++ only). */
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,8 +17,8 @@ struct Staged {
     bool want;
 };
 
-/* A query's host entry (n > 0, nothing refused): staged through device buffers on the null stream, like
- * rtc_scene_update.  `call` gets the device pointers in the items' order and issues the asynchronous entry. */
+/* A host entry (a non-null scene, nothing refused): staged through device buffers on the null stream.  `call` gets the
+ * device pointers in the items' order (null for an item not wanted) and issues the asynchronous entry. */
 template <int N, class Call>
 static int staged_query(const char *who, const RtcDeviceScene *s, const Staged (&items)[N], Call call)
 {
