@@ -30,7 +30,7 @@ $(BUILD)/scene_build.o: $(CSRC)/scene_build.c $(CSRC)/rtc_internal.h include/rtc
 	$(CC) $(CFLAGS) -c $< -o $@
 
 # header dependencies: explicit below, and generated (-MMD) for anything the explicit lists miss
-HDRS     := $(CSRC)/rtc_params.h $(CSRC)/rtc_closest.h $(CSRC)/rtc_diag.h $(CSRC)/rtc_cull.h $(CSRC)/rtc_lane.h $(CSRC)/rtc_sky.h $(CSRC)/rtc_chain.h $(CSRC)/rtc_first_hit.h $(CSRC)/rtc_trace_rays.h $(CSRC)/rtc_trace_paths.h $(CSRC)/rtc_occluded.h \
+HDRS     := $(CSRC)/rtc_params.h $(CSRC)/rtc_closest.h $(CSRC)/rtc_diag.h $(CSRC)/rtc_cull.h $(CSRC)/rtc_lane.h $(CSRC)/rtc_sky.h $(CSRC)/rtc_chain.h $(CSRC)/rtc_first_hit.h $(CSRC)/rtc_trace_rays.h $(CSRC)/rtc_trace_paths.h $(CSRC)/rtc_occluded.h $(CSRC)/rtc_render_pixels.h \
             $(CSRC)/rtc_layout.h $(CSRC)/rtc_plan.h $(CSRC)/rtc_device.h $(CSRC)/rtc_math.h $(CSRC)/rtc_bm_tables.h $(CSRC)/rtc_hip_util.h $(CSRC)/rtc_staged.h $(CSRC)/rtc_regroup.h $(CSRC)/rtc_records.h $(CSRC)/rtc_internal.h include/rtc.h
 -include $(wildcard $(BUILD)/*.d)
 

@@ -97,7 +97,8 @@ typedef struct RtcRenderDesc {
 #define RTC_F_NO_DRAW_CACHE 0x4000 /* the launch neither reads nor fills the scene's draw cache (rtc_scene_set_draw_cache):
                                       rtc_render_chain computes every hit draw as before the cache.  A/B timing and
                                       tests.  Same frame bit for bit. */
-#define RTC_F_WAVE_PER_RAY  0x20000 /* rtc_trace_paths_async / rtc_trace_paths only (every other entry: RTC_EINVAL): one
+#define RTC_F_WAVE_PER_RAY  0x20000 /* rtc_trace_paths_async / rtc_trace_paths, and rtc_render_pixels_async / rtc_render_pixels
+                                       (a wave per listed pixel), only (every other entry: RTC_EINVAL): one
                                        wave per ray, the ray's samples on the wave's lanes at RNG offsets 7 draws apart
                                        (lane j starts 7 j draws after the ray's state), instead of one
                                        lane per ray.  Same radiance, seeds and segment count bit for bit; for few rays
@@ -504,6 +505,49 @@ int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, const float *d
  * (each nullable, not both; *count += the occluded rays).  The same refusals; RTC_ENODEV without a GPU. */
 int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly, int flags,
                  unsigned char *occluded, unsigned long long *count);
+/* A pass over a list of pixels of a progressive frame: rtc_render_samples_async for the listed pixels
+ * alone, in the frame's own buffers, in place.  d, range, dColors, dAccum and dRngState mean what they mean there: the
+ * frame's desc (d->spp gives the weight (float)(1. / spp)) and the frame's three buffers, compact in launch-row order.
+ * dPixels[k] is a compact pixel index p = launchRow * width + x: the index of the pixel's rngState; its accumulator lies
+ * at 3 p and its Color at bytes 3 p .. 3 p + 2.  For every listed p < rows_selected * width: x = p % width, the launch
+ * row r = p / width, the image row y as a launch selects it (rowStart, rowStride, rowBand), the ray {cam->origin, the
+ * direction of main.c:88-94 for (x, y)}.  With range->first == 0 neither buffer is read: the pixel starts from the seed
+ * x + y * width and +0; otherwise from dRngState[p] and dAccum[3 p ..].  Then range->count times acc = acc +
+ * calcColor(ray, trianglesOnly, maxBounce, *scene) * (float)(1. / spp); then dAccum[3 p ..] and dRngState[p] are stored
+ * and, where dColors is not null, vec3ToColor(acc) at dColors[3 p .. 3 p + 2], with byte stores only (a pixel whose primary
+ * ray misses draws nothing: its state stays its seed, which a first == 0 pass writes).  dSegments, where not null, is ONE
+ * device u64 (rtc_trace_paths_async's, not a launch's counter array) to which the launch atomically adds its number of
+ * calculateRayCollision calls.
+ * The contract: after whole passes over [0, a) and a pixel pass over [a, b) with list L, every p in L holds the
+ * accumulator, the RNG state and the Color of whole passes over [0, b), bit for bit, and every p not in L holds, byte for
+ * byte, what it held before.  Pixel passes chain like whole passes and may alternate with them.
+ * An index >= rows_selected * width is skipped: its lane or wave loads and stores nothing (a stale list is never an
+ * out-of-bounds access).  Duplicates are the caller's error: the values at a duplicated pixel are unspecified, nothing
+ * else is affected.
+ * flags (the entry's own): 0, RTC_F_NO_CLUSTER_CULL, RTC_F_WAVE_PER_RAY -- here one wave per listed pixel -- or both; the
+ * same words under each.  Of d->flags, RTC_F_DEBUG_BOUNCES and RTC_F_OVERLAP are refused (calcDebugColor is not offered
+ * for pixel lists) and so are the removed kernels' flags; the remaining bits only choose routes of frame launches and are
+ * ignored, so a caller passes the desc it passes to its whole passes.
+ * Asynchronous on `stream` and complete there, under rtc_trace_paths_async's rules: it reads the generation current when
+ * it is enqueued, uses no scratch, primary record, counter set, stream or event of the scene's, leaves the one-shot
+ * events, rtc_scene_chain_report, rtc_scene_kernel_times and the draw cache as they were and restores the caller's current
+ * device.  It waits for nothing beyond stream order: whole passes are joined, so they and other pixel passes on `stream`
+ * are complete before it; the frame's buffers must not be the target of an RTC_F_OVERLAP launch still in flight.
+ * n == 0 or rows_selected == 0: returns 0, nothing enqueued.
+ * RTC_EINVAL, with nothing enqueued, checked before any device call and before `s` is read: a null s, scene, cam, d,
+ * range, dPixels, dAccum or dRngState; n > 0x7fffffff; bad geometry (as rtc_render_rows_async); d->spp <= 0; first < 0,
+ * count <= 0 or first + count > spp; the d->flags named above; any other bit in flags. */
+int rtc_render_pixels_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                            const RtcSampleRange *range, const unsigned int *dPixels, size_t n, int flags,
+                            void *dColors /* nullable */, float *dAccum, unsigned int *dRngState,
+                            unsigned long long *dSegments /* nullable, ONE u64 */, void *stream);
+/* The same for HOST arrays, synchronous, built like rtc_trace_paths: stages the list, the frame's three whole buffers
+ * (colors nullable; each goes in as well as out, so the pixels that are not listed come back as they were) and the
+ * counter's value, waits for the device, runs the pass on the null stream and copies the buffers and *segments back.  The
+ * same refusals; RTC_ENODEV without a GPU. */
+int rtc_render_pixels(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                      const RtcSampleRange *range, const unsigned int *pixels, size_t n, int flags, void *colors,
+                      float *accum, unsigned int *rngState, unsigned long long *segments);
 /* A coherent order for caller-supplied rays.  The three queries above put 64 consecutive rays of the
  * caller's buffer in one wave, so their speed depends on the order the rays are stored in; these entries sort rays by a
  * 30-bit coherence key on the device and apply the order.  No query kernel and no value changes: an ordered query is
@@ -664,6 +708,18 @@ int rtc_plan_sim_trace_paths(RtcPlanSim *sim, unsigned long long stream, unsigne
 int rtc_plan_sim_occluded(RtcPlanSim *sim, unsigned long long stream, unsigned long long rays, unsigned long long tMax,
                           unsigned long long occluded, unsigned long long count, int flags, int *ops, int maxOps,
                           unsigned long long *footprint, int maxFootprint);
+/* Plans one rtc_render_pixels_async on the caller's stream `stream`, in rtc_plan_sim_trace_paths's encodings: one kernel op
+ * (kernel 17, stream 0, no event) with its footprint records -- it reads the current generation (resource 9) and the list
+ * (resource 20, id = `pixels`) and, with first > 0, the accumulator (resource 6, id = `accum`) and the RNG states
+ * (resource 8, id = `rng`), writes the accumulator and the states and, where asked for (an identity that is not 0), the
+ * Color (resource 5, id = `colors`) and adds to the caller's segment counter (resource 7, an atomic add), in that order --
+ * then one u64 record (~0, 0, the generation read, 0, 0, 0).  The planner's state is left as it was.  RTC_EINVAL where the
+ * entry point refuses, as far as the planner sees it: `pixels`, `accum` or `rng` 0, first < 0, a flag other than
+ * RTC_F_NO_CLUSTER_CULL and RTC_F_WAVE_PER_RAY (which plans the same operation and the same records). */
+int rtc_plan_sim_render_pixels(RtcPlanSim *sim, unsigned long long stream, unsigned long long pixels,
+                               unsigned long long colors, unsigned long long accum, unsigned long long rng,
+                               unsigned long long segments, int first, int flags, int *ops, int maxOps,
+                               unsigned long long *footprint, int maxFootprint);
 /* The last planned launch's scratch, as rows of 3 u64: (slot offset, slot bytes, scratch bytes the launch needs), (scratch
  * bytes allocated once it is enqueued, sample-slot bytes it needs, bit mask of the buffers it binds: rtc_plan.h Buf),
  * then one row per scratch region it binds (region index, byte offset in the scratch, bytes in use).  Returns the

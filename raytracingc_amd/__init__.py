@@ -69,7 +69,7 @@ __all__ = [
     "getEnvironmentLight", "random_sequences", "device_count", "lib", "TRIANGLE_DT", "SPHERE_DT", "RAY_DT",
     "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress", "scene_records_host", "RECORD_ARRAYS",
     "ray_keys_host", "ray_order_scratch_bytes", "gather_async", "scatter_async",
-    "regroup_membership_host", "regroup_max_tris",
+    "regroup_membership_host", "regroup_max_tris", "adaptive_selection",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -748,6 +748,125 @@ class DeviceScene:
             self.progress = ProgressState(host_accum, rng.cpu().numpy().view(np.uint32), done, ProgressState.fields_of(cfg))
             yield done, colors.cpu().numpy(), host_accum
 
+    def render_pixels_async(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, first: int, count: int,
+                            pixels_ptr: int, n: int, accum_ptr: int, rng_ptr: int, colors_ptr: int = 0,
+                            segments_ptr: int | None = None, flags: int = 0, stream: int | None = None):
+        """rtc_render_pixels_async: samples [first, first + count) of cfg.spp for the n pixels listed at
+        pixels_ptr (uint32 compact indices launch_row * W + x, device memory) of a progressive frame, from and into the
+        frame's own buffers -- accum float32 [rows, W, 3], rng uint32 [rows, W], colors uint8 [rows, W, 3] (0: not wanted)
+        -- in place: a listed pixel holds what render_samples_async over the same range leaves there, bit for bit, every
+        other pixel its bytes as they were; an index >= rows * W is skipped.  With first == 0 neither buffer is read.
+        segments_ptr: ONE u64 the launch adds its calculateRayCollision calls to.  flags: 0, RTC_F_NO_CLUSTER_CULL,
+        RTC_F_WAVE_PER_RAY (a wave per listed pixel: few pixels with many samples) or both; of cfg's own flags
+        debug_bounces and overlap are refused and the rest ignored.  Asynchronous on `stream`, complete there; the scene's
+        ordering state and events stay as they were."""
+        d = cfg.desc()
+        rg = RtcSampleRange(int(first), int(count))
+        check(lib().rtc_render_pixels_async(self._h, C.byref(scene), C.byref(cam), C.byref(d), C.byref(rg),
+                                            _vp(pixels_ptr), int(n), int(flags), _vp(colors_ptr), _vp(accum_ptr),
+                                            _vp(rng_ptr), _vp(segments_ptr), _vp(stream)), "rtc_render_pixels_async")
+
+    def render_pixels(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, first: int, count: int, pixels, accum, rng,
+                      colors=None, segments: bool = False, flags: int = 0) -> dict:
+        """A pass over the listed pixels of a progressive frame (render_pixels_async's values): {"accum", "rng"} plus
+        "colors" where given and "segments": int when asked for.  `pixels`: compact indices launch_row * W + x.  Either
+        everything is numpy -- pixels any integer array, accum float32 [rows, W, 3], rng uint32 [rows, W], colors uint8
+        [rows, W, 3] or None -- which takes the synchronous host entry rtc_render_pixels on copies (the caller's arrays are
+        left as they were, the results are new arrays); or everything is a contiguous torch tensor on the scene's device
+        (pixels and rng any 4-byte integer type), updated in place by rtc_render_pixels_async on torch's current stream
+        there: the result holds the same tensors."""
+        who = "DeviceScene.render_pixels"
+        npix = cfg.rows() * cfg.width
+        if hasattr(pixels, "data_ptr"):
+            import torch
+
+            dev = pixels.device
+            n = pixels.numel()
+            sizes = (("pixels", pixels, 4 * n), ("accum", accum, 12 * npix), ("rng", rng, 4 * npix), ("colors", colors, 3 * npix))
+            for name, t, nbytes in sizes:
+                if t is None and name == "colors":
+                    continue
+                if not hasattr(t, "data_ptr") or not t.is_cuda or t.device != dev or not t.is_contiguous() or \
+                        t.numel() * t.element_size() != nbytes:
+                    raise ValueError(f"{who}: {name} must be a contiguous tensor of {nbytes} bytes on the list's device")
+            if pixels.element_size() != 4 or rng.element_size() != 4 or accum.dtype != torch.float32:
+                raise ValueError(f"{who}: pixels and rng are 4-byte integers, accum is float32")
+            seg = torch.zeros(1, dtype=torch.int64, device=dev)
+            if n and npix:
+                with _current_stream_of(dev) as st:
+                    self.render_pixels_async(scene, cam, cfg, first, count, pixels.data_ptr(), n, accum.data_ptr(),
+                                             rng.data_ptr(), colors.data_ptr() if colors is not None else 0,
+                                             seg.data_ptr() if segments else None, flags, st)
+            res = {"accum": accum, "rng": rng}
+            if colors is not None:
+                res["colors"] = colors
+            if segments:
+                res["segments"] = int(seg.cpu().numpy()[0])
+            return res
+        px = np.asarray(pixels).reshape(-1)
+        if px.size and (not np.issubdtype(px.dtype, np.integer) or px.min() < 0 or px.max() > 0xffffffff):
+            raise ValueError(f"{who}: pixels must be integers in [0, 2^32)")
+        px = np.ascontiguousarray(px, np.uint32)
+        acc = np.array(accum, np.float32, order="C")  # (copies: the caller's arrays are left as they were)
+        state = np.array(rng, np.uint32, order="C")
+        col = None if colors is None else np.array(colors, np.uint8, order="C")
+        if acc.size != 3 * npix or state.size != npix or (col is not None and col.size != 3 * npix):
+            raise ValueError(f"{who}: accum float32 [rows, W, 3], rng uint32 [rows, W] and colors uint8 [rows, W, 3] of "
+                             f"the frame's {npix} pixels")
+        seg = C.c_ulonglong(0)
+        if len(px) and npix:
+            d = cfg.desc()
+            rg = RtcSampleRange(int(first), int(count))
+            check(lib().rtc_render_pixels(self._h, C.byref(scene), C.byref(cam), C.byref(d), C.byref(rg), _ptr(px), len(px),
+                                          int(flags), _ptr(col), _ptr(acc), _ptr(state),
+                                          C.cast(C.pointer(seg), C.c_void_p) if segments else None), "rtc_render_pixels")
+        res = {"accum": acc, "rng": state}
+        if col is not None:
+            res["colors"] = col
+        if segments:
+            res["segments"] = int(seg.value)
+        return res
+
+    def render_adaptive(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, select, flags: int = 0):
+        """A generator over the passes of one adaptively sampled frame: `passes` is a list of sample counts summing to at
+        most cfg.spp.  The first is a whole pass (render_samples_async); every further one is a pass over the pixels that
+        `select(done, colors, accum, samples)` returns before it (render_pixels_async with `flags`): compact indices
+        launch_row * W + x, which must be a subset of the previous pass's pixels -- all at samples == done, none twice --
+        or ValueError is raised; an empty selection ends the frame.  It owns the three device buffers (torch tensors on the
+        current device) and after each pass yields (done, colors uint8 [rows, W, 3], accum float32 [rows, W, 3], samples
+        int32 [rows, W]) as host arrays: `samples` is what each pixel has had, `done` the most any has; a pixel's sum and
+        state are the reference's after its own number of samples, weighted 1 / spp each, so a caller normalises with
+        accum * spp / samples.  Stop iterating to cancel."""
+        import torch
+
+        passes = [int(c) for c in passes]
+        if not passes or any(c <= 0 for c in passes) or sum(passes) > cfg.spp:
+            raise ValueError(f"render_adaptive: passes {passes} are not positive counts summing to at most spp = {cfg.spp}")
+        rows = cfg.rows()
+        colors = torch.zeros((rows, cfg.width, 3), dtype=torch.uint8, device="cuda")
+        accum = torch.zeros((rows, cfg.width, 3), dtype=torch.float32, device="cuda")
+        rng = torch.zeros((rows, cfg.width), dtype=torch.int32, device="cuda")
+        samples = np.zeros((rows, cfg.width), np.int32)
+        st = torch.cuda.current_stream().cuda_stream
+        done, host = 0, None
+        for k, count in enumerate(passes):
+            if k == 0:
+                self.render_samples_async(scene, cam, cfg, 0, count, colors.data_ptr(), accum.data_ptr(), rng.data_ptr(),
+                                          None, st)
+                samples += count
+            else:
+                sel = adaptive_selection(select(done, host[0], host[1], samples.copy()), samples, done)
+                if len(sel) == 0:
+                    return
+                pixels = torch.from_numpy(sel.view(np.int32)).cuda()
+                self.render_pixels_async(scene, cam, cfg, done, count, pixels.data_ptr(), len(sel), accum.data_ptr(),
+                                         rng.data_ptr(), colors.data_ptr(), None, flags, st)
+                samples.reshape(-1)[sel] += count
+            done += count
+            torch.cuda.synchronize()
+            host = (colors.cpu().numpy(), accum.cpu().numpy())
+            yield done, host[0], host[1], samples.copy()
+
     @property
     def chain_wgs(self) -> int:
         """rtc_render_chain's workgroups per CU for whole frames, chosen at upload (rtc_scene_chain_wgs)."""
@@ -959,6 +1078,27 @@ class ProgressState:
             raise ValueError("the saved frame's buffers do not have the launch's shape")
         if not 0 < self.samples_done <= cfg.spp:
             raise ValueError(f"the saved frame has {self.samples_done} of {cfg.spp} samples")
+
+
+def adaptive_selection(selection, samples, done: int) -> np.ndarray:
+    """What DeviceScene.render_adaptive accepts from its `select` callback, as uint32 compact indices in the order given:
+    integers below samples.size, none twice, every one a pixel of the previous pass (samples == done there; `samples`:
+    int [rows, W], the samples each pixel has had).  Anything else raises ValueError; an empty selection is fine."""
+    sel = np.asarray(selection).reshape(-1)
+    if sel.size == 0:
+        return np.zeros(0, np.uint32)
+    flat = np.asarray(samples).reshape(-1)
+    if not np.issubdtype(sel.dtype, np.integer):
+        raise ValueError("render_adaptive: the selection must be integer pixel indices")
+    sel = sel.astype(np.int64)
+    if sel.min() < 0 or sel.max() >= flat.size:
+        raise ValueError(f"render_adaptive: the selection names a pixel outside the frame's {flat.size}")
+    if len(np.unique(sel)) != len(sel):
+        raise ValueError("render_adaptive: the selection names a pixel twice")
+    if np.any(flat[sel] != done):
+        raise ValueError(f"render_adaptive: the selection is not a subset of the previous pass's pixels (every pixel that "
+                         f"goes on has had all {done} samples)")
+    return np.ascontiguousarray(sel, np.uint32)
 
 
 def save_progress(path: str, state: ProgressState) -> None:

@@ -120,7 +120,7 @@ RTC_F_OVERLAP = 0x800
 RTC_F_HOST_ROWS = 0x1000
 RTC_F_SPLIT_SPHERES = 0x2000  # sphere launches take the split launch whatever the scene's gate says (A/B, tests)
 RTC_F_NO_DRAW_CACHE = 0x4000  # the launch neither reads nor fills the scene's draw cache (A/B, tests)
-RTC_F_WAVE_PER_RAY = 0x20000  # trace_paths only: one wave per ray, its samples on the lanes (same values bit for bit)
+RTC_F_WAVE_PER_RAY = 0x20000  # trace_paths and render_pixels only: one wave per ray / listed pixel, its samples on the lanes (same values bit for bit)
 # the ray sort's shape (rtc_ray_order_shape): keys per workgroup, and the
 # workgroup counts one scan workgroup takes per step of its loop -- the sizes at which the sort takes another path
 RAY_ORDER_KEYS_PER_GROUP = 4096
@@ -181,6 +181,7 @@ EXPORTS = [
     "rtc_gather_async", "rtc_scatter_async",
     "rtc_scene_regroup_scratch_bytes", "rtc_scene_regroup_max_tris", "rtc_scene_regroup_async", "rtc_scene_regroup",
     "rtc_regroup_membership_host", "rtc_plan_sim_regroup",
+    "rtc_render_pixels_async", "rtc_render_pixels", "rtc_plan_sim_render_pixels",
 ]
 
 _lib = None
@@ -330,6 +331,13 @@ def lib() -> C.CDLL:
         L.rtc_scene_regroup.argtypes = [vp, vp, ip, vp, ip]
         L.rtc_regroup_membership_host.argtypes = [vp, ip, vp]
         L.rtc_plan_sim_regroup.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, vp, ip, vp, ip]
+    if hasattr(L, "rtc_render_pixels_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_render_pixels_async.argtypes = [vp, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
+                                              C.POINTER(RtcSampleRange), vp, sz, ip, vp, vp, vp, vp, vp]
+        L.rtc_render_pixels.argtypes = [vp, C.POINTER(Scene), C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
+                                        C.POINTER(RtcSampleRange), vp, sz, ip, vp, vp, vp, vp]
+        L.rtc_plan_sim_render_pixels.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
+                                                 C.c_ulonglong, C.c_ulonglong, ip, ip, vp, ip, vp, ip]
     _lib = L
     return L
 

@@ -612,6 +612,20 @@ int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_
                            out, max);
 }
 
+int pixels_footprint(const TracePlan &t, uint64_t pixels, uint64_t colors, uint64_t accum, uint64_t rngState, bool segments,
+                     bool readState, Footprint *out, int max)
+{
+    return query_footprint(t,
+                           {{kResPixelList, kRead, pixels, true},
+                            {kResAccum, kRead, accum, readState},
+                            {kResRngState, kRead, rngState, readState},
+                            {kResAccum, kWrite, accum, true},
+                            {kResRngState, kWrite, rngState, true},
+                            {kResColors, kWrite, colors, colors != 0},
+                            {kResCallerSegments, kAtomic, 0, segments}},
+                           out, max);
+}
+
 } // namespace rtcplan
 
 /* ---- the CPU test hook (include/rtc.h rtc_plan_sim_*) ---------------------------------------------------------- */
@@ -853,6 +867,22 @@ extern "C" int rtc_plan_sim_occluded(RtcPlanSim *s, unsigned long long stream, u
     return sim_query(s, rtcplan::kKOccluded, ops, maxOps, fp, maxFp,
                      [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
                          return rtcplan::occluded_footprint(t, rays, tMax, occluded, count != 0, f, max);
+                     });
+}
+
+extern "C" int rtc_plan_sim_render_pixels(RtcPlanSim *s, unsigned long long stream, unsigned long long pixels,
+                                          unsigned long long colors, unsigned long long accum, unsigned long long rng,
+                                          unsigned long long segments, int first, int flags, int *ops, int maxOps,
+                                          unsigned long long *fp, int maxFp)
+{
+    /* refused as rtc_render_pixels_async refuses it, as far as the planner sees it.  RTC_F_WAVE_PER_RAY changes the kernel
+     * alone: the same operation, the same footprint */
+    if (!s || !ops || !pixels || !accum || !rng || first < 0 || (flags & ~(RTC_F_NO_CLUSTER_CULL | RTC_F_WAVE_PER_RAY)))
+        return RTC_EINVAL;
+    (void)stream; /* (the caller's stream is stream 0 of the ops, whichever it is) */
+    return sim_query(s, rtcplan::kKRenderPixels, ops, maxOps, fp, maxFp,
+                     [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                         return rtcplan::pixels_footprint(t, pixels, colors, accum, rng, segments != 0, first > 0, f, max);
                      });
 }
 

@@ -67,9 +67,10 @@ enum Kernel : int { kKPrep, kKSuperCull, kKTileCull, kKSky, kKChain, kKAccum, kK
                     kKTracePaths /* rtc_trace_paths_async's kernel (plan_query); never part of a launch */,
                     kKOccluded /* rtc_occluded_async's kernel (plan_query); never part of a launch */,
                     /* rtc_scene_regroup_async's kernels before its refit (plan_regroup); never part of a launch */
-                    kKRegroupCentroids, kKRegroupLevel, kKRegroupIndex };
+                    kKRegroupCentroids, kKRegroupLevel, kKRegroupIndex,
+                    kKRenderPixels /* rtc_render_pixels_async's kernel (plan_query); never part of a launch */ };
 static_assert(kKRefit == 9 && kKFirstHit == 10 && kKTraceRays == 11 && kKTracePaths == 12 && kKOccluded == 13 &&
-                  kKRegroupCentroids == 14 && kKRegroupLevel == 15 && kKRegroupIndex == 16,
+                  kKRegroupCentroids == 14 && kKRegroupLevel == 15 && kKRegroupIndex == 16 && kKRenderPixels == 17,
               "the kernels' numbers are the test hooks' encoding");
 enum OpKind : int { kOpKernel = 0, kOpRecord = 1, kOpWait = 2 };
 struct Op {
@@ -264,7 +265,8 @@ enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3,
                  kResSeeds = 14 /* id: the caller's seed buffer */, kResRadiance = 15 /* id: the caller's buffer */,
                  kResTMax = 16 /* id: the caller's limit buffer */, kResOccluded = 17 /* id: the caller's byte buffer */,
                  kResMembership = 18 /* the scene's cluster membership (clIndex) */,
-                 kResRegroupScratch = 19 /* id: the caller's regroup scratch */ };
+                 kResRegroupScratch = 19 /* id: the caller's regroup scratch */,
+                 kResPixelList = 20 /* id: the caller's list of pixels (rtc_render_pixels_async) */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -311,7 +313,8 @@ void plan_regroup(const State &s, int levels, RegroupPlan &g);
 int regroup_footprint(const RegroupPlan &g, int kernel, uint64_t scratch, Footprint *out, int max);
 
 /* One query for caller-supplied rays -- rtc_trace_rays_async (kKTraceRays), rtc_trace_paths_async
- * (kKTracePaths, §3.12) or rtc_occluded_async (kKOccluded, §3.13): one kernel on the caller's stream that reads the current
+ * (kKTracePaths, §3.12) or rtc_occluded_async (kKOccluded, §3.13) -- or one pass over a list of a frame's pixels
+ * (rtc_render_pixels_async, kKRenderPixels, §3.17): one kernel on the caller's stream that reads the current
  * generation of the scene records and the caller's buffers and writes the caller's buffers.  It uses no scratch slot,
  * primary record, counter set, stream or event of the scene's, so it waits for nothing and arms nothing: stream order
  * alone places it after the update that wrote its generation and before the one that will rewrite it (an update writes
@@ -346,5 +349,11 @@ int paths_footprint(const TracePlan &t, uint64_t rays, uint64_t seeds, uint64_t 
  * for; resource 7 with id 0, as in a launch's footprint) */
 int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_t occluded, bool count, Footprint *out,
                        int max);
+/* rtc_render_pixels_async, in this order: the generation read, the list read (id: the buffer), the accumulator and the RNG
+ * states read only when the pass continues a frame (readState: first > 0), both written, the Color written (id: the
+ * buffer; 0: not asked for) and the caller's segment counter added to atomically (when asked for; id 0 as in a launch's
+ * footprint).  The accumulator, the states and the Color carry the resources a launch's footprint gives them. */
+int pixels_footprint(const TracePlan &t, uint64_t pixels, uint64_t colors, uint64_t accum, uint64_t rngState, bool segments,
+                     bool readState, Footprint *out, int max);
 
 } // namespace rtcplan

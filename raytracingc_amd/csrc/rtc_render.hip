@@ -103,6 +103,7 @@ extern "C" int rtc_device_count(int *count)
 #include "rtc_trace_rays.h"
 #include "rtc_trace_paths.h"
 #include "rtc_occluded.h"
+#include "rtc_render_pixels.h"
 
 /* A kernel launch whose completion also records `stop` (null: a plain launch): the event is the dispatch's own
  * completion signal, so the stream gets no separate marker packet -- each marker on the launch stream cost ~5-7 us
@@ -670,7 +671,8 @@ extern "C" int rtc_render_first_hit_async(const RtcDeviceScene *s, const RtcCame
 }
 
 /* ---- caller-supplied rays: closest hit, radiance, occlusion -------------------------------------- */
-/* The three queries share everything on the host but their arguments.  A query supplies: its args struct (whose record
+/* The three queries (and the pass over a list of pixels behind them, §3.17, which is a path query whose rays and seeds come
+ * from a frame) share everything on the host but their arguments.  A query supplies: its args struct (whose record
  * part, `rays` and `n` carry these names), its <SPHERES, CULL> kernel table and kernel number, its own refusals, its
  * footprint rows (rtc_plan.h) and, for the host entry, the table of what is staged. */
 
@@ -708,6 +710,14 @@ static void set_mats(Args &a, const DevMat *mats)
     a.mats = mats;
 }
 
+/* (a pixel pass has no ray buffer: its list is among its own fields) */
+static void set_rays(RenderPixelsArgs &a, const Ray *, size_t n) { a.n = (unsigned)n; }
+template <class Args>
+static void set_rays(Args &a, const Ray *dRays, size_t n)
+{
+    a.rays = (const float *)dRays, a.n = (unsigned)n;
+}
+
 /* From a query's args, its own fields filled, to its kernel enqueued on `stream` (n > 0).  The planner names the generation
  * and the one operation (rtc_plan.h plan_query); the ordering state stays as it is (TracePlan::after == s->plan), and so do
  * the hooks, the timing events, the chain report and the draw cache.  `raysPerGroup`: how many rays a workgroup of the
@@ -727,7 +737,7 @@ static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, v
     set_mats(a, g.mats);
     a.triPadded = s->triPadded, a.sphereCount = trianglesOnly ? 0 : s->sphereCount;
     a.clusterCount = s->clusterCount, a.chunkCount = s->chunkCount;
-    a.rays = (const float *)dRays, a.n = (unsigned)n;
+    set_rays(a, dRays, n);
     for (int i = 0; i < tp.nOps; ++i) {
         const rtcplan::Op &op = tp.ops[i];
         if (op.kind != rtcplan::kOpKernel || op.kernel != kernel || op.stream != rtcplan::kStCaller)
@@ -899,6 +909,95 @@ extern "C" int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const floa
     });
 }
 
+/* ---- a pass over a list of pixels of a progressive frame */
+static int check_render_pixels(const char *who, const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                               const RtcRenderDesc *d, const RtcSampleRange *range, const void *pixels, size_t n, int flags,
+                               const void *accum, const void *rngState)
+{
+    return refuse_query(who, "a pixel", s, !scene || !cam || !d || !range || !pixels || !accum || !rngState, nullptr, n,
+                        flags, RTC_F_NO_CLUSTER_CULL | RTC_F_WAVE_PER_RAY, "RTC_F_NO_CLUSTER_CULL, RTC_F_WAVE_PER_RAY", [&] {
+        const int geometry = rtcplan::geometry_error(*d); /* (as check_arguments reports it) */
+        if (geometry == 1)
+            return rtc_fail(RTC_EINVAL, "%s: bad geometry %dx%d rows %d+k*%d", who, d->width, d->height, d->rowStart,
+                            d->rowStride);
+        if (geometry)
+            return rtc_fail(RTC_EINVAL, "%s: frame too large", who);
+        if (d->spp <= 0)
+            return rtc_fail(RTC_EINVAL, "%s: spp %d", who, d->spp);
+        if (range->first < 0 || range->count <= 0 || range->first > d->spp - range->count)
+            return rtc_fail(RTC_EINVAL, "%s: samples [%d, %d + %d) are not within the frame's %d", who, range->first,
+                            range->first, range->count, d->spp);
+        /* of the frame's own flags: every other bit only chooses a route of the frame's launches and is ignored, so that a
+         * caller passes the desc of its whole passes */
+        if (d->flags & (RTC_F_DEBUG_BOUNCES | RTC_F_OVERLAP))
+            return rtc_fail(RTC_EINVAL, "%s: desc flags 0x%x (RTC_F_DEBUG_BOUNCES: calcDebugColor is not offered for pixel "
+                                        "lists; RTC_F_OVERLAP: a pass is never overlapped)", who, d->flags);
+        if (d->flags & (RTC_F_COOP4 | RTC_F_COOP8 | RTC_F_PIPE | RTC_F_SPEC))
+            return rtc_fail(RTC_EINVAL, "%s: desc flags RTC_F_COOP4 / COOP8 / PIPE / SPEC name kernels that were removed", who);
+        return 0;
+    });
+}
+
+extern "C" int rtc_render_pixels_async(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam,
+                                       const RtcRenderDesc *d, const RtcSampleRange *range, const unsigned int *dPixels,
+                                       size_t n, int flags, void *dColors, float *dAccum, unsigned int *dRngState,
+                                       unsigned long long *dSegments, void *stream)
+{
+    const char *const who = "rtc_render_pixels_async";
+    if (const int rc = check_render_pixels(who, s, scene, cam, d, range, dPixels, n, flags, dAccum, dRngState))
+        return rc;
+    const int rows = rtc_rows_selected(d);
+    if (n == 0 || rows == 0)
+        return 0;
+    RenderPixelsArgs a{};
+    a.env = env_of(*scene);
+    a.invSpp = (float)(1. / (double)d->spp); /* main.c:99 */
+    a.sampleFirst = range->first, a.sampleCount = range->count, a.maxBounce = d->maxBounce;
+    a.view.width = d->width, a.view.height = d->height, a.view.rows = rows;
+    a.view.rowStart = d->rowStart, a.view.rowStride = d->rowStride;
+    a.view.rowBandShift = d->rowBand > 1 ? __builtin_ctz((unsigned)d->rowBand) : 0;
+    a.view.ex = v3(cam->ex), a.view.ey = v3(cam->ey), a.view.ez = v3(cam->ez), a.view.fov = cam->fov;
+    a.origin = v3(cam->origin);
+    a.pixelCount = (unsigned)((size_t)rows * (size_t)d->width); /* (geometry_error: at most 2^29) */
+    a.pixels = dPixels;
+    a.colors = (unsigned char *)dColors, a.accum = dAccum, a.rngState = dRngState, a.segments = dSegments;
+    /* <SPHERES, CULL> */
+    static void (*const kRenderPixels[2][2])(RenderPixelsArgs) = {
+        {rtc_render_pixels<false, false>, rtc_render_pixels<false, true>},
+        {rtc_render_pixels<true, false>, rtc_render_pixels<true, true>}};
+    /* RTC_F_WAVE_PER_RAY: a wave per listed pixel; the same operation, buffers and ordering */
+    static void (*const kRenderPixelsWave[2][2])(RenderPixelsArgs) = {
+        {rtc_render_pixels_wave<false, false>, rtc_render_pixels_wave<false, true>},
+        {rtc_render_pixels_wave<true, false>, rtc_render_pixels_wave<true, true>}};
+    if (flags & RTC_F_WAVE_PER_RAY)
+        return enqueue_query(who, s, rtcplan::kKRenderPixels, kRenderPixelsWave, a, nullptr, n, d->trianglesOnly, flags,
+                             stream, kBlock / 64);
+    return enqueue_query(who, s, rtcplan::kKRenderPixels, kRenderPixels, a, nullptr, n, d->trianglesOnly, flags, stream);
+}
+
+extern "C" int rtc_render_pixels(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
+                                 const RtcSampleRange *range, const unsigned int *pixels, size_t n, int flags, void *colors,
+                                 float *accum, unsigned int *rngState, unsigned long long *segments)
+{
+    const char *const who = "rtc_render_pixels";
+    if (const int rc = check_render_pixels(who, s, scene, cam, d, range, pixels, n, flags, accum, rngState))
+        return rc;
+    const size_t px = (size_t)rtc_rows_selected(d) * (size_t)d->width;
+    if (n == 0 || px == 0)
+        return 0;
+    /* the list, the frame's three whole buffers and the counter's value.  The buffers go in as well as out, whatever the
+     * range: the pixels that are not listed come back as they were */
+    const Staged items[5] = {{pixels, nullptr, n * sizeof(unsigned), true},
+                             {colors, colors, px * 3, colors != nullptr},
+                             {accum, accum, px * 3 * sizeof(float), true},
+                             {rngState, rngState, px * sizeof(unsigned), true},
+                             {segments, segments, sizeof(unsigned long long), segments != nullptr}};
+    return staged_query(who, s, items, [&](void *const *dev) {
+        return rtc_render_pixels_async(s, scene, cam, d, range, (const unsigned *)dev[0], n, flags, dev[1], (float *)dev[2],
+                                       (unsigned *)dev[3], (unsigned long long *)dev[4], nullptr);
+    });
+}
+
 int rtc_cull_items(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,
                    void *dColors, RtcCullItems *items)
 {
@@ -1066,3 +1165,12 @@ template __global__ void rtc_trace_paths_wave<false, true>(TracePathsArgs);
 template __global__ void rtc_trace_paths_wave<true, true>(TracePathsArgs);
 template __global__ void rtc_trace_paths_wave<false, false>(TracePathsArgs);
 template __global__ void rtc_trace_paths_wave<true, false>(TracePathsArgs);
+/* a pass over a list of pixels: a lane per pixel, a wave per pixel */
+template __global__ void rtc_render_pixels<false, true>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels<true, true>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels<false, false>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels<true, false>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels_wave<false, true>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels_wave<true, true>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels_wave<false, false>(RenderPixelsArgs);
+template __global__ void rtc_render_pixels_wave<true, false>(RenderPixelsArgs);
