@@ -750,6 +750,19 @@ static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, v
     return 0;
 }
 
+/* A path query -- rtc_trace_paths_async, rtc_render_pixels_async -- has two kernel families, by [RTC_F_WAVE_PER_RAY]: a
+ * lane per ray, and a wave per ray (rtc_trace_paths.h): the same operation, buffers and ordering,
+ * kBlock / 64 rays to a workgroup. */
+#define PATH_TABLE(k) {{k<false, false>, k<false, true>}, {k<true, false>, k<true, true>}} /* <SPHERES, CULL> */
+template <class Args>
+static int enqueue_path_query(const char *who, const RtcDeviceScene *s, int kernel, void (*const (&table)[2][2][2])(Args),
+                              Args &a, const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream)
+{
+    const bool wave = (flags & RTC_F_WAVE_PER_RAY) != 0;
+    return enqueue_query(who, s, kernel, table[wave], a, dRays, n, trianglesOnly, flags, stream,
+                         wave ? kBlock / 64 : kBlock);
+}
+
 /* ---- closest hit */
 static int check_trace_rays(const char *who, const RtcDeviceScene *s, const void *rays, size_t n, int flags,
                             const void *const out[4], bool haveOut)
@@ -828,18 +841,10 @@ extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene
     a.invSpp = (float)(1. / d->spp); /* main.c:99 */
     a.sampleFirst = d->sampleFirst, a.sampleCount = d->sampleCount, a.maxBounce = d->maxBounce;
     a.seeds = dSeeds, a.radiance = dRadiance, a.seedsOut = dSeedsOut, a.segments = dSegments;
-    /* <SPHERES, CULL> */
-    static void (*const kTracePaths[2][2])(TracePathsArgs) = {
-        {rtc_trace_paths<false, false>, rtc_trace_paths<false, true>},
-        {rtc_trace_paths<true, false>, rtc_trace_paths<true, true>}};
-    /* RTC_F_WAVE_PER_RAY: the same operation, outputs and ordering; a wave per ray (rtc_trace_paths.h) */
-    static void (*const kTracePathsWave[2][2])(TracePathsArgs) = {
-        {rtc_trace_paths_wave<false, false>, rtc_trace_paths_wave<false, true>},
-        {rtc_trace_paths_wave<true, false>, rtc_trace_paths_wave<true, true>}};
-    if (d->flags & RTC_F_WAVE_PER_RAY)
-        return enqueue_query(who, s, rtcplan::kKTracePaths, kTracePathsWave, a, dRays, n, d->trianglesOnly, d->flags,
-                             stream, kBlock / 64);
-    return enqueue_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags, stream);
+    static void (*const kTracePaths[2][2][2])(TracePathsArgs) = {PATH_TABLE(rtc_trace_paths),
+                                                                 PATH_TABLE(rtc_trace_paths_wave)};
+    return enqueue_path_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags,
+                              stream);
 }
 
 extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds,
@@ -961,18 +966,10 @@ extern "C" int rtc_render_pixels_async(const RtcDeviceScene *s, const Scene *sce
     a.pixelCount = (unsigned)((size_t)rows * (size_t)d->width); /* (geometry_error: at most 2^29) */
     a.pixels = dPixels;
     a.colors = (unsigned char *)dColors, a.accum = dAccum, a.rngState = dRngState, a.segments = dSegments;
-    /* <SPHERES, CULL> */
-    static void (*const kRenderPixels[2][2])(RenderPixelsArgs) = {
-        {rtc_render_pixels<false, false>, rtc_render_pixels<false, true>},
-        {rtc_render_pixels<true, false>, rtc_render_pixels<true, true>}};
-    /* RTC_F_WAVE_PER_RAY: a wave per listed pixel; the same operation, buffers and ordering */
-    static void (*const kRenderPixelsWave[2][2])(RenderPixelsArgs) = {
-        {rtc_render_pixels_wave<false, false>, rtc_render_pixels_wave<false, true>},
-        {rtc_render_pixels_wave<true, false>, rtc_render_pixels_wave<true, true>}};
-    if (flags & RTC_F_WAVE_PER_RAY)
-        return enqueue_query(who, s, rtcplan::kKRenderPixels, kRenderPixelsWave, a, nullptr, n, d->trianglesOnly, flags,
-                             stream, kBlock / 64);
-    return enqueue_query(who, s, rtcplan::kKRenderPixels, kRenderPixels, a, nullptr, n, d->trianglesOnly, flags, stream);
+    static void (*const kRenderPixels[2][2][2])(RenderPixelsArgs) = {PATH_TABLE(rtc_render_pixels),
+                                                                     PATH_TABLE(rtc_render_pixels_wave)};
+    return enqueue_path_query(who, s, rtcplan::kKRenderPixels, kRenderPixels, a, nullptr, n, d->trianglesOnly, flags,
+                              stream);
 }
 
 extern "C" int rtc_render_pixels(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,

@@ -2,12 +2,12 @@
  * DESIGN §3.17): main.c:88-100 for the listed pixels alone -- per pixel, the camera ray of main.c:88-94, the state of
  * main.c:95 or the frame's stored one, sampleCount times acc = acc + calcColor(ray, trianglesOnly, maxBounce, scene) *
  * (float)(1. / spp), and the pixel's 16 bytes of state and 3 bytes of Color stored where a whole pass keeps them.
- * A section of rtc_render.hip's translation unit: included there once, after rtc_trace_paths.h (it uses trace_closest and
- * the names of the headers above it in that file's list, and rtcdev's through the file's using-directive).
+ * A section of rtc_render.hip's translation unit: included there once, after rtc_trace_paths.h (it uses rtc_trace_rays.h's
+ * trace_closest and the names of the headers above it in that file's list, and rtcdev's through the file's
+ * using-directive).
  * The two kernels are rtc_trace_paths and rtc_trace_paths_wave with another head (the pixel index, the derived ray and
- * seed, the state load) and another tail (the state store, the three Color bytes).  Their hit and miss statements are
- * rtc_trace_paths.h's own, repeated: sharing them would have to leave that file's kernels instruction-identical
- * (tools/kernel_diff.py), and a copy cannot fail to. */
+ * seed, the state load) and another tail (the state store, the three Color bytes).  Between the two their statements are
+ * rtc_trace_paths.h's own, again: the shared bodies that were built measured slower (that file's comment). */
 #pragma once
 
 /* The kernel's own arguments: the record part of TracePathsArgs (the bound generation's records and their counts), the
@@ -34,17 +34,6 @@ struct RenderPixelsArgs {
     unsigned *rngState;                      /* pixelCount; read when sampleFirst > 0, written */
     unsigned long long *segments;            /* one u64, nullable: += calculateRayCollision calls */
 };
-
-/* what trace_closest reads of its arguments: the records and their counts */
-__device__ __forceinline__ TracePathsArgs pixel_records(const RenderPixelsArgs &A)
-{
-    TracePathsArgs T{};
-    T.tris = A.tris, T.mats = A.mats, T.spheres = A.spheres;
-    T.clTris = A.clTris, T.clusters = A.clusters, T.chunks = A.chunks;
-    T.triPadded = A.triPadded, T.sphereCount = A.sphereCount;
-    T.clusterCount = A.clusterCount, T.chunkCount = A.chunkCount;
-    return T;
-}
 
 /* A listed pixel's camera ray direction and seed (main.c:88-95): x = p % width, launch row r = p / width, image row
  * y = launch_row_y(r) */
@@ -85,7 +74,6 @@ __global__ __launch_bounds__(kBlock) void rtc_render_pixels(RenderPixelsArgs A)
     sPow.fill(threadIdx.x);
     __syncthreads();
     sPow.attach(A.env);
-    const TracePathsArgs T = pixel_records(A);
 
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     unsigned p = 0;
@@ -112,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void rtc_render_pixels(RenderPixelsArgs A)
     unsigned long long segCalls = 0;
 
     while (__any(alive)) {
-        const Closest c = trace_closest<SPHERES, CULL>(T, pos, dir, alive);
+        const Closest c = trace_closest<SPHERES, CULL>(A, pos, dir, alive);
         if (alive) {
             segCalls++;
             bool endSample;
@@ -196,7 +184,6 @@ __global__ __launch_bounds__(kBlock) void rtc_render_pixels_wave(RenderPixelsArg
     sPow.fill(threadIdx.x);
     __syncthreads();
     sPow.attach(A.env);
-    const TracePathsArgs T = pixel_records(A);
 
     const size_t i = (size_t)blockIdx.x * (kBlock / 64) + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= (size_t)A.n)
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void rtc_render_pixels_wave(RenderPixelsArg
     /* every sample's first segment is the camera ray: traced once, counted per sample */
     Closest first{999999.f, -1};
     if (left > 0)
-        first = trace_closest<SPHERES, CULL>(T, pos0, dir0, true);
+        first = trace_closest<SPHERES, CULL>(A, pos0, dir0, true);
     const RngJump laneJump = rng_jump_by(7u * lane); /* s -> the state 7 lane draws later */
 
     while (left > 0) {
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(kBlock) void rtc_render_pixels_wave(RenderPixelsArg
             }
             if (!__any(alive))
                 break;
-            c = trace_closest<SPHERES, CULL>(T, pos, dir, alive);
+            c = trace_closest<SPHERES, CULL>(A, pos, dir, alive);
         }
 
         /* the walk, in the reference's order */

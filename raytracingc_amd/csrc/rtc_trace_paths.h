@@ -2,8 +2,9 @@
  * (rtc_trace_paths_async): main.c:95-100 with the ray given instead of derived from a pixel -- per ray,
  * sampleCount times acc = acc + calcColor(ray, trianglesOnly, maxBounce, scene) * (float)(1. / spp) (raytracing.c:262-296)
  * on one RNG chain that starts at the caller's seed.
- * A section of rtc_render.hip's translation unit: included there once, after rtc_trace_rays.h (it uses the names of the
- * headers above it in that file's list, and rtcdev's through the file's using-directive). */
+ * A section of rtc_render.hip's translation unit: included there once, after rtc_trace_rays.h (it uses that file's
+ * trace_closest, the names of the headers above it in that file's list, and rtcdev's through the file's
+ * using-directive). */
 #pragma once
 
 /* The kernel's own arguments: the record part of TraceRaysArgs (the bound generation's records and their counts), the
@@ -26,61 +27,6 @@ struct TracePathsArgs {
     unsigned *seedsOut;                      /* n; nullable */
     unsigned long long *segments;            /* one u64, nullable: += calculateRayCollision calls */
 };
-
-/* The closest hit of one ray per lane (calculateRayCollision, raytracing.c:216-240), wave-wide: rtc_trace_rays' walk
- * (rtc_trace_rays.h has the description and the argument for its exactness) as a function, statement for statement, with
- * the participating lanes as an argument.  `live` is this lane's bit of that mask: a lane that is not live runs through the
- * wave-uniform loops with whatever ray it holds, keeps no ball in the ballots and gets a result its caller discards.
- * Call it from wave-uniform control flow.
- * rtc_trace_rays keeps its own copy of these statements: calling this function from it (tried returning the Closest, filling
- * a reference, and with the arguments by value) changed the register allocation and block order of its four kernels, and
- * the kernels of earlier rounds stay instruction-identical (tools/kernel_diff.py). */
-template <bool SPHERES, bool CULL>
-__device__ __forceinline__ Closest trace_closest(const TracePathsArgs &A, V3 pos, V3 dir, bool live)
-{
-    Closest c{999999.f, -1}; /* HitInfo closest = {0, 999999} */
-    if (SPHERES) {
-        for (int k = 0; k < A.sphereCount; ++k) {
-            const DevSphere sp = A.spheres[k];
-            float d;
-            if (ray_sphere(pos, dir, V3{sp.cx, sp.cy, sp.cz}, sp.radius, d) && d < c.dst) {
-                c.dst = d;
-                c.idx = k;
-            }
-        }
-    }
-    const int base = SPHERES ? A.sphereCount : 0;
-    if (!CULL) {
-        RenderParams P{}; /* (closest_general reads the records and their padded count, nothing else) */
-        P.tris = A.tris;
-        P.triPadded = A.triPadded;
-        closest_general(P, pos, dir, c, base);
-    } else {
-        const float rho = fabsf(dir.x) + fabsf(dir.y) + fabsf(dir.z), dd = dir_dd(dir);
-        const bool cull = live && rho <= kClusterRhoMax; /* this lane may cull: it has a ray, within the bound's premise */
-        for (int h = 0; h < A.chunkCount; ++h) {
-            const int c0 = h * kChunkClusters, nCl = min(kChunkClusters, A.clusterCount - c0);
-            if (A.chunkCount > 1) {
-                const DevCluster H = KLOAD(A.chunks, h);
-                if (!__ballot(live && !(cull && cluster_culled(pos, dir, rho, dd, H))))
-                    continue;
-            }
-            for (int k = 0; k < nCl; ++k) {
-                const DevCluster K = KLOAD(A.clusters, c0 + k);
-                if (!__ballot(live && !(cull && cluster_culled(pos, dir, rho, dd, K))))
-                    continue;
-                const DevTri *rec = A.clTris + (size_t)(c0 + k) * kClusterSize;
-#pragma unroll 4
-                for (int j = 0; j < kClusterSize; ++j) {
-                    const DevTri R = KLOAD(rec, j);
-                    if (general_filter(pos, dir, R))
-                        general_exact(pos, dir, R, base + __float_as_int(R.pad0), c);
-                }
-            }
-        }
-    }
-    return c;
-}
 
 /* One lane per ray, a wave 64 consecutive rays; lanes past n load and store nothing, are never alive and stay in the
  * wave-wide operations.  rtc_lane.h's state machine without the camera, the tile masks, hoisting and DEBUG: while any
@@ -207,8 +153,10 @@ __global__ __launch_bounds__(kBlock) void rtc_trace_paths(TracePathsArgs A)
  * rays), so a walked lane holds what the sequential chain computes there.
  * Every wave-uniform value (S, acc, left, calls, k) is computed by all lanes alike; lane 0 stores.  A wave past n takes part
  * in the table fill and its barrier and leaves.
- * The hit and miss statements are rtc_trace_paths' own, repeated: sharing them through a function would have to leave that
- * kernel instruction-identical (tools/kernel_diff.py), and a copy cannot fail to. */
+ * The hit and miss statements are rtc_trace_paths' own, and rtc_render_pixels.h has both kernels' bodies again: one
+ * calcColor step and one body per kind, called from all four, were built and measured -- the same
+ * instructions in another register allocation, 0.5 to 1.3 % slower on three of this file's legs in both alternations, one
+ * VGPR more in one pixel kernel -- so a change to the bounce step or the window loop is made in each of them. */
 template <bool SPHERES, bool CULL>
 __global__ __launch_bounds__(kBlock) void rtc_trace_paths_wave(TracePathsArgs A)
 {

@@ -1,6 +1,7 @@
 /* rtc_trace_rays.h -- rtc_trace_rays: the closest hit of caller-supplied rays against the resident scene
  * (rtc_trace_rays_async): calculateRayCollision(ray, trianglesOnly) (raytracing.c:216-240) for n arbitrary
- * Rays, into rtc_first_hit's four buffers.
+ * Rays, into rtc_first_hit's four buffers -- and trace_closest, the closest-hit walk of every query kernel that follows
+ * (rtc_trace_paths.h, rtc_render_pixels.h).
  * A section of rtc_render.hip's translation unit: included there once, after the headers above it in that file's
  * list (it uses their names, and rtcdev's through the file's using-directive). */
 #pragma once
@@ -23,8 +24,10 @@ struct TraceRaysArgs {
     float *__restrict__ albedo;
 };
 
-/* One lane per ray, a wave 64 consecutive rays; lanes past n load and store nothing but stay in the wave-wide operations
- * (their ray is pos = dir = 0: whatever it is tested against is discarded).
+/* The closest hit of one ray per lane (calculateRayCollision(ray, trianglesOnly), raytracing.c:216-240), wave-wide, for
+ * every query kernel of this unit: `A` is any argument struct with TraceRaysArgs' record fields.  `live` is this lane's bit
+ * of the participating lanes: a lane that is not live runs through the wave-uniform loops with whatever ray it holds, keeps
+ * no ball in the ballots and gets a result its caller discards.  Call it from wave-uniform control flow.
  * Spheres first, per lane, in index order with strict `<`, as closest_hit does (A.sphereCount: 0 with trianglesOnly).
  * !CULL: closest_general over the records in reference order -- general_test, strict `<`, ascending index.
  * CULL: the cluster hierarchy, with wave-uniform loops over the chunks (scenes of more than one) and a chunk's clusters.
@@ -35,22 +38,10 @@ struct TraceRaysArgs {
  * not visited in index order, so equal distances keep the lowest reference index (general_exact's rule; a sphere's index
  * is below every triangle's): the result does not depend on the order, nor on the other lanes' rays.
  * The direction is used as given (not normalised: the reference does not).
- * Loads and stores: plain per-lane accesses.  A lane's six ray dwords lie at a 24-B stride (the compiler merges them into
- * one dwordx4 and one dwordx2 load; the wave's 1,536 B are 12 adjacent lines, read once from L2 and again from the vector
- * L1), and store_hit's stores are rtc_first_hit's (a dword each for prim and depth, a dwordx3 at a 12-B stride for normal
- * and albedo).  No staging through LDS: at ~120 record tests per ray the 56 B a ray moves are not what the kernel waits
- * for (DESIGN §3.11 has the measurement). */
-template <bool SPHERES, bool CULL>
-__global__ __launch_bounds__(kBlock) void rtc_trace_rays(TraceRaysArgs A)
+ * (rtc_occluded's walk is another one: any hit within a distance limit.) */
+template <bool SPHERES, bool CULL, class Args>
+__device__ __forceinline__ Closest trace_closest(const Args &A, V3 pos, V3 dir, bool live)
 {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool live = i < (size_t)A.n;
-    V3 pos{0.f, 0.f, 0.f}, dir{0.f, 0.f, 0.f};
-    if (live) {
-        const float *r = A.rays + 6 * i;
-        pos = V3{r[0], r[1], r[2]};
-        dir = V3{r[3], r[4], r[5]};
-    }
     Closest c{999999.f, -1}; /* HitInfo closest = {0, 999999} */
     if (SPHERES) {
         for (int k = 0; k < A.sphereCount; ++k) {
@@ -92,6 +83,28 @@ __global__ __launch_bounds__(kBlock) void rtc_trace_rays(TraceRaysArgs A)
             }
         }
     }
+    return c;
+}
+
+/* One lane per ray, a wave 64 consecutive rays; lanes past n load and store nothing but stay in trace_closest's wave-wide
+ * operations (their ray is pos = dir = 0: whatever it is tested against is discarded).
+ * Loads and stores: plain per-lane accesses.  A lane's six ray dwords lie at a 24-B stride (the compiler merges them into
+ * one dwordx4 and one dwordx2 load; the wave's 1,536 B are 12 adjacent lines, read once from L2 and again from the vector
+ * L1), and store_hit's stores are rtc_first_hit's (a dword each for prim and depth, a dwordx3 at a 12-B stride for normal
+ * and albedo).  No staging through LDS: at ~120 record tests per ray the 56 B a ray moves are not what the kernel waits
+ * for (DESIGN §3.11 has the measurement). */
+template <bool SPHERES, bool CULL>
+__global__ __launch_bounds__(kBlock) void rtc_trace_rays(TraceRaysArgs A)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < (size_t)A.n;
+    V3 pos{0.f, 0.f, 0.f}, dir{0.f, 0.f, 0.f};
+    if (live) {
+        const float *r = A.rays + 6 * i;
+        pos = V3{r[0], r[1], r[2]};
+        dir = V3{r[3], r[4], r[5]};
+    }
+    const Closest c = trace_closest<SPHERES, CULL>(A, pos, dir, live);
     if (live)
         store_hit<SPHERES>(A, pos, dir, c.idx, c.dst, i, A.prim, A.depth, A.normal, A.albedo);
 }
