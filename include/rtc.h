@@ -310,6 +310,31 @@ typedef struct RtcChainReport {
     int chainPrimF, wgsPerCu, chainDyn, clusterCount, chunkCount, launches;
 } RtcChainReport;
 int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *out);
+/* What the scene's most recent enqueue planned -- a launch, a pass, a first-hit launch, an update, a regroup, one of the
+ * queries for caller-supplied rays or a pass over a list of pixels -- recorded on the host, from the plan the call
+ * executed, when its last operation was enqueued (a call that is refused or fails leaves the record as it was); read-only,
+ * no device work, no reference counterpart.  The encoding is the planner hooks' (rtc_plan_sim_launch, _update, _regroup,
+ * _trace_rays, _trace_paths, _occluded, _render_pixels, below): 4 ints per operation into ops, 6 u64 per footprint row into
+ * footprint, the hook's trailing ~0 record last, and the return value nOps | rows << 8 -- the caller's buffers carry their
+ * device addresses as identities.  0 before anything was enqueued; RTC_EINVAL for a null argument or when maxOps or
+ * maxFootprint is less than the plan has (48 operations and 256 rows always suffice).  tests/test_gpu_footprints.py holds
+ * every byte a call changes in the scene's memory to the write rows of this record. */
+int rtc_scene_last_plan(const RtcDeviceScene *s, int *ops, int maxOps, unsigned long long *footprint, int maxFootprint);
+/* Every device allocation the scene owns, as spans: res and id in the footprint rows' numbering, part where one (res, id)
+ * is several arrays, base the device address, bytes the size (0 with base 0: not allocated yet).  In this order: the
+ * scratch (res 0: all slots, footprint rows give byte ranges inside it); each slot's primary records (res 1, id the slot,
+ * parts 0 and 1: the filter and the exact records); each counter set (res 2, id the set); the deferred sample slots (res
+ * 3); the segment-counter slots (res 4); each array of each generation of the scene records (res 9, id the generation,
+ * part the array: tris, mats, spheres, clTris, clusters, chunks); the draw cache's slot table, counter words and block
+ * seeds (res 12, parts 0-2); each slot's item-draw array (res 13, id the slot); the cluster membership (res 18); the draw
+ * cache's pool of 1-KB blocks (res 21, which no footprint row names: a block is written once, by the launch whose tile cull
+ * took it -- the first counter word, part 1 of res 12, is the number of blocks taken).  Returns the number of spans (60);
+ * RTC_EINVAL for a null argument or max less than that.  Read-only host state: no device work; a launch that regrows or
+ * first allocates a buffer changes its span. */
+typedef struct RtcSpan {
+    unsigned long long res, id, part, base, bytes;
+} RtcSpan;
+int rtc_scene_spans(const RtcDeviceScene *s, RtcSpan *out, int max);
 /* The draw cache (no reference counterpart; it never changes a frame).  A sample's m-th hit draws RandomDiretion's six
  * values and the roulette's one from the pixel's seed x + y * width (main.c:95) advanced by 7 (j + m) draws: a function of
  * the frame's width and the pixel alone, whatever the camera, scene, materials or environment.  The scene keeps, per pixel

@@ -884,6 +884,26 @@ class DeviceScene:
                    cluster_count=r.clusterCount, chunk_count=r.chunkCount, launches=r.launches)
         return out
 
+    def last_plan(self):
+        """What the scene's most recent enqueue planned (rtc_scene_last_plan; host state, no device work), in the planner
+        hooks' encoding: (ops int32 [n, 4]: kind, stream, event, kernel; rows uint64 [m, 6]: op index, res, access, id, lo,
+        hi, the trailing ~0 record last).  Before anything was enqueued both are empty."""
+        ops = np.zeros((48, 4), np.int32)
+        fp = np.zeros((256, 6), np.uint64)
+        rc = lib().rtc_scene_last_plan(self._h, _ptr(ops), 48, _ptr(fp), 256)
+        if rc < 0:
+            raise RtcError(rc, "rtc_scene_last_plan")
+        return ops[: rc & 0xff].copy(), fp[: rc >> 8].copy()
+
+    def spans(self):
+        """Every device allocation the scene owns (rtc_scene_spans; host state, no device work): uint64 [n, 5] rows of
+        res, id, part, base, bytes -- res and id in the footprint rows' numbering, bytes 0 where nothing is allocated yet."""
+        out = np.zeros((64, 5), np.uint64)
+        rc = lib().rtc_scene_spans(self._h, _ptr(out), 64)
+        if rc < 0:
+            raise RtcError(rc, "rtc_scene_spans")
+        return out[:rc].copy()
+
     def set_draw_cache(self, blocks: int = -1):
         """The draw cache's capacity in 1-KB blocks, one per cached pixel (rtc_scene_set_draw_cache): 0 disables it, a
         negative value restores the default.  Synchronises the device and drops what is cached."""

@@ -82,6 +82,10 @@ class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geom
                                        "chainDyn", "clusterCount", "chunkCount", "launches")]
 
 
+class RtcSpan(C.Structure):  # rtc_scene_spans: one device allocation of a scene (include/rtc.h)
+    _fields_ = [(k, C.c_ulonglong) for k in ("res", "id", "part", "base", "bytes")]
+
+
 class RtcStats(C.Structure):
     _fields_ = [
         ("renderMs", C.c_double),
@@ -170,7 +174,7 @@ EXPORTS = [
     "rtc_probe_primary_cull",
     "rtc_scene_update_async", "rtc_scene_update", "rtc_plan_sim_update", "rtc_plan_sim_set_update_fault",
     "rtc_scene_records_host", "rtc_probe_scene_records",
-    "rtc_scene_chain_report",
+    "rtc_scene_chain_report", "rtc_scene_last_plan", "rtc_scene_spans",
     "rtc_render_first_hit_async", "rtc_plan_sim_set_first_hit",
     "rtc_trace_rays_async", "rtc_trace_rays", "rtc_plan_sim_trace_rays",
     "rtc_scene_set_draw_cache", "rtc_scene_draw_cache_reset", "rtc_scene_draw_cache_stats", "rtc_probe_draw_cache",
@@ -289,6 +293,9 @@ def lib() -> C.CDLL:
         L.rtc_probe_scene_records.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "rtc_scene_chain_report"):  # (absent from libraries of earlier rounds loaded for A/B timing)
         L.rtc_scene_chain_report.argtypes = [vp, C.POINTER(RtcChainReport)]
+    if hasattr(L, "rtc_scene_last_plan"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_scene_last_plan.argtypes = [vp, vp, ip, vp, ip]
+        L.rtc_scene_spans.argtypes = [vp, vp, ip]
     if hasattr(L, "rtc_render_first_hit_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
         L.rtc_render_first_hit_async.argtypes = [vp, C.POINTER(RtcCamera), C.POINTER(RtcRenderDesc),
                                                  C.POINTER(RtcHitBuffers), vp]

@@ -357,6 +357,9 @@ struct RtcDeviceScene {
     bool timing; /* record them (rtc_scene_set_timing; off by default: each record costs the launch a few us) */
     bool timed;  /* the last launch was a split launch that recorded them */
     RtcChainReport chainReport; /* what the last geometry-kernel launch chose (run_chain; rtc_scene_chain_report) */
+    /* what the last enqueue planned -- a launch, a pass, a first-hit launch, an update, a regroup, a query, a pixel pass --
+     * recorded once every operation of its plan is enqueued (host stores only; rtc_scene_last_plan) */
+    rtcplan::Recorded lastPlan;
     /* The draw cache (rtc_params.h DrawCache), allocated at the first launch that uses it and freed with the
      * scene.  The pool's blocks are append-only -- written once by the fill behind the cull that allocated them, before
      * any geometry kernel that can name them; never touched again -- which is why launches in flight may read them while

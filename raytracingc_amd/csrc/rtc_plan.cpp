@@ -674,18 +674,89 @@ int serialise(const rtcplan::Op *o, int nOps, int *ops, int maxOps, unsigned lon
     return nOps | ((nf + 1) << 8);
 }
 
-/* a query, once its hook has refused what its entry point refuses: planned, the state adopted, and handed back with the
- * trailer (~0, nothing regrown, the generation read, -, -, -) */
+/* The encoding of each kind of plan, once: what its rtc_plan_sim_* hook hands back and what the executor records for
+ * rtc_scene_last_plan (rtc_plan.h Recorded). */
+/* a launch.  The trailer: the regrowth (hipFree + hipMalloc of the scratch or the sample slots: the device is synchronised
+ * first; so it is before the draw cache is cleared or its item-draw arrays regrown) and the plan's shape */
+int encode_launch(const rtcplan::Plan &p, const rtcplan::Request &r, int *ops, int maxOps, unsigned long long *fp, int maxFp)
+{
+    return serialise(p.ops, p.nOps, ops, maxOps, fp, maxFp,
+                     {p.scratchGrow || p.samplesGrow || p.drawReset || p.itemDrawGrow, (unsigned long long)p.half,
+                      p.chainOnCs, p.overlap, p.slotOffset},
+                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
+                         return rtcplan::kernel_footprint(p, r, o.kernel, f, max);
+                     });
+}
+/* an update.  The trailer: (~0, nothing regrown, the generation written, -, -, -) */
+int encode_update(const rtcplan::UpdatePlan &u, int *ops, int maxOps, unsigned long long *fp, int maxFp)
+{
+    return serialise(u.ops, u.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)u.writes, 0, 0, 0},
+                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) {
+                         return rtcplan::update_footprint(u, f, max);
+                     });
+}
+/* a regroup.  The trailer: (~0, nothing regrown, the generation written, the levels, -, -) */
+int encode_regroup(const rtcplan::RegroupPlan &g, uint64_t scratch, int *ops, int maxOps, unsigned long long *fp, int maxFp)
+{
+    return serialise(g.ops, g.nOps, ops, maxOps, fp, maxFp,
+                     {0, (unsigned long long)g.writes, (unsigned long long)g.levels, 0, 0},
+                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
+                         return rtcplan::regroup_footprint(g, o.kernel, scratch, f, max);
+                     });
+}
+/* a query, its one kernel's rows given.  The trailer: (~0, nothing regrown, the generation read, -, -, -) */
+int encode_query(const rtcplan::TracePlan &t, const rtcplan::Footprint *rows, int n, int *ops, int maxOps,
+                 unsigned long long *fp, int maxFp)
+{
+    return serialise(t.ops, t.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)t.gen, 0, 0, 0},
+                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) {
+                         std::copy(rows, rows + std::min(n, max), f);
+                         return n;
+                     });
+}
+
+/* a query, once its hook has refused what its entry point refuses: planned, the state adopted, and handed back */
 template <class FootprintOf>
 int sim_query(RtcPlanSim *s, int kernel, int *ops, int maxOps, unsigned long long *fp, int maxFp, FootprintOf footprint)
 {
     rtcplan::TracePlan t;
     rtcplan::plan_query(s->st, kernel, t);
     s->st = t.after;
-    return serialise(t.ops, t.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)t.gen, 0, 0, 0},
-                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) { return footprint(t, f, max); });
+    rtcplan::Footprint rows[24];
+    const int n = std::min(footprint(t, rows, 24), 24);
+    return encode_query(t, rows, n, ops, maxOps, fp, maxFp);
 }
 } // namespace
+
+namespace rtcplan {
+/* A Recorded holds every operation any plan can have; its rows suffice for every plan there is (a launch has some 60),
+ * and a plan that ever had more is not recorded in part: serialise counts what there is, not what fitted, so such a
+ * record is void (encoded 0) and rtc_scene_last_plan never reads past what was stored. */
+static_assert(sizeof Plan{}.ops / sizeof(Op) <= kRecordedOps && sizeof UpdatePlan{}.ops / sizeof(Op) <= kRecordedOps &&
+                  sizeof RegroupPlan{}.ops / sizeof(Op) <= kRecordedOps && sizeof TracePlan{}.ops / sizeof(Op) <= kRecordedOps,
+              "a Recorded holds the operations of every kind of plan");
+static_assert(kRecordedOps <= 0xff, "nOps | rows << 8");
+static int stored(int encoded)
+{
+    return (encoded & 0xff) <= kRecordedOps && (encoded >> 8) <= kRecordedRows ? encoded : 0;
+}
+void record_launch(const Plan &p, const Request &r, Recorded &out)
+{
+    out.encoded = stored(encode_launch(p, r, out.ops, kRecordedOps, out.fp, kRecordedRows));
+}
+void record_update(const UpdatePlan &u, Recorded &out)
+{
+    out.encoded = stored(encode_update(u, out.ops, kRecordedOps, out.fp, kRecordedRows));
+}
+void record_regroup(const RegroupPlan &g, uint64_t scratch, Recorded &out)
+{
+    out.encoded = stored(encode_regroup(g, scratch, out.ops, kRecordedOps, out.fp, kRecordedRows));
+}
+void record_query(const TracePlan &t, const Footprint *rows, int n, Recorded &out)
+{
+    out.encoded = stored(encode_query(t, rows, n, out.ops, kRecordedOps, out.fp, kRecordedRows));
+}
+} // namespace rtcplan
 
 extern "C" int rtc_plan_sim_create(int triCount, int legacySlotLayout, RtcPlanSim **out)
 {
@@ -771,14 +842,7 @@ extern "C" int rtc_plan_sim_launch(RtcPlanSim *s, const RtcRenderDesc *d, unsign
     rtcplan::Plan &p = s->last;
     rtcplan::plan_launch(s->st, r, p);
     s->st = p.after;
-    /* the trailer: the scratch regrowth (hipFree + hipMalloc: the device is synchronised first; so it is before the draw
-     * cache is cleared or its item-draw arrays regrown) and the plan's shape */
-    return serialise(p.ops, p.nOps, ops, maxOps, fp, maxFp,
-                     {p.scratchGrow || p.samplesGrow || p.drawReset || p.itemDrawGrow, (unsigned long long)p.half,
-                      p.chainOnCs, p.overlap, p.slotOffset},
-                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
-                         return rtcplan::kernel_footprint(p, r, o.kernel, f, max);
-                     });
+    return encode_launch(p, r, ops, maxOps, fp, maxFp);
 }
 
 extern "C" int rtc_plan_sim_set_update_fault(RtcPlanSim *s, int mode)
@@ -798,11 +862,7 @@ extern "C" int rtc_plan_sim_update(RtcPlanSim *s, unsigned long long stream, int
     rtcplan::UpdatePlan u;
     rtcplan::plan_update(s->st, s->updateFault, u);
     s->st = u.after;
-    /* the trailer: (~0, nothing regrown, the generation written, -, -, -) */
-    return serialise(u.ops, u.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)u.writes, 0, 0, 0},
-                     [&](const rtcplan::Op &, rtcplan::Footprint *f, int max) {
-                         return rtcplan::update_footprint(u, f, max);
-                     });
+    return encode_update(u, ops, maxOps, fp, maxFp);
 }
 
 extern "C" int rtc_plan_sim_regroup(RtcPlanSim *s, unsigned long long stream, unsigned long long scratch, int *ops,
@@ -816,11 +876,7 @@ extern "C" int rtc_plan_sim_regroup(RtcPlanSim *s, unsigned long long stream, un
     rtcplan::RegroupPlan g;
     rtcplan::plan_regroup(s->st, regroup_levels(s->shape.triPadded), g);
     s->st = g.after;
-    /* the trailer: (~0, nothing regrown, the generation written, the levels, -, -) */
-    return serialise(g.ops, g.nOps, ops, maxOps, fp, maxFp, {0, (unsigned long long)g.writes, (unsigned long long)g.levels, 0, 0},
-                     [&](const rtcplan::Op &o, rtcplan::Footprint *f, int max) {
-                         return rtcplan::regroup_footprint(g, o.kernel, scratch, f, max);
-                     });
+    return encode_regroup(g, scratch, ops, maxOps, fp, maxFp);
 }
 
 extern "C" int rtc_plan_sim_trace_rays(RtcPlanSim *s, unsigned long long stream, unsigned long long rays,

@@ -266,7 +266,9 @@ enum Res : int { kResScratch = 0, kResPrim = 1, kResGeoSet = 2, kResSamples = 3,
                  kResTMax = 16 /* id: the caller's limit buffer */, kResOccluded = 17 /* id: the caller's byte buffer */,
                  kResMembership = 18 /* the scene's cluster membership (clIndex) */,
                  kResRegroupScratch = 19 /* id: the caller's regroup scratch */,
-                 kResPixelList = 20 /* id: the caller's list of pixels (rtc_render_pixels_async) */ };
+                 kResPixelList = 20 /* id: the caller's list of pixels (rtc_render_pixels_async) */,
+                 kResDrawPool = 21 /* the draw cache's blocks: append-only (Buf), so in no footprint row; rtc_scene_spans
+                                      lists them under this number */ };
 enum Access : int { kRead = 0, kWrite = 1, kAtomic = 2, kKeyedWrite = 3 /* writes values the key determines */ };
 struct Footprint {
     int res, access;
@@ -355,5 +357,21 @@ int occluded_footprint(const TracePlan &t, uint64_t rays, uint64_t tMax, uint64_
  * footprint).  The accumulator, the states and the Color carry the resources a launch's footprint gives them. */
 int pixels_footprint(const TracePlan &t, uint64_t pixels, uint64_t colors, uint64_t accum, uint64_t rngState, bool segments,
                      bool readState, Footprint *out, int max);
+
+/* What a scene's most recent enqueue planned (RtcDeviceScene::lastPlan, rtc_scene_last_plan), kept as the rtc_plan_sim_*
+ * hooks hand a plan back: 4 ints per operation, 6 u64 per footprint row, the hook's trailing ~0 record, and
+ * encoded = nOps | rows << 8 (0: nothing enqueued yet).  Each record_* is the one encoding its rtc_plan_sim_* hook returns
+ * too, filled from the plan the executor ran when every operation of it is enqueued: host stores, no device work. */
+constexpr int kRecordedOps = 48, kRecordedRows = 256;
+struct Recorded {
+    int encoded;
+    int ops[4 * kRecordedOps];
+    unsigned long long fp[6 * kRecordedRows];
+};
+void record_launch(const Plan &p, const Request &r, Recorded &out);
+void record_update(const UpdatePlan &u, Recorded &out);
+void record_regroup(const RegroupPlan &g, uint64_t scratch, Recorded &out);
+/* a query: `rows` is what its *_footprint call returned for `t` (n of them) */
+void record_query(const TracePlan &t, const Footprint *rows, int n, Recorded &out);
 
 } // namespace rtcplan

@@ -565,6 +565,12 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         for (hipEvent_t ev : {geoEvent, frameEvent})
             if (ev)
                 HIP_TRY(hipEventRecord(ev, st));
+        /* rtc_scene_last_plan: the planner's empty launch (it reads no more of the request than this) */
+        rtcplan::Request none{};
+        none.firstHit = hit != nullptr;
+        rtcplan::Plan empty;
+        rtcplan::plan_launch(s->plan, none, empty);
+        rtcplan::record_launch(empty, none, ms->lastPlan);
         return 0;
     }
     static thread_local rtcplan::Plan pl;
@@ -640,6 +646,7 @@ static int render_rows(const RtcDeviceScene *s, const Scene *scene, const RtcCam
         *items = RtcCullItems{P.geoCount, P.geoList,   P.pixMask, P.geoCap,    P.blocksX * 2,        pl.tiles, P.wideItems,
                               P.tileMask, P.maskWords, P.primF,   P.triPadded, pl.superCull ? 1 : 0};
     }
+    rtcplan::record_launch(pl, rq, ms->lastPlan); /* (behind the last refusal: a call that fails leaves the record) */
     return 0;
 }
 
@@ -721,10 +728,11 @@ static void set_rays(Args &a, const Ray *dRays, size_t n)
 /* From a query's args, its own fields filled, to its kernel enqueued on `stream` (n > 0).  The planner names the generation
  * and the one operation (rtc_plan.h plan_query); the ordering state stays as it is (TracePlan::after == s->plan), and so do
  * the hooks, the timing events, the chain report and the draw cache.  `raysPerGroup`: how many rays a workgroup of the
- * table's kernels takes (kBlock: a lane each; kBlock / 64: a wave each, at most 2^29 workgroups for 2^31 - 1 rays). */
-template <class Args>
+ * table's kernels takes (kBlock: a lane each; kBlock / 64: a wave each, at most 2^29 workgroups for 2^31 - 1 rays).
+ * `rows(plan, out, max)`: the query's footprint call (rtc_plan.h), recorded with the plan for rtc_scene_last_plan. */
+template <class Args, class Rows>
 static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, void (*const (&table)[2][2])(Args), Args &a,
-                         const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream,
+                         const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream, Rows rows,
                          size_t raysPerGroup = kBlock)
 {
     RtcDeviceGuard guard(s->device);
@@ -747,6 +755,9 @@ static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, v
                            a);
         HIP_TRY(hipGetLastError());
     }
+    rtcplan::Footprint f[24];
+    const int nf = std::min(rows(tp, f, 24), 24);
+    rtcplan::record_query(tp, f, nf, const_cast<RtcDeviceScene *>(s)->lastPlan);
     return 0;
 }
 
@@ -754,12 +765,12 @@ static int enqueue_query(const char *who, const RtcDeviceScene *s, int kernel, v
  * lane per ray, and a wave per ray (rtc_trace_paths.h): the same operation, buffers and ordering,
  * kBlock / 64 rays to a workgroup. */
 #define PATH_TABLE(k) {{k<false, false>, k<false, true>}, {k<true, false>, k<true, true>}} /* <SPHERES, CULL> */
-template <class Args>
+template <class Args, class Rows>
 static int enqueue_path_query(const char *who, const RtcDeviceScene *s, int kernel, void (*const (&table)[2][2][2])(Args),
-                              Args &a, const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream)
+                              Args &a, const Ray *dRays, size_t n, int trianglesOnly, int flags, void *stream, Rows rows)
 {
     const bool wave = (flags & RTC_F_WAVE_PER_RAY) != 0;
-    return enqueue_query(who, s, kernel, table[wave], a, dRays, n, trianglesOnly, flags, stream,
+    return enqueue_query(who, s, kernel, table[wave], a, dRays, n, trianglesOnly, flags, stream, rows,
                          wave ? kBlock / 64 : kBlock);
 }
 
@@ -789,7 +800,12 @@ extern "C" int rtc_trace_rays_async(const RtcDeviceScene *s, const Ray *dRays, s
     /* <SPHERES, CULL> */
     static void (*const kTraceRays[2][2])(TraceRaysArgs) = {{rtc_trace_rays<false, false>, rtc_trace_rays<false, true>},
                                                             {rtc_trace_rays<true, false>, rtc_trace_rays<true, true>}};
-    return enqueue_query(who, s, rtcplan::kKTraceRays, kTraceRays, a, dRays, n, trianglesOnly, flags, stream);
+    const uint64_t ids[4] = {(uint64_t)(uintptr_t)out->prim, (uint64_t)(uintptr_t)out->depth,
+                             (uint64_t)(uintptr_t)out->normal, (uint64_t)(uintptr_t)out->albedo};
+    return enqueue_query(who, s, rtcplan::kKTraceRays, kTraceRays, a, dRays, n, trianglesOnly, flags, stream,
+                         [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                             return rtcplan::trace_footprint(t, (uint64_t)(uintptr_t)dRays, ids, f, max);
+                         });
 }
 
 extern "C" int rtc_trace_rays(const RtcDeviceScene *s, const Ray *rays, size_t n, int trianglesOnly, int flags, int *prim,
@@ -843,8 +859,13 @@ extern "C" int rtc_trace_paths_async(const RtcDeviceScene *s, const Scene *scene
     a.seeds = dSeeds, a.radiance = dRadiance, a.seedsOut = dSeedsOut, a.segments = dSegments;
     static void (*const kTracePaths[2][2][2])(TracePathsArgs) = {PATH_TABLE(rtc_trace_paths),
                                                                  PATH_TABLE(rtc_trace_paths_wave)};
-    return enqueue_path_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags,
-                              stream);
+    return enqueue_path_query(who, s, rtcplan::kKTracePaths, kTracePaths, a, dRays, n, d->trianglesOnly, d->flags, stream,
+                              [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                                  return rtcplan::paths_footprint(t, (uint64_t)(uintptr_t)dRays, (uint64_t)(uintptr_t)dSeeds,
+                                                                  (uint64_t)(uintptr_t)dRadiance,
+                                                                  (uint64_t)(uintptr_t)dSeedsOut, dSegments != nullptr,
+                                                                  d->sampleFirst > 0, f, max);
+                              });
 }
 
 extern "C" int rtc_trace_paths(const RtcDeviceScene *s, const Scene *scene, const Ray *rays, const unsigned int *seeds,
@@ -892,7 +913,11 @@ extern "C" int rtc_occluded_async(const RtcDeviceScene *s, const Ray *dRays, con
     /* <SPHERES, CULL> */
     static void (*const kOccluded[2][2])(OccludedArgs) = {{rtc_occluded<false, false>, rtc_occluded<false, true>},
                                                           {rtc_occluded<true, false>, rtc_occluded<true, true>}};
-    return enqueue_query(who, s, rtcplan::kKOccluded, kOccluded, a, dRays, n, trianglesOnly, flags, stream);
+    return enqueue_query(who, s, rtcplan::kKOccluded, kOccluded, a, dRays, n, trianglesOnly, flags, stream,
+                         [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                             return rtcplan::occluded_footprint(t, (uint64_t)(uintptr_t)dRays, (uint64_t)(uintptr_t)dTMax,
+                                                                (uint64_t)(uintptr_t)dOccluded, dCount != nullptr, f, max);
+                         });
 }
 
 extern "C" int rtc_occluded(const RtcDeviceScene *s, const Ray *rays, const float *tMax, size_t n, int trianglesOnly,
@@ -968,8 +993,13 @@ extern "C" int rtc_render_pixels_async(const RtcDeviceScene *s, const Scene *sce
     a.colors = (unsigned char *)dColors, a.accum = dAccum, a.rngState = dRngState, a.segments = dSegments;
     static void (*const kRenderPixels[2][2][2])(RenderPixelsArgs) = {PATH_TABLE(rtc_render_pixels),
                                                                      PATH_TABLE(rtc_render_pixels_wave)};
-    return enqueue_path_query(who, s, rtcplan::kKRenderPixels, kRenderPixels, a, nullptr, n, d->trianglesOnly, flags,
-                              stream);
+    return enqueue_path_query(who, s, rtcplan::kKRenderPixels, kRenderPixels, a, nullptr, n, d->trianglesOnly, flags, stream,
+                              [&](const rtcplan::TracePlan &t, rtcplan::Footprint *f, int max) {
+                                  return rtcplan::pixels_footprint(t, (uint64_t)(uintptr_t)dPixels,
+                                                                   (uint64_t)(uintptr_t)dColors, (uint64_t)(uintptr_t)dAccum,
+                                                                   (uint64_t)(uintptr_t)dRngState, dSegments != nullptr,
+                                                                   range->first > 0, f, max);
+                              });
 }
 
 extern "C" int rtc_render_pixels(const RtcDeviceScene *s, const Scene *scene, const RtcCamera *cam, const RtcRenderDesc *d,

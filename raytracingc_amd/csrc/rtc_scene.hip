@@ -625,6 +625,62 @@ extern "C" int rtc_scene_chain_report(const RtcDeviceScene *s, RtcChainReport *o
     return 0;
 }
 
+extern "C" int rtc_scene_last_plan(const RtcDeviceScene *s, int *ops, int maxOps, unsigned long long *footprint,
+                                   int maxFootprint)
+{
+    if (!s || !ops || !footprint)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_last_plan: null argument");
+    const rtcplan::Recorded &r = s->lastPlan;
+    const int nOps = r.encoded & 0xff, rows = r.encoded >> 8;
+    if (maxOps < nOps || maxFootprint < rows)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_last_plan: room for %d operations and %d rows, the plan has %d and %d",
+                        maxOps, maxFootprint, nOps, rows);
+    std::copy(r.ops, r.ops + 4 * nOps, ops);
+    std::copy(r.fp, r.fp + 6 * (size_t)rows, footprint);
+    return r.encoded;
+}
+
+/* Every device allocation of a scene, by the planner's resource numbers (rtc_plan.h Res).  The allocations are those of
+ * rtc_scene_upload_with_share (the two generations' arrays, clIndex, primF, primX, segSlots, geoCounts), of
+ * rtc_render.hip's grow_capacity (scratch, samples) and of draws_prepare above (table, ctr, blockSeed, pool, itemDraw):
+ * a new hipMalloc in one of them needs its span here (tests/test_footprints.py counts them). */
+extern "C" int rtc_scene_spans(const RtcDeviceScene *s, RtcSpan *out, int max)
+{
+    if (!s || !out)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_spans: null argument");
+    int n = 0;
+    const auto span = [&](int res, unsigned long long id, int part, const void *base, size_t bytes) {
+        if (n < max)
+            out[n] = RtcSpan{(unsigned long long)res, id, (unsigned long long)part,
+                             (unsigned long long)(uintptr_t)(base && bytes ? base : nullptr), base ? bytes : 0};
+        ++n;
+    };
+    span(rtcplan::kResScratch, 0, 0, s->scratch, s->plan.scratchCap);
+    for (int h = 0; h < kSkySlots; ++h) {
+        span(rtcplan::kResPrim, h, 0, s->primF + (size_t)h * s->primStride, s->primStride * sizeof(DevPrimF));
+        span(rtcplan::kResPrim, h, 1, s->primX + (size_t)h * s->primStride, s->primStride * sizeof(DevPrimX));
+    }
+    for (int q = 0; q < kGeoRing; ++q)
+        span(rtcplan::kResGeoSet, q, 0, s->geoCounts + (size_t)q * kGeoSetInts, kGeoSetInts * sizeof(int));
+    span(rtcplan::kResSamples, 0, 0, s->samples, s->plan.samplesCap);
+    span(rtcplan::kResSegSlots, 0, 0, s->segSlots, 256 * 16 * sizeof(unsigned long long));
+    for (int g = 0; g < 2; ++g)
+        for (int k = 0; k < kSceneArrayCount; ++k)
+            span(rtcplan::kResSceneGen, g, k, scene_array(s->gen[g], k), s->recBytes[k]);
+    const RtcDeviceScene::Draws &D = s->draws;
+    span(rtcplan::kResDrawTable, 0, 0, D.table, D.tablePixels * sizeof(unsigned));
+    span(rtcplan::kResDrawTable, 0, 1, D.ctr, kDcWords * sizeof(unsigned));
+    span(rtcplan::kResDrawTable, 0, 2, D.blockSeed, D.capacity * sizeof(unsigned));
+    for (int h = 0; h < kSkySlots; ++h)
+        span(rtcplan::kResItemDraw, h, 0, D.itemDraw ? D.itemDraw + (size_t)h * (s->plan.itemDrawCap / kSkySlots) : nullptr,
+             s->plan.itemDrawCap / kSkySlots);
+    span(rtcplan::kResMembership, 0, 0, s->clIndex, (size_t)s->clusterCount * kClusterSize * sizeof(int));
+    span(rtcplan::kResDrawPool, 0, 0, D.pool, D.capacity * kDrawBlockBytes);
+    if (n > max)
+        return rtc_fail(RTC_EINVAL, "rtc_scene_spans: room for %d spans, the scene has %d", max, n);
+    return n;
+}
+
 /* ---- the draw cache's memory (rtc_layout.h RtcDeviceScene::Draws; the kernels: rtc_cull.h, rtc_chain.h) -------------- */
 void rtc_draws_free(RtcDeviceScene *s)
 {
@@ -1067,6 +1123,7 @@ extern "C" int rtc_scene_update_async(RtcDeviceScene *s, const Triangle *dTris, 
         }
     }
     s->plan = up.after; /* every operation is enqueued */
+    rtcplan::record_update(up, s->lastPlan);
     return 0;
 }
 
@@ -1136,6 +1193,7 @@ extern "C" int rtc_scene_regroup_async(RtcDeviceScene *s, const Triangle *dTris,
         }
     }
     s->plan = gp.after; /* every operation is enqueued */
+    rtcplan::record_regroup(gp, (uint64_t)(uintptr_t)dScratch, s->lastPlan);
     return 0;
 }
 
