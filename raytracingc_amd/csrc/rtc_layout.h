@@ -469,6 +469,5 @@ static inline EnvParams env_of(const Scene &s)
     return e;
 }
 
-/* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB: 393,216 triangles); larger
- * scenes render without it, and without the geometry kernel whose occupancy bounce_hit_share chooses */
-constexpr int kMaxCullMaskWords = 6144;
+/* the tile cull's cap on a scene's mask words: the planner's (rtc_plan.h) */
+constexpr int kMaxCullMaskWords = rtcplan::kMaxCullMaskWords;

@@ -147,7 +147,7 @@ void plan_launch(const State &s, const Request &r, Plan &p)
     p.resume = r.resume;
     p.resumeRead = r.resume && r.sampleFirst > 0;
     /* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB) */
-    p.cull = !(r.flags & RTC_F_NO_TILE_CULL) && r.maskWords <= 6144;
+    p.cull = !(r.flags & RTC_F_NO_TILE_CULL) && r.maskWords <= kMaxCullMaskWords;
     /* the split launch (rtc_render_chain + the sky pass): every triangle-only scene, and the sphere scenes sphere_split
      * admits */
     p.fused = p.cull && !p.debug && (r.sphereCount == 0 || r.sphereSplit) &&

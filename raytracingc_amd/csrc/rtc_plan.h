@@ -36,6 +36,9 @@ constexpr size_t kItemRecordBytes = 16;
 constexpr int kItemCoordMax = 65535;
 constexpr size_t kInlineSumPixels = 600000; /* small shares, and the alternating cull streams' limit for whole frames */
 constexpr size_t kSuperCullPixels = 400000; /* launches of more pixels run rtc_super_cull */
+/* the tile cull keeps a workgroup's prefilter survivors in LDS (maskWords u64, <= 48 KB: 393,216 triangles); larger
+ * scenes render without it, and without the geometry kernel whose occupancy bounce_hit_share chooses */
+constexpr int kMaxCullMaskWords = 6144;
 constexpr size_t kSampleBufBudget = (size_t)2 << 30;
 constexpr size_t kSampleSlotBytes = 12;
 /* Sphere scenes through the split launch: at most kSplitSpheresMax spheres (the per-lane sphere loop of

@@ -152,6 +152,9 @@ LAYER_CAMERAS = (((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), 1.0), ((0.1, 0.0, 0.05), (0.
                  ((-0.1, 0.0, -0.05), (0.0, 0.0, 1.0), 1.0))
 
 
+LARGE_SCENE_SIZES = {"w257": (48, 40), "cap": (33, 17), "past_cap": (33, 17)}  # the frames of tests/large_scenes.py
+
+
 def _default_cameras():
     o = rt.DEFAULT_ORIGIN
     return tuple((tuple(np.add(o, d)), rt.DEFAULT_LOOKING_AT, rt.DEFAULT_FOV)
@@ -167,6 +170,12 @@ def geometry(scene):
 
     if scene == "layers_33":
         return PATH_SCENES[scene][0], None, LAYER_CAMERAS
+    if scene in LARGE_SCENE_SIZES:  # (tests/large_scenes.py: the case's camera sees the whole field, the others stand aside)
+        import large_scenes
+
+        T = large_scenes.CLASSES[scene]
+        return large_scenes.tris(scene), None, tuple(large_scenes.camera_args(T, *LARGE_SCENE_SIZES[scene], shift=d)
+                                                     for d in ((0.0, 0.0, 0.0), (0.7, 0.2, 0.4), (-0.5, -0.3, 0.6)))
     if scene == "open5":
         return load_tris("ultracomplex")[0], open5(), _default_cameras()
     if scene == "default":
@@ -235,6 +244,10 @@ JOINED = [
     # (the sphere covers the frame from every camera: full pixel masks, equal weights and the same order each time)
     Case("default_sphere_one_lane", "default", must=("mask", "prim"),
          rows=(("order", "order", WRITE), ("render", "order", READ)), absent=("chain", "sky")),
+    # 257 mask words and 65 chunks (tests/large_scenes.py): the split launch past one stride of the tile cull's workgroup
+    # (the field fills the same pixels from each of its cameras: the pixel masks are rewritten as they were)
+    Case("w257_split", "w257", size=LARGE_SCENE_SIZES["w257"], must=("mask", "geoList", "prim", "geoset", "samples"),
+         rows=_SPLIT_ROWS + (("chain", "samples", WRITE), ("accum", "samples", READ))),
 ]
 LARGE = [
     Case("super_cull", "cube", size=(1024, 400), spp=1, must=_SPLIT + ("superMask",),
@@ -242,6 +255,9 @@ LARGE = [
     # (the cube stays within the same superblocks of so wide a frame: their survivor words are rewritten as they were)
     Case("wide_items", "cube", size=(70000, 8), spp=1, must=_SPLIT,
          rows=_SPLIT_ROWS + (("super_cull", "superMask", WRITE),)),
+    # 6,145 mask words (tests/large_scenes.py): past the tile cull's cap the launch asks for neither cull nor split launch
+    Case("past_cap", "past_cap", size=LARGE_SCENE_SIZES["past_cap"], must=("prim",), rows=(("prep", "prim", WRITE),),
+         absent=("tile_cull", "super_cull", "chain", "sky", "order")),
 ]
 # a small row share, pipelined: the planner merges the sky pass behind the geometry kernel
 MERGE = Case("merge_small_share", "cube", size=(64, 80), cfg=(("overlap", True), ("row_stride", 2), ("chain_inline", True)),
@@ -299,11 +315,12 @@ class Sim:
 
     IDS = dict(colors=0x1000, accum=0x2000, rng=0x3000, hit=(0x4000, 0x5000, 0x6000, 0x7000))
 
-    def __init__(self, scene, cache=False):
-        tris, sph, _ = geometry(scene)
+    def __init__(self, scene, cache=False, tri_count=None):
+        """tri_count: a scene of that many triangles and no sphere, in place of the named one's."""
+        tris, sph, _ = geometry(scene) if tri_count is None else (None, None, None)
         self.L = rt.lib()
         self.h = C.c_void_p()
-        assert self.L.rtc_plan_sim_create(len(tris), 0, C.byref(self.h)) == 0
+        assert self.L.rtc_plan_sim_create(len(tris) if tri_count is None else tri_count, 0, C.byref(self.h)) == 0
         if sph is not None:  # (the matrix's sphere scenes: `default` stays on the one-lane kernel, open5 is forced)
             assert self.L.rtc_plan_sim_set_spheres(self.h, len(sph), 0) == 0
         assert self.L.rtc_plan_sim_set_draw_cache(self.h, int(cache)) == 0
