@@ -617,6 +617,69 @@ int rtc_ray_keys_host(const Ray *rays, size_t n, const float lo[3], const float 
  * dword buffer.  n == 0: returns 0, nothing enqueued. */
 int rtc_gather_async(void *dDst, const void *dSrc, const unsigned *dOrder, size_t n, size_t elemBytes, void *stream);
 int rtc_scatter_async(void *dDst, const void *dSrc, const unsigned *dOrder, size_t n, size_t elemBytes, void *stream);
+/* The next pixel list of an adaptively sampled frame, made on the device: the producer of the list that
+ * rtc_render_pixels_async takes, the per-pixel sample counts, and the final normalise-and-quantise.  The entries work on
+ * the current device (like rtc_gather_async): they name no scene and take no part in the launch planner.
+ * The selection, for pixel p with A = dAccum[3 p ..] and P = dPrev[3 p ..] (a snapshot of the accumulator at an earlier
+ * sample count, which the caller makes with a device-to-device copy), all arithmetic f32, operation by operation, no
+ * contraction:
+ *   e_c = fabsf(A_c * wAccum - P_c * wPrev)   for c = x, y, z
+ *   d   = (e_x + e_y) + e_z
+ *   l   = ((A_x + A_y) + A_z) * wLevel
+ *   selected(p) = d * d > threshold * (l + floor)
+ * The comparison is strict (equality is not selected) and false for any NaN; infinities, an overflowing d * d and a
+ * negative l + floor get what the arithmetic gives.  The weights are the caller's: with wAccum = spp / (done - before),
+ * wPrev = wAccum + spp / before and wLevel = spp / done the statement compares the mean of the samples since the snapshot
+ * with the mean before it, a squared relative-error test without a division or a square root.  samplesDone is what the
+ * call stamps into dSamples. */
+typedef struct RtcSelectDesc {
+    float wAccum, wPrev, wLevel; /* host weights, the caller's */
+    float floor, threshold;
+    int samplesDone;
+} RtcSelectDesc;
+/* rtc_select_pixels_async.  The input sequence is dIn[0, nIn), or 0 .. pixelCount - 1 with dIn == NULL (nIn must then be
+ * 0).  An entry >= pixelCount is invalid: nothing is loaded for it, it is not selected and not stamped -- the sentinel tail
+ * of an earlier output is this case, and invalid entries may stand anywhere.  The selected valid entries go to
+ * dOut[0, min(count, capacity)) IN INPUT ORDER: the output is a subsequence of the input (stable; ascending when the input
+ * is; duplicates judged and listed once each); dOut[k] = 0xFFFFFFFF for min(count, capacity) <= k < capacity, which
+ * rtc_render_pixels_async skips; *dCount = count, a store: the number selected BEFORE the cut at capacity, so the caller
+ * sees an overflow.  Where dSamples is given, dSamples[p] = sel->samplesDone for every valid entry p, selected or not (the
+ * select visits exactly the pixels the pass before it rendered).  dOut == NULL goes with capacity == 0: a call that only
+ * stamps and counts.  nIn == 0 with a list: dOut[0, capacity) becomes sentinels and *dCount = 0 -- enqueued work, not a
+ * no-op, because the next pass reads the list.
+ * dScratch: rtc_select_scratch_bytes(n) bytes of device memory, 16-byte aligned, n the input sequence's length (nIn, or
+ * pixelCount without a list); all temporary storage.  Three kernels -- judge (one ballot word per 64 entries and a count
+ * per tile of T entries), scan (one workgroup, G tile counts a step), emit -- without atomics and without one workgroup
+ * waiting for another, so the result is a function of the inputs alone.
+ * Asynchronous on `stream`, complete there: no allocation, no synchronisation, no host read of device memory; nothing is
+ * written outside dOut[0, capacity), the 8 bytes of dCount, dSamples at valid entries and the scratch's stated size; the
+ * accumulator, the snapshot and the input are only read.  The frame's buffers must not be the target of an RTC_F_OVERLAP
+ * launch still in flight (rtc_render_pixels_async's rule).
+ * RTC_EINVAL, checked before any device call: a null dAccum, dPrev or sel; pixelCount, nIn or capacity > 0x7fffffff;
+ * dIn == NULL with nIn != 0; dOut == NULL with capacity != 0; dOut, dCount and dSamples all null; dOut == dIn; dSamples
+ * given with samplesDone < 0; dScratch null, not 16-byte aligned or scratchBytes too small. */
+size_t rtc_select_scratch_bytes(size_t nIn); /* a multiple of 16, monotone in nIn */
+/* The select's shape (host only): the entries a workgroup takes (T) and the tile counts the scan workgroup takes per step
+ * of its loop (G) -- n = T +- 1, 2 T + 1 and G T + 1 are the sizes at which the select takes another path. */
+int rtc_select_shape(int *entriesPerGroup, int *scanGroups);
+int rtc_select_pixels_async(const float *dAccum, const float *dPrev, size_t pixelCount,
+                            const unsigned *dIn /* nullable */, size_t nIn, const RtcSelectDesc *sel,
+                            unsigned *dOut /* nullable */, size_t capacity, unsigned long long *dCount /* nullable */,
+                            int *dSamples /* nullable */, void *dScratch, size_t scratchBytes, void *stream);
+/* The same statement and the same sequence semantics for HOST arrays in plain C++, without a GPU and without scratch: what
+ * the device's output, count and samples are compared with, byte for byte.  The same refusals (but the scratch's). */
+int rtc_select_pixels_host(const float *accum, const float *prev, size_t pixelCount, const unsigned *in, size_t nIn,
+                           const RtcSelectDesc *sel, unsigned *out, size_t capacity, unsigned long long *count,
+                           int *samples);
+/* The displayable frame of an adaptive render: every sample is weighted 1 / spp, so a pixel that stopped at s samples is
+ * spp / s too dark.  Per pixel p: s = dSamples[p]; scale = s > 0 ? (float)spp / (float)s : 0.f (the correctly rounded
+ * f32 division); dColors[3 p + c] = floatToUint(dAccum[3 p + c] * scale) (moremath.c:25-30; NaN gives 0, as
+ * rtc_quantize).  Exactly 3 * pixelCount bytes are written, at any byte alignment of dColors: whole dwords where aligned,
+ * single bytes at a ragged head or tail.  Asynchronous on `stream`, on the current device.  pixelCount == 0: returns 0,
+ * nothing enqueued.  RTC_EINVAL: a null pointer, spp <= 0, pixelCount > 0x7fffffff. */
+int rtc_resolve_async(const float *dAccum, const int *dSamples, size_t pixelCount, int spp, void *dColors, void *stream);
+/* The same for HOST arrays, without a GPU (rtc_quantize of the scaled accumulator). */
+int rtc_resolve_host(const float *accum, const int *samples, size_t pixelCount, int spp, void *colors);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */

@@ -55,6 +55,7 @@ from ._abi import (  # noqa: F401
     RtcPathDesc,
     RtcRenderDesc,
     RtcSampleRange,
+    RtcSelectDesc,
     RtcStats,
     Scene,
     Vec3,
@@ -70,6 +71,7 @@ __all__ = [
     "SCENE_DT", "RtcError", "ProgressState", "save_progress", "load_progress", "scene_records_host", "RECORD_ARRAYS",
     "ray_keys_host", "ray_order_scratch_bytes", "gather_async", "scatter_async",
     "regroup_membership_host", "regroup_max_tris", "adaptive_selection",
+    "select_desc", "select_pixels", "select_pixels_async", "select_scratch_bytes", "resolve", "resolve_async",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -867,6 +869,66 @@ class DeviceScene:
             host = (colors.cpu().numpy(), accum.cpu().numpy())
             yield done, host[0], host[1], samples.copy()
 
+    def render_adaptive_device(self, scene: Scene, cam: RtcCamera, cfg: RenderConfig, passes, threshold: float,
+                               floor: float, capacity: int, flags: int = RTC_F_WAVE_PER_RAY) -> dict:
+        """One adaptively sampled frame enqueued whole on torch's current stream, without one synchronisation or host read
+        (DESIGN 3.20).  `passes`: at least two sample counts summing to at most cfg.spp.  Passes 0 and 1 are whole passes
+        (render_samples_async); a snapshot of the accumulator is taken before every pass from 1 on (a device-to-device
+        copy), and after it select_pixels_async judges the pixels the pass rendered -- every pixel after pass 1, the last
+        list after a later one -- with select_desc(cfg.spp, before, done, threshold, floor) and stamps `done` into
+        `samples`; its output, cut at `capacity`, is the list of the next pass (render_pixels_async with n = capacity and
+        `flags`; the sentinel tail is skipped there), alternating between two list buffers.  The last pass's select only
+        stamps and counts (capacity 0), and resolve_async makes the displayable frame.  Returns device tensors: "colors"
+        uint8 [rows, W, 3] (resolved), "accum" float32 [rows, W, 3], "rng" int32 [rows, W], "samples" int32 [rows, W] and
+        "counts" int64 [len(passes) - 1]: what each select chose BEFORE the cut at capacity.  Nothing is complete until
+        the stream is."""
+        import torch
+
+        passes = [int(c) for c in passes]
+        capacity = int(capacity)
+        if len(passes) < 2 or any(c <= 0 for c in passes) or sum(passes) > cfg.spp:
+            raise ValueError(f"render_adaptive_device: passes {passes} are not two or more positive counts summing to at "
+                             f"most spp = {cfg.spp}")
+        if not 1 <= capacity <= 0x7fffffff:
+            raise ValueError(f"render_adaptive_device: a capacity of {capacity} pixels")
+        rows, width = cfg.rows(), cfg.width
+        npix = rows * width
+        dev = torch.device("cuda", torch.cuda.current_device())
+        colors = torch.zeros((rows, width, 3), dtype=torch.uint8, device=dev)
+        accum = torch.zeros((rows, width, 3), dtype=torch.float32, device=dev)
+        prev = torch.empty_like(accum)
+        rng = torch.zeros((rows, width), dtype=torch.int32, device=dev)
+        samples = torch.zeros((rows, width), dtype=torch.int32, device=dev)
+        counts = torch.zeros(len(passes) - 1, dtype=torch.int64, device=dev)
+        lists = [torch.full((capacity,), -1, dtype=torch.int32, device=dev) for _ in range(2)]
+        nbytes = select_scratch_bytes(max(npix, capacity))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        res = {"colors": colors, "accum": accum, "rng": rng, "samples": samples, "counts": counts}
+        if npix == 0:
+            return res
+        st = torch.cuda.current_stream().cuda_stream
+        self.render_samples_async(scene, cam, cfg, 0, passes[0], colors.data_ptr(), accum.data_ptr(), rng.data_ptr(), None,
+                                  st)
+        done, cur = passes[0], None  # cur: the list buffer the next pass renders (None: every pixel)
+        for k in range(1, len(passes)):
+            before, done = done, done + passes[k]
+            prev.copy_(accum)
+            if cur is None:
+                self.render_samples_async(scene, cam, cfg, before, passes[k], colors.data_ptr(), accum.data_ptr(),
+                                          rng.data_ptr(), None, st)
+            else:
+                self.render_pixels_async(scene, cam, cfg, before, passes[k], lists[cur].data_ptr(), capacity,
+                                         accum.data_ptr(), rng.data_ptr(), 0, None, flags, st)
+            last = k == len(passes) - 1
+            nxt = 0 if cur is None else 1 - cur
+            select_pixels_async(accum.data_ptr(), prev.data_ptr(), npix, None if cur is None else lists[cur].data_ptr(),
+                                0 if cur is None else capacity, select_desc(cfg.spp, before, done, threshold, floor),
+                                None if last else lists[nxt].data_ptr(), 0 if last else capacity,
+                                counts.data_ptr() + 8 * (k - 1), samples.data_ptr(), scratch.data_ptr(), nbytes, st)
+            cur = nxt
+        resolve_async(accum.data_ptr(), samples.data_ptr(), npix, cfg.spp, colors.data_ptr(), st)
+        return res
+
     @property
     def chain_wgs(self) -> int:
         """rtc_render_chain's workgroups per CU for whole frames, chosen at upload (rtc_scene_chain_wgs)."""
@@ -1119,6 +1181,141 @@ def adaptive_selection(selection, samples, done: int) -> np.ndarray:
         raise ValueError(f"render_adaptive: the selection is not a subset of the previous pass's pixels (every pixel that "
                          f"goes on has had all {done} samples)")
     return np.ascontiguousarray(sel, np.uint32)
+
+
+def select_desc(spp: int, before: int, done: int, threshold: float, floor: float) -> RtcSelectDesc:
+    """The RtcSelectDesc that compares the mean of samples [before, done) of a frame of `spp` with the mean of samples
+    [0, before) (include/rtc.h): wAccum = spp / (done - before), wPrev = wAccum + spp / before and wLevel =
+    spp / done, computed in double and rounded once to f32; samplesDone = done."""
+    spp, before, done = int(spp), int(before), int(done)
+    if not 0 < before < done or spp <= 0:
+        raise ValueError(f"select_desc: 0 < before < done and spp > 0, not before = {before}, done = {done}, spp = {spp}")
+    w_accum = spp / (done - before)
+    return RtcSelectDesc(w_accum, w_accum + spp / before, spp / done, float(floor), float(threshold), done)
+
+
+def select_scratch_bytes(n: int) -> int:
+    """rtc_select_scratch_bytes: the device scratch rtc_select_pixels_async needs for an input sequence of n entries (the
+    list's length, or the pixel count without a list)."""
+    return int(lib().rtc_select_scratch_bytes(int(n)))
+
+
+def select_pixels_async(accum_ptr: int, prev_ptr: int, pixel_count: int, in_ptr: int | None, n_in: int,
+                        sel: RtcSelectDesc, out_ptr: int | None, capacity: int, count_ptr: int | None,
+                        samples_ptr: int | None, scratch_ptr: int, scratch_bytes: int, stream: int | None = None) -> None:
+    """rtc_select_pixels_async on the current device (include/rtc.h): addresses as ints, 0 or None for a null pointer."""
+    check(lib().rtc_select_pixels_async(_vp(accum_ptr), _vp(prev_ptr), int(pixel_count), _vp(in_ptr), int(n_in),
+                                        C.byref(sel), _vp(out_ptr), int(capacity), _vp(count_ptr), _vp(samples_ptr),
+                                        _vp(scratch_ptr), int(scratch_bytes), _vp(stream)), "rtc_select_pixels_async")
+
+
+def resolve_async(accum_ptr: int, samples_ptr: int, pixel_count: int, spp: int, colors_ptr: int,
+                  stream: int | None = None) -> None:
+    """rtc_resolve_async on the current device (include/rtc.h): colors at any byte alignment."""
+    check(lib().rtc_resolve_async(_vp(accum_ptr), _vp(samples_ptr), int(pixel_count), int(spp), _vp(colors_ptr),
+                                  _vp(stream)), "rtc_resolve_async")
+
+
+def _frame_tensor(who: str, name: str, t, dev, nbytes: int, dtype=None):
+    if not hasattr(t, "data_ptr") or not t.is_cuda or t.device != dev or not t.is_contiguous() or \
+            t.numel() * t.element_size() != nbytes or (dtype is not None and t.dtype != dtype):
+        raise ValueError(f"{who}: {name} must be a contiguous tensor of {nbytes} bytes on the accumulator's device")
+    return t
+
+
+def select_pixels(accum, prev, sel: RtcSelectDesc, pixels=None, capacity: int | None = None, samples=None):
+    """The pixels of a progressive frame that go on (include/rtc.h): (out, count).  `accum` and `prev` are the
+    accumulator now and its snapshot at an earlier sample count, float32 of 3 floats per pixel; `pixels` the input list
+    (compact indices; None: every pixel; an entry >= the pixel count is skipped); `out` holds the selected entries in
+    input order, cut at `capacity` (None: the input's length) and filled up with 0xFFFFFFFF, `count` the number selected
+    before the cut; `samples` (int32, one per pixel), where given, gets sel.samplesDone IN PLACE at every valid entry.
+    Everything numpy: rtc_select_pixels_host, anywhere; out uint32 [capacity], count an int.  Everything a contiguous torch
+    tensor on one device: rtc_select_pixels_async on torch's current stream there with a torch allocation as scratch, no
+    synchronisation; out int32 [capacity] (the same bits) and count int64 [1] are device tensors."""
+    who = "select_pixels"
+    if hasattr(accum, "data_ptr"):
+        import torch
+
+        dev = accum.device
+        if accum.dtype != torch.float32 or accum.numel() % 3:
+            raise ValueError(f"{who}: accum is float32, three per pixel")
+        npix = accum.numel() // 3
+        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        _frame_tensor(who, "prev", prev, dev, 12 * npix, torch.float32)
+        if samples is not None:
+            _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
+        n_in = 0
+        if pixels is not None:
+            n_in = pixels.numel() if hasattr(pixels, "data_ptr") else -1
+            _frame_tensor(who, "pixels", pixels, dev, 4 * max(n_in, 0))
+        n = npix if pixels is None else n_in
+        capacity = n if capacity is None else int(capacity)
+        out = torch.empty(capacity, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        nbytes = select_scratch_bytes(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            select_pixels_async(accum.data_ptr(), prev.data_ptr(), npix, None if pixels is None else pixels.data_ptr(),
+                                n_in, sel, out.data_ptr() if capacity else None, capacity, count.data_ptr(),
+                                None if samples is None else samples.data_ptr(), scratch.data_ptr(), nbytes,
+                                torch.cuda.current_stream().cuda_stream)
+        return out, count
+    acc = np.ascontiguousarray(accum, np.float32).reshape(-1)
+    prv = np.ascontiguousarray(prev, np.float32).reshape(-1)
+    if acc.size % 3 or prv.size != acc.size:
+        raise ValueError(f"{who}: accum and prev are float32, three per pixel, of one frame")
+    npix = acc.size // 3
+    if samples is not None and (not isinstance(samples, np.ndarray) or samples.dtype != np.int32 or samples.size != npix
+                                or not samples.flags.c_contiguous):
+        raise ValueError(f"{who}: samples must be a contiguous int32 array of the frame's {npix} pixels")
+    px = None
+    if pixels is not None:
+        px = np.asarray(pixels).reshape(-1)
+        if px.size and (not np.issubdtype(px.dtype, np.integer) or px.min() < 0 or px.max() > 0xffffffff):
+            raise ValueError(f"{who}: pixels must be integers in [0, 2^32)")
+        px = np.ascontiguousarray(px, np.uint32)
+    n = npix if px is None else len(px)
+    capacity = n if capacity is None else int(capacity)
+    out = np.zeros(capacity, np.uint32)
+    count = C.c_ulonglong(0)
+    stand_in = np.zeros(1, np.float32)  # (an empty numpy array has no address to speak of)
+    check(lib().rtc_select_pixels_host(_ptr(acc if npix else stand_in), _ptr(prv if npix else stand_in), npix,
+                                       None if px is None else _ptr(px if len(px) else np.zeros(1, np.uint32)), n if px is not None else 0,
+                                       C.byref(sel), _ptr(out) if capacity else None, capacity,
+                                       C.cast(C.pointer(count), C.c_void_p), _ptr(samples)), "rtc_select_pixels_host")
+    return out, int(count.value)
+
+
+def resolve(accum, samples, spp: int):
+    """The displayable frame of an adaptive render (include/rtc.h): uint8 of accum's shape, floatToUint(accum * spp /
+    samples) per component (0 where samples <= 0).  numpy arrays: rtc_resolve_host, anywhere; contiguous torch tensors on
+    one device: rtc_resolve_async on torch's current stream there, no synchronisation."""
+    who = "resolve"
+    if hasattr(accum, "data_ptr"):
+        import torch
+
+        dev = accum.device
+        if accum.dtype != torch.float32 or accum.numel() % 3:
+            raise ValueError(f"{who}: accum is float32, three per pixel")
+        npix = accum.numel() // 3
+        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
+        colors = torch.empty(accum.shape, dtype=torch.uint8, device=dev)
+        if npix:
+            with torch.cuda.device(dev):
+                resolve_async(accum.data_ptr(), samples.data_ptr(), npix, spp, colors.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream)
+        return colors
+    acc = np.ascontiguousarray(accum, np.float32)
+    smp = np.ascontiguousarray(samples, np.int32)
+    if acc.size % 3 or smp.size * 3 != acc.size:
+        raise ValueError(f"{who}: accum float32, three per pixel, and samples int32, one per pixel")
+    colors = np.zeros(acc.shape, np.uint8)
+    if acc.size:
+        check(lib().rtc_resolve_host(_ptr(acc), _ptr(smp), smp.size, int(spp), _ptr(colors)), "rtc_resolve_host")
+    elif int(spp) <= 0:
+        raise ValueError(f"{who}: spp = {spp}")
+    return colors
 
 
 def save_progress(path: str, state: ProgressState) -> None:

@@ -77,6 +77,11 @@ class RtcPathDesc(C.Structure):  # rtc_trace_paths_async's sample weight, bounce
     _fields_ = [(k, C.c_int) for k in ("spp", "maxBounce", "trianglesOnly", "flags", "sampleFirst", "sampleCount")]
 
 
+class RtcSelectDesc(C.Structure):  # rtc_select_pixels_async's weights, bounds and the count it stamps (include/rtc.h)
+    _fields_ = [("wAccum", C.c_float), ("wPrev", C.c_float), ("wLevel", C.c_float), ("floor", C.c_float),
+                ("threshold", C.c_float), ("samplesDone", C.c_int)]
+
+
 class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geometry-kernel launch chose (include/rtc.h)
     _fields_ = [(k, C.c_int) for k in ("multi", "count", "hits", "general", "spheres", "resume", "chainPrimF", "wgsPerCu",
                                        "chainDyn", "clusterCount", "chunkCount", "launches")]
@@ -129,6 +134,11 @@ RTC_F_WAVE_PER_RAY = 0x20000  # trace_paths and render_pixels only: one wave per
 # workgroup counts one scan workgroup takes per step of its loop -- the sizes at which the sort takes another path
 RAY_ORDER_KEYS_PER_GROUP = 4096
 RAY_ORDER_SCAN_GROUPS = 256
+# the select's shape (rtc_select_shape): entries per workgroup (T), and the tile counts the scan workgroup
+# takes per step of its loop (G) -- the sizes at which the select takes another path
+SELECT_ENTRIES_PER_GROUP = 2048
+SELECT_SCAN_GROUPS = 256
+SELECT_SENTINEL = 0xFFFFFFFF  # the tail of a select's output list: no pixel, skipped by render_pixels
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007
@@ -186,6 +196,8 @@ EXPORTS = [
     "rtc_scene_regroup_scratch_bytes", "rtc_scene_regroup_max_tris", "rtc_scene_regroup_async", "rtc_scene_regroup",
     "rtc_regroup_membership_host", "rtc_plan_sim_regroup",
     "rtc_render_pixels_async", "rtc_render_pixels", "rtc_plan_sim_render_pixels",
+    "rtc_select_scratch_bytes", "rtc_select_shape", "rtc_select_pixels_async", "rtc_select_pixels_host",
+    "rtc_resolve_async", "rtc_resolve_host",
 ]
 
 _lib = None
@@ -345,6 +357,14 @@ def lib() -> C.CDLL:
                                         C.POINTER(RtcSampleRange), vp, sz, ip, vp, vp, vp, vp]
         L.rtc_plan_sim_render_pixels.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong,
                                                  C.c_ulonglong, C.c_ulonglong, ip, ip, vp, ip, vp, ip]
+    if hasattr(L, "rtc_select_pixels_async"):  # (absent from libraries of earlier rounds loaded for A/B timing)
+        L.rtc_select_scratch_bytes.argtypes = [sz]
+        L.rtc_select_scratch_bytes.restype = sz
+        L.rtc_select_shape.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rtc_select_pixels_async.argtypes = [vp, vp, sz, vp, sz, C.POINTER(RtcSelectDesc), vp, sz, vp, vp, vp, sz, vp]
+        L.rtc_select_pixels_host.argtypes = [vp, vp, sz, vp, sz, C.POINTER(RtcSelectDesc), vp, sz, vp, vp]
+        L.rtc_resolve_async.argtypes = [vp, vp, sz, ip, vp, vp]
+        L.rtc_resolve_host.argtypes = [vp, vp, sz, ip, vp]
     _lib = L
     return L
 
