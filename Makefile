@@ -54,12 +54,16 @@ $(BUILD)/rtc_ray_order.o: $(CSRC)/rtc_ray_order.hip $(HDRS) | $(BUILD)
 $(BUILD)/rtc_select.o: $(CSRC)/rtc_select.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
+# the edge-avoiding denoise filter; its own code object, the render kernels are untouched
+$(BUILD)/rtc_denoise.o: $(CSRC)/rtc_denoise.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
+
 # the launch planner: pure host C++ (rtc_plan.h), no HIP
 $(BUILD)/rtc_plan.o: $(CSRC)/rtc_plan.cpp $(CSRC)/rtc_plan.h $(CSRC)/rtc_regroup.h include/rtc.h | $(BUILD)
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -Wextra -c $< -o $@
 
 # the objects every library variant shares (the render kernels are rtc_render.o, or a variant of it)
-COMMON   := $(BUILD)/rtc_frame.o $(BUILD)/rtc_scene.o $(BUILD)/rtc_probe.o $(BUILD)/rtc_ray_order.o $(BUILD)/rtc_select.o $(BUILD)/rtc_plan.o $(BUILD)/scene_build.o
+COMMON   := $(BUILD)/rtc_frame.o $(BUILD)/rtc_scene.o $(BUILD)/rtc_probe.o $(BUILD)/rtc_ray_order.o $(BUILD)/rtc_select.o $(BUILD)/rtc_denoise.o $(BUILD)/rtc_plan.o $(BUILD)/scene_build.o
 
 $(LIB): $(BUILD)/rtc_render.o $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ -Wl,-soname,librtc.so -ldl -L/opt/rocm/lib -lhsa-runtime64

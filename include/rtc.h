@@ -680,6 +680,74 @@ int rtc_select_pixels_host(const float *accum, const float *prev, size_t pixelCo
 int rtc_resolve_async(const float *dAccum, const int *dSamples, size_t pixelCount, int spp, void *dColors, void *stream);
 /* The same for HOST arrays, without a GPU (rtc_quantize of the scaled accumulator). */
 int rtc_resolve_host(const float *accum, const int *samples, size_t pixelCount, int spp, void *colors);
+/* Denoise a frame on the device: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the
+ * accumulator, guided by the first-hit buffers (rtc_render_first_hit_async), with rtc_resolve_async's per-sample-count
+ * normalisation and the quantiser folded in.  The entries work on the current device (like rtc_select_pixels_async): they
+ * name no scene and take no part in the launch planner.  The image is rows * width pixels, pixel (x, y) at p = y * width
+ * + x, compact in launch-row order like dAccum.  All arithmetic is f32, operation by operation, no contraction; every
+ * division is the correctly rounded one; the device keeps subnormals, the host does too.
+ * Load.  For pixel p with A = dAccum[3 p ..]:
+ *   L_c = A_c                      without dSamples
+ *   L_c = A_c * scale              with dSamples: s = dSamples[p]; scale = s > 0 ? (float)spp / (float)s : 0.f, exactly
+ *                                  as in rtc_resolve_async
+ *   L_c = albedo_c > albedoFloor ? L_c / albedo_c : L_c      then, with RTC_DN_DEMODULATE; the test is per component and
+ *                                  false for NaN
+ * Iteration k = 0 .. iterations - 1.  Step s = 1 << k, input image C (C = L for k = 0).  The 1-D taps are
+ * H[0] = 0.375f, H[1] = 0.25f, H[2] = 0.0625f.  For the pixel at (x, y) with centre colour c, normal n and depth z:
+ *   sum_c = c_c * 0.140625f;  wsum = 0.140625f        (the centre tap is never edge-tested)
+ *   the other 24 taps in row-major order: j = -2 .. 2 outer, i = -2 .. 2 inner, skipping (0, 0)
+ *     qx = x + i s, qy = y + j s; a tap outside [0, width) x [0, rows) is skipped
+ *     w = H[|i|] * H[|j|]
+ *     normal weight, when guides->normal is given:
+ *       t = (n.x nq.x + n.y nq.y) + n.z nq.z;  t = t > 0 ? t : 0.f;  then normalSquarings times t = t * t;  w = w * t
+ *     depth weight, when guides->depth is given:
+ *       dz = (z - zq) * depthScale;  w = w / (1.f + dz * dz)
+ *     colour weight, always:
+ *       e = (|c.x - q.x| + |c.y - q.y|) + |c.z - q.z|;  w = w / (1.f + (e * e) * cs_k)
+ *       cs_k = colorScale * (float)(1 << 2k), computed on the host
+ *     if (!(w > 0)) continue;     (a NaN or zero weight never enters, so a NaN neighbour cannot spread; a pixel's own NaN
+ *                                  stays)
+ *     sum_c = sum_c + q_c * w;  wsum = wsum + w
+ *   C'_c = sum_c / wsum
+ * Store.  After the last iteration: O_c = albedo_c > albedoFloor ? C'_c * albedo_c : C'_c with RTC_DN_DEMODULATE, else
+ * O_c = C'_c; dOut[3 p + c] = O_c; where dColors is given, byte 3 p + c of it = floatToUint(O_c) (moremath.c:25-30; NaN
+ * gives 0, as rtc_quantize), at any byte alignment of dColors, exactly 3 * width * rows bytes, as rtc_resolve_async.
+ * Miss pixels.  A first-hit miss has the normal +0, +0, +0 and the depth 999999.f: wherever normals are given it gives
+ * and takes the weight 0 (t = 0), so it comes out as c * w0 / w0 with w0 = 0.140625f, its own colour up to that rounding.
+ * guides: nullable, and each member nullable (no weight of that kind); prim is ignored.  dSamples: nullable.
+ * dScratch: rtc_denoise_scratch_bytes(width * rows, iterations) bytes of device memory, 16-byte aligned; all temporary
+ * storage: a pack pass performs the load step into 16-byte entries (colour rgb + pad; normal.xyz + depth), so that every
+ * tap is two 16-byte loads, and the intermediate images alternate between two such colour images.  An iteration is one
+ * kernel: at steps 1 and 2 a workgroup stages a tileW x tileH tile of the image plus a halo of 2 s in LDS and takes the
+ * taps from there, from step 4 on every tap is loaded from global memory; either way a pixel's taps are summed in the
+ * order above, in registers.  No atomics: the result is a function of the inputs alone.
+ * Asynchronous on `stream`, complete there: no allocation, no synchronisation, no host read of device memory; nothing is
+ * written outside dOut[0, 3 n), the 3 n bytes of dColors (n = width * rows) and the scratch's stated size; the
+ * accumulator, the samples and the guides are only read.
+ * RTC_EINVAL, checked before any device call: a null dAccum, d or dOut; width or rows <= 0; width * rows > 0x7fffffff;
+ * iterations outside 1 .. 6; normalSquarings outside 0 .. 8; a flag other than RTC_DN_DEMODULATE; RTC_DN_DEMODULATE
+ * without guides->albedo; dSamples given with spp <= 0; dOut == dAccum; dScratch null, not 16-byte aligned or
+ * scratchBytes too small. */
+#define RTC_DN_DEMODULATE 0x1
+typedef struct RtcDenoiseDesc {
+    int width, rows;        /* the image: rows * width pixels, compact launch-row order, like dAccum */
+    int iterations;         /* 1 .. 6: iteration k = 0.. uses step s = 1 << k */
+    int flags;              /* 0 or RTC_DN_DEMODULATE (needs guides->albedo) */
+    int spp;                /* with dSamples: the frame's spp, as rtc_resolve_async; otherwise ignored */
+    int normalSquarings;    /* 0 .. 8: the normal weight is max(0, n.nq) ^ (2 ^ normalSquarings) */
+    float depthScale, colorScale, albedoFloor; /* host floats, the caller's */
+} RtcDenoiseDesc;
+size_t rtc_denoise_scratch_bytes(size_t pixelCount, int iterations); /* a multiple of 16, monotone in both */
+/* The filter's shape (host only): the image tile a workgroup stages at steps 1 and 2 -- width or rows = tile +- 1 and
+ * 2 tile + 1 are the sizes at which the kernels take another path (from step 4 on a workgroup takes tileW x 8 pixels). */
+int rtc_denoise_shape(int *tileW, int *tileH);
+int rtc_denoise_async(const float *dAccum, const int *dSamples /* nullable */, const RtcHitBuffers *guides /* nullable */,
+                      const RtcDenoiseDesc *d, float *dOut, void *dColors /* nullable */, void *dScratch,
+                      size_t scratchBytes, void *stream);
+/* The same statement for HOST arrays in plain C++, without a GPU and without scratch: what the device's dOut and dColors
+ * are compared with, byte for byte.  The same refusals (but the scratch's); RTC_ENOMEM when its own images do not fit. */
+int rtc_denoise_host(const float *accum, const int *samples, const RtcHitBuffers *guides, const RtcDenoiseDesc *d,
+                     float *out, void *colors);
 /* Copy `bytes` (16-byte aligned pointers) on `stream` with `blocks` workgroups (<= 0: 32): e.g. Color[] from HBM
  * into pinned host memory with a small CU footprint while render kernels run (the runtime's D2H blit kernel
  * takes one workgroup on every CU).  Asynchronous. */

@@ -37,6 +37,7 @@ from ._abi import (  # noqa: F401
     RTC_F_NO_REORDER,
     RTC_F_NO_TILE_CULL,
     RTC_F_WAVE_PER_RAY,
+    RTC_DN_DEMODULATE,
     RTC_SEGMENT_COUNTERS,
     RTC_EBUSY,
     RTC_EINVAL,
@@ -49,6 +50,7 @@ from ._abi import (  # noqa: F401
     Ray,
     RtcCamera,
     RtcChainReport,
+    RtcDenoiseDesc,
     RtcError,
     RtcHitBuffers,
     RtcLoopStats,
@@ -72,6 +74,7 @@ __all__ = [
     "ray_keys_host", "ray_order_scratch_bytes", "gather_async", "scatter_async",
     "regroup_membership_host", "regroup_max_tris", "adaptive_selection",
     "select_desc", "select_pixels", "select_pixels_async", "select_scratch_bytes", "resolve", "resolve_async",
+    "denoise_desc", "denoise_scratch_bytes", "denoise_async", "denoise",
 ]
 
 # main.c:114-116 (camera) and main.c:10-12 (frame) defaults
@@ -1316,6 +1319,102 @@ def resolve(accum, samples, spp: int):
     elif int(spp) <= 0:
         raise ValueError(f"{who}: spp = {spp}")
     return colors
+
+
+def denoise_desc(width: int, rows: int, iterations: int = 5, normal_squarings: int = 5, depth_scale: float = 1.0,
+                 color_scale: float = 1.0, albedo_floor: float = 0.0, demodulate: bool = False,
+                 spp: int = 0) -> RtcDenoiseDesc:
+    """The RtcDenoiseDesc of a rows x width frame (include/rtc.h): `iterations` a-trous iterations (steps 1,
+    2, 4, ...), the normal weight max(0, n.nq) ^ (2 ^ normal_squarings), the depth weight 1 / (1 + ((z - zq) *
+    depth_scale)^2), the colour weight 1 / (1 + e^2 * color_scale * 4^k) with e the L1 colour distance; demodulate:
+    RTC_DN_DEMODULATE (the colour is divided by the albedo where that exceeds albedo_floor, filtered, and multiplied
+    again).  The three floats are rounded to f32 once; spp counts only with per-pixel sample counts."""
+    return RtcDenoiseDesc(int(width), int(rows), int(iterations), RTC_DN_DEMODULATE if demodulate else 0, int(spp),
+                          int(normal_squarings), float(depth_scale), float(color_scale), float(albedo_floor))
+
+
+def denoise_scratch_bytes(n: int, iterations: int) -> int:
+    """rtc_denoise_scratch_bytes: the device scratch rtc_denoise_async needs for n pixels and `iterations` iterations."""
+    return int(lib().rtc_denoise_scratch_bytes(int(n), int(iterations)))
+
+
+def denoise_async(accum_ptr: int, samples_ptr: int | None, desc: RtcDenoiseDesc, out_ptr: int, colors_ptr: int | None,
+                  scratch_ptr: int, scratch_bytes: int, normal_ptr: int | None = None, depth_ptr: int | None = None,
+                  albedo_ptr: int | None = None, stream: int | None = None) -> None:
+    """rtc_denoise_async on the current device (include/rtc.h): addresses as ints, 0 or None for a null pointer."""
+    guides = RtcHitBuffers(None, depth_ptr or None, normal_ptr or None, albedo_ptr or None)
+    check(lib().rtc_denoise_async(_vp(accum_ptr), _vp(samples_ptr), C.byref(guides), C.byref(desc), _vp(out_ptr),
+                                  _vp(colors_ptr), _vp(scratch_ptr), int(scratch_bytes), _vp(stream)), "rtc_denoise_async")
+
+
+_GUIDE_FLOATS = {"normal": 3, "depth": 1, "albedo": 3}
+
+
+def denoise(accum, guides=None, samples=None, spp=None, desc: RtcDenoiseDesc | None = None, colors: bool = False):
+    """A frame's accumulator through the edge-avoiding a-trous filter (include/rtc.h): float32 of accum's
+    shape, or (that, uint8 of accum's shape: floatToUint of it) with colors=True.  `accum`: float32 [rows, W, 3]; `guides`:
+    the dict DeviceScene.first_hit returns or its device tensors -- "normal", "depth" and "albedo" are used where present
+    (albedo only with a demodulating desc), "prim" is ignored; `samples` (int32 [rows, W]) and `spp`: the per-pixel sample
+    counts and the frame's spp of an adaptive render (DeviceScene.render_adaptive_device), so that every pixel is scaled by
+    spp / samples first; `desc`: denoise_desc(...) for accum's width and rows (None: denoise_desc(W, rows)).
+    Everything numpy: rtc_denoise_host, anywhere, no GPU.  Everything a contiguous torch tensor on one device:
+    rtc_denoise_async on torch's current stream there with a torch allocation as scratch, no synchronisation."""
+    who = "denoise"
+    on_device = hasattr(accum, "data_ptr")
+    shape = tuple(accum.shape)
+    if len(shape) != 3 or shape[2] != 3 or shape[0] <= 0 or shape[1] <= 0:
+        raise ValueError(f"{who}: accum is float32 [rows, W, 3], not {shape}")
+    rows, width = shape[0], shape[1]
+    npix = rows * width
+    if desc is None:
+        desc = denoise_desc(width, rows)
+    if (desc.width, desc.rows) != (width, rows):
+        raise ValueError(f"{who}: the desc is for {desc.width} x {desc.rows}, accum for {width} x {rows}")
+    if (samples is None) != (spp is None):
+        raise ValueError(f"{who}: samples and spp go together")
+    d = RtcDenoiseDesc.from_buffer_copy(desc)
+    if spp is not None:
+        d.spp = int(spp)
+    guides = {k: v for k, v in (guides or {}).items() if k in _GUIDE_FLOATS and v is not None}
+    if not d.flags & RTC_DN_DEMODULATE:
+        guides.pop("albedo", None)
+    if on_device:
+        import torch
+
+        dev = accum.device
+        if accum.dtype != torch.float32:
+            raise ValueError(f"{who}: accum is float32")
+        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        if samples is not None:
+            _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
+        for k, v in guides.items():
+            _frame_tensor(who, k, v, dev, 4 * _GUIDE_FLOATS[k] * npix, torch.float32)
+        out = torch.empty_like(accum)
+        col = torch.empty(shape, dtype=torch.uint8, device=dev) if colors else None
+        nbytes = denoise_scratch_bytes(npix, d.iterations)
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            denoise_async(accum.data_ptr(), None if samples is None else samples.data_ptr(), d, out.data_ptr(),
+                          None if col is None else col.data_ptr(), scratch.data_ptr(), nbytes,
+                          **{k + "_ptr": v.data_ptr() for k, v in guides.items()},
+                          stream=torch.cuda.current_stream().cuda_stream)
+        return (out, col) if colors else out
+    acc = np.ascontiguousarray(accum, np.float32)
+    smp = None
+    if samples is not None:
+        smp = np.ascontiguousarray(samples, np.int32)
+        if smp.size != npix:
+            raise ValueError(f"{who}: samples is int32, one per pixel")
+    held = {}
+    for k, v in guides.items():
+        held[k] = np.ascontiguousarray(v, np.float32)
+        if held[k].size != _GUIDE_FLOATS[k] * npix:
+            raise ValueError(f"{who}: guides[{k!r}] has {held[k].size} floats for {npix} pixels")
+    hb = RtcHitBuffers(None, _ptr(held.get("depth")), _ptr(held.get("normal")), _ptr(held.get("albedo")))
+    out = np.zeros(shape, np.float32)
+    col = np.zeros(shape, np.uint8) if colors else None
+    check(lib().rtc_denoise_host(_ptr(acc), _ptr(smp), C.byref(hb), C.byref(d), _ptr(out), _ptr(col)), "rtc_denoise_host")
+    return (out, col) if colors else out
 
 
 def save_progress(path: str, state: ProgressState) -> None:

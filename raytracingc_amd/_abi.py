@@ -82,6 +82,12 @@ class RtcSelectDesc(C.Structure):  # rtc_select_pixels_async's weights, bounds a
                 ("threshold", C.c_float), ("samplesDone", C.c_int)]
 
 
+class RtcDenoiseDesc(C.Structure):  # rtc_denoise_async's image, iterations and edge weights (include/rtc.h)
+    _fields_ = [("width", C.c_int), ("rows", C.c_int), ("iterations", C.c_int), ("flags", C.c_int), ("spp", C.c_int),
+                ("normalSquarings", C.c_int), ("depthScale", C.c_float), ("colorScale", C.c_float),
+                ("albedoFloor", C.c_float)]
+
+
 class RtcChainReport(C.Structure):  # rtc_scene_chain_report: what the last geometry-kernel launch chose (include/rtc.h)
     _fields_ = [(k, C.c_int) for k in ("multi", "count", "hits", "general", "spheres", "resume", "chainPrimF", "wgsPerCu",
                                        "chainDyn", "clusterCount", "chunkCount", "launches")]
@@ -139,6 +145,11 @@ RAY_ORDER_SCAN_GROUPS = 256
 SELECT_ENTRIES_PER_GROUP = 2048
 SELECT_SCAN_GROUPS = 256
 SELECT_SENTINEL = 0xFFFFFFFF  # the tail of a select's output list: no pixel, skipped by render_pixels
+# the denoise filter's shape (rtc_denoise_shape): the image tile a workgroup stages at steps 1 and 2 -- the
+# sizes at which the iteration kernels take another path
+DENOISE_TILE_W = 32
+DENOISE_TILE_H = 32
+RTC_DN_DEMODULATE = 0x1
 RTC_SEGMENT_COUNTERS = 5  # u64 counters rtc_render_rows_async adds to (include/rtc.h)
 RTC_EINVAL, RTC_ENODEV, RTC_EIO, RTC_ENOMEM, RTC_EFORMAT = -10001, -10002, -10003, -10004, -10005
 RTC_ETIMEDOUT, RTC_EBUSY = -10006, -10007
@@ -198,6 +209,7 @@ EXPORTS = [
     "rtc_render_pixels_async", "rtc_render_pixels", "rtc_plan_sim_render_pixels",
     "rtc_select_scratch_bytes", "rtc_select_shape", "rtc_select_pixels_async", "rtc_select_pixels_host",
     "rtc_resolve_async", "rtc_resolve_host",
+    "rtc_denoise_scratch_bytes", "rtc_denoise_shape", "rtc_denoise_async", "rtc_denoise_host",
 ]
 
 _lib = None
@@ -365,6 +377,12 @@ def lib() -> C.CDLL:
         L.rtc_select_pixels_host.argtypes = [vp, vp, sz, vp, sz, C.POINTER(RtcSelectDesc), vp, sz, vp, vp]
         L.rtc_resolve_async.argtypes = [vp, vp, sz, ip, vp, vp]
         L.rtc_resolve_host.argtypes = [vp, vp, sz, ip, vp]
+    if hasattr(L, "rtc_denoise_async"):
+        L.rtc_denoise_scratch_bytes.argtypes = [sz, ip]
+        L.rtc_denoise_scratch_bytes.restype = sz
+        L.rtc_denoise_shape.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rtc_denoise_async.argtypes = [vp, vp, C.POINTER(RtcHitBuffers), C.POINTER(RtcDenoiseDesc), vp, vp, vp, sz, vp]
+        L.rtc_denoise_host.argtypes = [vp, vp, C.POINTER(RtcHitBuffers), C.POINTER(RtcDenoiseDesc), vp, vp]
     _lib = L
     return L
 
