@@ -31,31 +31,12 @@ $(BUILD)/scene_build.o: $(CSRC)/scene_build.c $(CSRC)/rtc_internal.h include/rtc
 
 # header dependencies: explicit below, and generated (-MMD) for anything the explicit lists miss
 HDRS     := $(CSRC)/rtc_params.h $(CSRC)/rtc_closest.h $(CSRC)/rtc_diag.h $(CSRC)/rtc_cull.h $(CSRC)/rtc_lane.h $(CSRC)/rtc_sky.h $(CSRC)/rtc_chain.h $(CSRC)/rtc_first_hit.h $(CSRC)/rtc_trace_rays.h $(CSRC)/rtc_trace_paths.h $(CSRC)/rtc_occluded.h $(CSRC)/rtc_render_pixels.h \
-            $(CSRC)/rtc_layout.h $(CSRC)/rtc_plan.h $(CSRC)/rtc_device.h $(CSRC)/rtc_math.h $(CSRC)/rtc_bm_tables.h $(CSRC)/rtc_hip_util.h $(CSRC)/rtc_staged.h $(CSRC)/rtc_regroup.h $(CSRC)/rtc_records.h $(CSRC)/rtc_internal.h include/rtc.h
+            $(CSRC)/rtc_layout.h $(CSRC)/rtc_plan.h $(CSRC)/rtc_device.h $(CSRC)/rtc_math.h $(CSRC)/rtc_bm_tables.h $(CSRC)/rtc_hip_util.h $(CSRC)/rtc_pass_util.h $(CSRC)/rtc_staged.h $(CSRC)/rtc_regroup.h $(CSRC)/rtc_records.h $(CSRC)/rtc_internal.h include/rtc.h
 -include $(wildcard $(BUILD)/*.d)
 
-$(BUILD)/rtc_render.o: $(CSRC)/rtc_render.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-$(BUILD)/rtc_frame.o: $(CSRC)/rtc_frame.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-$(BUILD)/rtc_scene.o: $(CSRC)/rtc_scene.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-$(BUILD)/rtc_probe.o: $(CSRC)/rtc_probe.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-# the ray order: key, radix sort, gather / scatter; its own code object, the render kernels are untouched
-$(BUILD)/rtc_ray_order.o: $(CSRC)/rtc_ray_order.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-# the adaptive frame's select and resolve; its own code object, the render kernels are untouched
-$(BUILD)/rtc_select.o: $(CSRC)/rtc_select.hip $(HDRS) | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
-
-# the edge-avoiding denoise filter; its own code object, the render kernels are untouched
-$(BUILD)/rtc_denoise.o: $(CSRC)/rtc_denoise.hip $(HDRS) | $(BUILD)
+# One code object per HIP unit.  The ray order, the adaptive frame's select and resolve (§3.20) and the
+# denoise filter (§3.21) are units of their own so that the render kernels (rtc_render.hip) stay untouched by them.
+$(BUILD)/%.o: $(CSRC)/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
 # the launch planner: pure host C++ (rtc_plan.h), no HIP

@@ -227,15 +227,41 @@ def _query_rays(who: str, rays):
 
 
 @contextlib.contextmanager
-def _current_stream_of(device):
-    """`device` made torch's current one: yields its current stream there (the hipStream_t as an int) and synchronises
-    that stream once the block has enqueued its work."""
+def _stream_of(device):
+    """`device` made torch's current one: yields its current stream there (the torch stream; .cuda_stream is the
+    hipStream_t as an int).  Nothing is synchronised."""
     import torch
 
     with torch.cuda.device(device):
-        st = torch.cuda.current_stream()
+        yield torch.cuda.current_stream()
+
+
+@contextlib.contextmanager
+def _current_stream_of(device):
+    """_stream_of(device), yielding the hipStream_t as an int, and that stream synchronised once the block has enqueued
+    its work."""
+    with _stream_of(device) as st:
         yield st.cuda_stream
         st.synchronize()
+
+
+def _six_bounds(who: str, bounds):
+    """A ray order's `bounds` as float32 [6] (lo, hi), or None for None (the scene's)."""
+    if bounds is None:
+        return None
+    b = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in bounds]), np.float32)
+    if b.size != 6:
+        raise ValueError(f"{who}: bounds are (lo, hi): six floats")
+    return b
+
+
+def _adaptive_passes(who: str, passes, spp: int, least: int) -> list:
+    """An adaptive frame's `passes` as ints: at least `least` (1 or 2) positive counts summing to at most spp."""
+    passes = [int(c) for c in passes]
+    if len(passes) < least or any(c <= 0 for c in passes) or sum(passes) > spp:
+        raise ValueError(f"{who}: passes {passes} are not {'two or more ' if least == 2 else ''}positive counts summing "
+                         f"to at most spp = {spp}")
+    return passes
 
 
 def _host_order(who: str, order, n: int) -> np.ndarray:
@@ -673,10 +699,7 @@ class DeviceScene:
         where wanted, the keys in input order into keys_ptr (uint32 [n]).  scratch_ptr: ray_order_scratch_bytes(n) bytes
         of device memory, 16-byte aligned.  bounds: None (the scene's, bounds()) or (lo, hi) / six floats, on the host.
         Asynchronous on `stream`, complete there; nothing of the scene's state is touched."""
-        b = None if bounds is None else np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(-1)
-                                                                             for v in bounds]), np.float32)
-        if b is not None and b.size != 6:
-            raise ValueError("DeviceScene.ray_order_async: bounds are (lo, hi): six floats")
+        b = _six_bounds("DeviceScene.ray_order_async", bounds)
         check(lib().rtc_ray_order_async(self._h, _vp(rays_ptr), n, _ptr(b), _vp(order_ptr), _vp(keys_ptr),
                                         _vp(scratch_ptr), scratch_bytes, _vp(stream)), "rtc_ray_order_async")
 
@@ -687,10 +710,7 @@ class DeviceScene:
         the scene's device is sorted in place of residence on torch's current stream there and gives int32 tensors on that
         device.  Pass the result as `order=` to trace_rays, trace_paths or occluded."""
         on_device, a, n = _query_rays("DeviceScene.ray_order", rays)
-        b = None if bounds is None else np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(-1)
-                                                                             for v in bounds]), np.float32)
-        if b is not None and b.size != 6:
-            raise ValueError("DeviceScene.ray_order: bounds are (lo, hi): six floats")
+        b = _six_bounds("DeviceScene.ray_order", bounds)
         if on_device:
             import torch
 
@@ -698,7 +718,7 @@ class DeviceScene:
             kt = torch.zeros(n, dtype=torch.int32, device=rays.device) if keys else None
             if n:
                 nbytes = ray_order_scratch_bytes(n)
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=rays.device)
+                scratch = _scratch(nbytes, rays.device)
                 with _current_stream_of(rays.device) as st:
                     self.ray_order_async(rays.data_ptr(), n, order.data_ptr(), scratch.data_ptr(), nbytes, b,
                                          kt.data_ptr() if keys else 0, stream=st)
@@ -844,9 +864,7 @@ class DeviceScene:
         accum * spp / samples.  Stop iterating to cancel."""
         import torch
 
-        passes = [int(c) for c in passes]
-        if not passes or any(c <= 0 for c in passes) or sum(passes) > cfg.spp:
-            raise ValueError(f"render_adaptive: passes {passes} are not positive counts summing to at most spp = {cfg.spp}")
+        passes = _adaptive_passes("render_adaptive", passes, cfg.spp, 1)
         rows = cfg.rows()
         colors = torch.zeros((rows, cfg.width, 3), dtype=torch.uint8, device="cuda")
         accum = torch.zeros((rows, cfg.width, 3), dtype=torch.float32, device="cuda")
@@ -887,11 +905,8 @@ class DeviceScene:
         the stream is."""
         import torch
 
-        passes = [int(c) for c in passes]
+        passes = _adaptive_passes("render_adaptive_device", passes, cfg.spp, 2)
         capacity = int(capacity)
-        if len(passes) < 2 or any(c <= 0 for c in passes) or sum(passes) > cfg.spp:
-            raise ValueError(f"render_adaptive_device: passes {passes} are not two or more positive counts summing to at "
-                             f"most spp = {cfg.spp}")
         if not 1 <= capacity <= 0x7fffffff:
             raise ValueError(f"render_adaptive_device: a capacity of {capacity} pixels")
         rows, width = cfg.rows(), cfg.width
@@ -905,7 +920,7 @@ class DeviceScene:
         counts = torch.zeros(len(passes) - 1, dtype=torch.int64, device=dev)
         lists = [torch.full((capacity,), -1, dtype=torch.int32, device=dev) for _ in range(2)]
         nbytes = select_scratch_bytes(max(npix, capacity))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _scratch(nbytes, dev)
         res = {"colors": colors, "accum": accum, "rng": rng, "samples": samples, "counts": counts}
         if npix == 0:
             return res
@@ -1226,6 +1241,25 @@ def _frame_tensor(who: str, name: str, t, dev, nbytes: int, dtype=None):
     return t
 
 
+def _accum_pixels(who: str, accum, what: str = "accum is float32, three per pixel") -> int:
+    """A device accumulator's pixel count: a contiguous float32 tensor of three floats per pixel (`what`: the refusal of
+    another type or size)."""
+    import torch
+
+    if accum.dtype != torch.float32 or accum.numel() % 3:
+        raise ValueError(f"{who}: {what}")
+    npix = accum.numel() // 3
+    _frame_tensor(who, "accum", accum, accum.device, 12 * npix)
+    return npix
+
+
+def _scratch(nbytes: int, dev):
+    """A torch allocation of at least nbytes (and at least 16: an empty tensor has no address) bytes on `dev`."""
+    import torch
+
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
 def select_pixels(accum, prev, sel: RtcSelectDesc, pixels=None, capacity: int | None = None, samples=None):
     """The pixels of a progressive frame that go on (include/rtc.h): (out, count).  `accum` and `prev` are the
     accumulator now and its snapshot at an earlier sample count, float32 of 3 floats per pixel; `pixels` the input list
@@ -1240,10 +1274,7 @@ def select_pixels(accum, prev, sel: RtcSelectDesc, pixels=None, capacity: int | 
         import torch
 
         dev = accum.device
-        if accum.dtype != torch.float32 or accum.numel() % 3:
-            raise ValueError(f"{who}: accum is float32, three per pixel")
-        npix = accum.numel() // 3
-        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        npix = _accum_pixels(who, accum)
         _frame_tensor(who, "prev", prev, dev, 12 * npix, torch.float32)
         if samples is not None:
             _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
@@ -1256,12 +1287,12 @@ def select_pixels(accum, prev, sel: RtcSelectDesc, pixels=None, capacity: int | 
         out = torch.empty(capacity, dtype=torch.int32, device=dev)
         count = torch.zeros(1, dtype=torch.int64, device=dev)
         nbytes = select_scratch_bytes(n)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+        scratch = _scratch(nbytes, dev)
+        with _stream_of(dev) as st:
             select_pixels_async(accum.data_ptr(), prev.data_ptr(), npix, None if pixels is None else pixels.data_ptr(),
                                 n_in, sel, out.data_ptr() if capacity else None, capacity, count.data_ptr(),
                                 None if samples is None else samples.data_ptr(), scratch.data_ptr(), nbytes,
-                                torch.cuda.current_stream().cuda_stream)
+                                st.cuda_stream)
         return out, count
     acc = np.ascontiguousarray(accum, np.float32).reshape(-1)
     prv = np.ascontiguousarray(prev, np.float32).reshape(-1)
@@ -1298,16 +1329,12 @@ def resolve(accum, samples, spp: int):
         import torch
 
         dev = accum.device
-        if accum.dtype != torch.float32 or accum.numel() % 3:
-            raise ValueError(f"{who}: accum is float32, three per pixel")
-        npix = accum.numel() // 3
-        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        npix = _accum_pixels(who, accum)
         _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
         colors = torch.empty(accum.shape, dtype=torch.uint8, device=dev)
         if npix:
-            with torch.cuda.device(dev):
-                resolve_async(accum.data_ptr(), samples.data_ptr(), npix, spp, colors.data_ptr(),
-                              torch.cuda.current_stream().cuda_stream)
+            with _stream_of(dev) as st:
+                resolve_async(accum.data_ptr(), samples.data_ptr(), npix, spp, colors.data_ptr(), st.cuda_stream)
         return colors
     acc = np.ascontiguousarray(accum, np.float32)
     smp = np.ascontiguousarray(samples, np.int32)
@@ -1382,9 +1409,7 @@ def denoise(accum, guides=None, samples=None, spp=None, desc: RtcDenoiseDesc | N
         import torch
 
         dev = accum.device
-        if accum.dtype != torch.float32:
-            raise ValueError(f"{who}: accum is float32")
-        _frame_tensor(who, "accum", accum, dev, 12 * npix)
+        _accum_pixels(who, accum, "accum is float32")
         if samples is not None:
             _frame_tensor(who, "samples", samples, dev, 4 * npix, torch.int32)
         for k, v in guides.items():
@@ -1392,12 +1417,11 @@ def denoise(accum, guides=None, samples=None, spp=None, desc: RtcDenoiseDesc | N
         out = torch.empty_like(accum)
         col = torch.empty(shape, dtype=torch.uint8, device=dev) if colors else None
         nbytes = denoise_scratch_bytes(npix, d.iterations)
-        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+        scratch = _scratch(nbytes, dev)
+        with _stream_of(dev) as st:
             denoise_async(accum.data_ptr(), None if samples is None else samples.data_ptr(), d, out.data_ptr(),
                           None if col is None else col.data_ptr(), scratch.data_ptr(), nbytes,
-                          **{k + "_ptr": v.data_ptr() for k, v in guides.items()},
-                          stream=torch.cuda.current_stream().cuda_stream)
+                          **{k + "_ptr": v.data_ptr() for k, v in guides.items()}, stream=st.cuda_stream)
         return (out, col) if colors else out
     acc = np.ascontiguousarray(accum, np.float32)
     smp = None

@@ -15,6 +15,7 @@
 #include "rtc_device.h"
 #include "rtc_internal.h"
 #include "rtc_hip_util.h"
+#include "rtc_pass_util.h"
 
 /* ---- the filter's shape (rtc_denoise_shape gives the tile; raytracingc_amd/_abi.py mirrors it as constants and
  * tests/test_denoise_abi.py compares the two) ---- */
@@ -32,18 +33,13 @@ struct DnWeights {
 
 /* ---- the statement.  f32 operation by operation (the translation unit is built with -ffp-contract=off); every
  * division is the correctly rounded one on both sides; subnormals are kept on both sides. ---- */
-__host__ __device__ inline float denoise_scale(float fspp, int s)
-{
-    return s > 0 ? fspp / (float)s : 0.f; /* rtc_resolve_async's scale */
-}
-
-/* Load: pixel p's colour entry (rgb, pad) */
+/* Load: pixel p's colour entry (rgb, pad), scaled as rtc_resolve_async scales it */
 __host__ __device__ inline float4 denoise_load(const float *accum, const int *samples, const float *albedo, size_t p,
                                                float fspp, float albedoFloor)
 {
     float L[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
     if (samples) {
-        const float scale = denoise_scale(fspp, samples[p]);
+        const float scale = rtc_sample_scale(fspp, samples[p]);
         for (int c = 0; c < 3; ++c)
             L[c] = L[c] * scale;
     }
@@ -226,13 +222,13 @@ __global__ __launch_bounds__(kDnBlock) void rtc_denoise_iter_tile(const float4 *
     }
 }
 
-/* the images in global memory as denoise_pixel sees them from pixel p */
+/* the images in memory (the device's, or rtc_denoise_host's) as denoise_pixel sees them from pixel p */
 struct DnGlobalAt {
     const float4 *color_, *guide_; /* the centre's entries */
     long long pitch;
     int s;
-    __device__ float4 color(int i, int j) const { return color_[j * s * pitch + i * s]; }
-    __device__ float4 guide(int i, int j) const { return guide_[j * s * pitch + i * s]; }
+    __host__ __device__ float4 color(int i, int j) const { return color_[j * s * pitch + i * s]; }
+    __host__ __device__ float4 guide(int i, int j) const { return guide_[j * s * pitch + i * s]; }
 };
 
 /* An iteration with step s >= 4, where a halo of 2 s would outweigh the tile: every tap is two dwordx4 loads from global
@@ -301,6 +297,18 @@ static DnWeights denoise_weights(const RtcDenoiseDesc *d, const RtcHitBuffers *g
     return w;
 }
 
+/* what a run works on: the guides it uses (albedo: only when demodulating) and, in `base`'s 3 n entries, the guide entries
+ * and the two colour images (image[1]: only with two or more iterations) */
+struct DnBuffers {
+    const float *normal, *depth, *albedo;
+    float4 *guide, *image[2];
+};
+static DnBuffers denoise_buffers(const RtcHitBuffers *guides, const RtcDenoiseDesc *d, float4 *base, size_t n)
+{
+    return {guides ? guides->normal : nullptr, guides ? guides->depth : nullptr,
+            (d->flags & RTC_DN_DEMODULATE) ? guides->albedo : nullptr, base, {base + n, base + 2 * n}};
+}
+
 extern "C" int rtc_denoise_shape(int *tileW, int *tileH)
 {
     if (!tileW || !tileH)
@@ -323,58 +331,39 @@ extern "C" int rtc_denoise_async(const float *dAccum, const int *dSamples, const
     if (const int rc = refuse_denoise(who, dAccum, dSamples, guides, d, dOut))
         return rc;
     const size_t n = (size_t)d->width * (size_t)d->rows;
-    if (!dScratch)
-        return rtc_fail(RTC_EINVAL, "%s: null scratch", who);
-    if (((size_t)dScratch & 15) != 0)
-        return rtc_fail(RTC_EINVAL, "%s: the scratch must be 16-byte aligned", who);
+    if (const int rc = rtc_refuse_scratch(who, dScratch))
+        return rc;
     if (scratchBytes < rtc_denoise_scratch_bytes(n, d->iterations))
         return rtc_fail(RTC_EINVAL, "%s: %zu bytes of scratch, %zu pixels and %d iterations need %zu "
                         "(rtc_denoise_scratch_bytes)", who, scratchBytes, n, d->iterations,
                         rtc_denoise_scratch_bytes(n, d->iterations));
     const hipStream_t st = (hipStream_t)stream;
-    const float *const normal = guides ? guides->normal : nullptr, *const depth = guides ? guides->depth : nullptr;
-    const float *const albedo = (d->flags & RTC_DN_DEMODULATE) ? guides->albedo : nullptr;
-    float4 *const guide = (float4 *)dScratch;
-    float4 *image[2] = {guide + n, guide + 2 * n}; /* (image[1]: only with two or more iterations) */
+    const DnBuffers b = denoise_buffers(guides, d, (float4 *)dScratch, n);
     const dim3 block(kDnBlock);
     hipLaunchKernelGGL(rtc_denoise_pack, dim3((unsigned)((n + kDnBlock - 1) / kDnBlock)), block, 0, st, dAccum, dSamples,
-                       normal, depth, albedo, (unsigned)n, (float)d->spp, d->albedoFloor, image[0], guide);
+                       b.normal, b.depth, b.albedo, (unsigned)n, (float)d->spp, d->albedoFloor, b.image[0], b.guide);
     for (int k = 0; k < d->iterations; ++k) {
         const int s = 1 << k;
         const DnWeights w = denoise_weights(d, guides, k);
         const bool last = k + 1 == d->iterations;
-        const float4 *const in = image[k & 1];
-        float4 *const next = last ? (float4 *)nullptr : image[(k + 1) & 1];
+        const float4 *const in = b.image[k & 1];
+        float4 *const next = last ? (float4 *)nullptr : b.image[(k + 1) & 1];
         unsigned char *const col = (unsigned char *)dColors;
         const unsigned tilesX = (unsigned)((d->width + kDnTile - 1) / kDnTile);
         const int tileRows = s <= 2 ? kDnTile : kDnDirectRows;
         const dim3 grid(tilesX * (unsigned)((d->rows + tileRows - 1) / tileRows)); /* (<= n / 256 + width + rows: < 2^31) */
-#define DN_TILE(LAST, S) hipLaunchKernelGGL((rtc_denoise_iter_tile<LAST, S>), grid, block, 0, st, in, guide, d->width, \
-                                            d->rows, tilesX, w, next, albedo, d->albedoFloor, dOut, col)
-#define DN_DIRECT(LAST) hipLaunchKernelGGL(rtc_denoise_iter_direct<LAST>, grid, block, 0, st, in, guide, d->width, \
-                                           d->rows, s, tilesX, w, next, albedo, d->albedoFloor, dOut, col)
-        if (s == 1) {
-            if (last) DN_TILE(true, 1); else DN_TILE(false, 1);
-        } else if (s == 2) {
-            if (last) DN_TILE(true, 2); else DN_TILE(false, 2);
-        } else {
-            if (last) DN_DIRECT(true); else DN_DIRECT(false);
-        }
-#undef DN_TILE
-#undef DN_DIRECT
+        if (s <= 2) {
+            const auto tile = s == 1 ? (last ? rtc_denoise_iter_tile<true, 1> : rtc_denoise_iter_tile<false, 1>)
+                                     : (last ? rtc_denoise_iter_tile<true, 2> : rtc_denoise_iter_tile<false, 2>);
+            hipLaunchKernelGGL(tile, grid, block, 0, st, in, b.guide, d->width, d->rows, tilesX, w, next, b.albedo,
+                               d->albedoFloor, dOut, col);
+        } else
+            hipLaunchKernelGGL(last ? rtc_denoise_iter_direct<true> : rtc_denoise_iter_direct<false>, grid, block, 0, st, in,
+                               b.guide, d->width, d->rows, s, tilesX, w, next, b.albedo, d->albedoFloor, dOut, col);
     }
     HIP_TRY(hipGetLastError());
     return 0;
 }
-
-/* the host's images as denoise_pixel sees them from pixel (x, y) */
-struct DnHostAt {
-    const float4 *color_, *guide_; /* the centre's entries */
-    long long pitch;
-    int s;
-    float4 color(int i, int j) const { return color_[j * s * pitch + i * s]; }
-    float4 guide(int i, int j) const { return guide_[j * s * pitch + i * s]; }
-};
 
 extern "C" int rtc_denoise_host(const float *accum, const int *samples, const RtcHitBuffers *guides,
                                 const RtcDenoiseDesc *d, float *out, void *colors)
@@ -386,30 +375,27 @@ extern "C" int rtc_denoise_host(const float *accum, const int *samples, const Rt
     float4 *const store = new (std::nothrow) float4[3 * n];
     if (!store)
         return rtc_fail(RTC_ENOMEM, "%s: %zu bytes of host memory", who, 3 * n * sizeof(float4));
-    const float *const normal = guides ? guides->normal : nullptr, *const depth = guides ? guides->depth : nullptr;
-    const float *const albedo = (d->flags & RTC_DN_DEMODULATE) ? guides->albedo : nullptr;
-    float4 *const guide = store;
-    float4 *image[2] = {store + n, store + 2 * n};
+    const DnBuffers b = denoise_buffers(guides, d, store, n);
     for (size_t p = 0; p < n; ++p) {
-        image[0][p] = denoise_load(accum, samples, albedo, p, (float)d->spp, d->albedoFloor);
-        guide[p] = denoise_guide(normal, depth, p);
+        b.image[0][p] = denoise_load(accum, samples, b.albedo, p, (float)d->spp, d->albedoFloor);
+        b.guide[p] = denoise_guide(b.normal, b.depth, p);
     }
     int rc = 0;
     for (int k = 0; k < d->iterations; ++k) {
         const DnWeights w = denoise_weights(d, guides, k);
-        const float4 *const in = image[k & 1];
-        float4 *const next = image[(k + 1) & 1];
+        const float4 *const in = b.image[k & 1];
+        float4 *const next = b.image[(k + 1) & 1];
         for (int y = 0; y < d->rows; ++y)
             for (int x = 0; x < d->width; ++x) {
                 const size_t p = (size_t)y * (size_t)d->width + (size_t)x;
-                const DnHostAt at = {in + p, guide + p, d->width, 1 << k};
+                const DnGlobalAt at = {in + p, b.guide + p, d->width, 1 << k};
                 next[p] = denoise_pixel(x, y, d->width, d->rows, 1 << k, w, at);
             }
     }
-    const float4 *const last = image[d->iterations & 1];
+    const float4 *const last = b.image[d->iterations & 1];
     for (size_t p = 0; p < n && rc == 0; ++p) {
         float O[3];
-        denoise_store(last[p], albedo, d->albedoFloor, p, O);
+        denoise_store(last[p], b.albedo, d->albedoFloor, p, O);
         out[3 * p] = O[0];
         out[3 * p + 1] = O[1];
         out[3 * p + 2] = O[2];

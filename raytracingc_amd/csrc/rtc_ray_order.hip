@@ -15,6 +15,7 @@
 #include "rtc_layout.h"
 #include "rtc_internal.h"
 #include "rtc_hip_util.h"
+#include "rtc_pass_util.h"
 #include "rtc_staged.h"
 
 /* ---- the sort's shape (rtc_ray_order_shape gives B and G; raytracingc_amd/_abi.py mirrors them as constants and
@@ -123,32 +124,6 @@ __device__ inline unsigned order_wave_rank(unsigned digit, bool valid, unsigned 
     return old + below;
 }
 
-/* The workgroup's exclusive prefix of one value per thread, and the workgroup's sum in `total`; waveSum: kOrderWaves LDS
- * words.  Two barriers; every thread of the workgroup calls it. */
-__device__ inline unsigned order_block_scan(unsigned v, unsigned *waveSum, int lane, int wave, unsigned &total)
-{
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(incl, o);
-        if (lane >= o)
-            incl += u;
-    }
-    if (lane == 63)
-        waveSum[wave] = incl;
-    __syncthreads();
-    unsigned pre = 0, sum = 0;
-#pragma unroll
-    for (int u = 0; u < kOrderWaves; ++u) {
-        const unsigned w = waveSum[u];
-        pre += u < wave ? w : 0u;
-        sum += w;
-    }
-    __syncthreads();
-    total = sum;
-    return pre + incl - v;
-}
-
 /* Per-workgroup digit histogram of one pass: hist[digit * groups + workgroup] = the workgroup's keys of that digit.  Wave w
  * of workgroup g takes keys [g B + w * 1024, + 1024), 64 consecutive keys a round. */
 __global__ __launch_bounds__(kOrderBlock) void rtc_rsort_hist(const unsigned *__restrict__ keys, unsigned n, int shift,
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(kOrderBlock) void rtc_rsort_scan(unsigned *__restri
         const unsigned g = c + (unsigned)t;
         const unsigned v = g < groups ? row[g] : 0u;
         unsigned total;
-        const unsigned excl = order_block_scan(v, waveSum, lane, wave, total);
+        const unsigned excl = rtc_block_scan<kOrderWaves>(v, waveSum, lane, wave, total);
         if (g < groups)
             row[g] = carry + excl;
         carry += total;
@@ -215,8 +190,8 @@ __global__ __launch_bounds__(kOrderBlock) void rtc_rsort_scatter(const unsigned 
 #pragma unroll
     for (int w = 0; w < kOrderWaves; ++w)
         cnt[w][t] = 0;
-    unsigned all;
-    const unsigned digitBase = order_block_scan(totals[t], waveSum, lane, wave, all); /* (its barriers cover the zeroing) */
+    unsigned all; /* (the scan's barriers cover the zeroing) */
+    const unsigned digitBase = rtc_block_scan<kOrderWaves>(totals[t], waveSum, lane, wave, all);
     const unsigned base = blockIdx.x * (unsigned)kOrderKeysPerGroup + (unsigned)(wave * kOrderKeysPerWave);
     unsigned key[kOrderRounds], rank[kOrderRounds];
 #pragma unroll
@@ -391,13 +366,11 @@ extern "C" int rtc_ray_order_async(const RtcDeviceScene *s, const Ray *dRays, si
     const char *const who = "rtc_ray_order_async";
     if (const int rc = refuse_order(who, s, dRays, dOrder, n))
         return rc;
-    if (!dScratch)
-        return rtc_fail(RTC_EINVAL, "%s: null scratch", who);
+    if (const int rc = rtc_refuse_scratch(who, dScratch))
+        return rc;
     if (scratchBytes < rtc_ray_order_scratch_bytes(n))
         return rtc_fail(RTC_EINVAL, "%s: %zu bytes of scratch, %zu rays need %zu (rtc_ray_order_scratch_bytes)", who,
                         scratchBytes, n, rtc_ray_order_scratch_bytes(n));
-    if (((size_t)dScratch & 15) != 0)
-        return rtc_fail(RTC_EINVAL, "%s: the scratch must be 16-byte aligned", who);
     if (n == 0)
         return 0;
     const RtcKeyBox box = bounds ? key_box(bounds, bounds + 3) : key_box(s->boundsLo, s->boundsHi);
@@ -420,15 +393,11 @@ extern "C" int rtc_ray_order_async(const RtcDeviceScene *s, const Ray *dRays, si
         unsigned *kout = keys[(p + 1) & 1], *iout = idx[(p + 1) & 1];
         hipLaunchKernelGGL(rtc_rsort_hist, groups, block, 0, st, kin, un, shift, ug, hist);
         hipLaunchKernelGGL(rtc_rsort_scan, dim3(kOrderRadix), block, 0, st, hist, ug, totals);
-        if (p == 0)
-            hipLaunchKernelGGL((rtc_rsort_scatter<true, false>), groups, block, 0, st, kin, iin, un, shift, ug, hist,
-                               totals, kout, iout);
-        else if (p == kOrderPasses - 1)
-            hipLaunchKernelGGL((rtc_rsort_scatter<false, true>), groups, block, 0, st, kin, iin, un, shift, ug, hist,
-                               totals, kout, iout);
-        else
-            hipLaunchKernelGGL((rtc_rsort_scatter<false, false>), groups, block, 0, st, kin, iin, un, shift, ug, hist,
-                               totals, kout, iout);
+        /* the first pass, the last, the ones between (in the order the kernels are emitted in) */
+        static constexpr decltype(&rtc_rsort_scatter<true, false>) kScatter[3] = {
+            rtc_rsort_scatter<true, false>, rtc_rsort_scatter<false, true>, rtc_rsort_scatter<false, false>};
+        hipLaunchKernelGGL(kScatter[p == 0 ? 0 : p == kOrderPasses - 1 ? 1 : 2], groups, block, 0, st, kin, iin, un, shift,
+                           ug, hist, totals, kout, iout);
     }
     HIP_TRY(hipGetLastError());
     return 0;

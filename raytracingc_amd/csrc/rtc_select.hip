@@ -13,6 +13,7 @@
 #include "rtc_device.h"
 #include "rtc_internal.h"
 #include "rtc_hip_util.h"
+#include "rtc_pass_util.h"
 
 /* ---- the select's shape (rtc_select_shape gives T and G; raytracingc_amd/_abi.py mirrors them as constants and
  * tests/test_select_abi.py compares the two) ---- */
@@ -40,32 +41,6 @@ __host__ __device__ inline bool select_pixel(const float A[3], const float P[3],
 }
 
 /* ---- kernels ------------------------------------------------------------------------------------------------------ */
-/* The workgroup's exclusive prefix of one value per thread and the workgroup's sum (as the ray sort's order_block_scan);
- * waveSum: kSelWaves LDS words.  Two barriers; every thread of the workgroup calls it. */
-__device__ inline unsigned select_block_scan(unsigned v, unsigned *waveSum, int lane, int wave, unsigned &total)
-{
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(incl, o);
-        if (lane >= o)
-            incl += u;
-    }
-    if (lane == 63)
-        waveSum[wave] = incl;
-    __syncthreads();
-    unsigned pre = 0, sum = 0;
-#pragma unroll
-    for (int u = 0; u < kSelWaves; ++u) {
-        const unsigned w = waveSum[u];
-        pre += u < wave ? w : 0u;
-        sum += w;
-    }
-    __syncthreads();
-    total = sum;
-    return pre + incl - v;
-}
-
 /* Judge.  Workgroup g takes entries [g T, (g + 1) T), wave w of it [g T + 512 w, + 512), 64 consecutive entries a round.
  * Entry i names pixel p = in[i] (LIST) or i; a valid one (i < n and p < pixels) is judged and stamped.  Each round's
  * predicate is one ballot word, stored at mask[i / 64] by lane 0 -- every word below ceil(n / 64) is written, the lanes
@@ -130,7 +105,7 @@ __global__ __launch_bounds__(kSelBlock) void rtc_select_scan(unsigned *__restric
         const unsigned g = c + (unsigned)t;
         const unsigned v = g < groups ? counts[g] : 0u;
         unsigned sum;
-        const unsigned excl = select_block_scan(v, waveSum, lane, wave, sum);
+        const unsigned excl = rtc_block_scan<kSelWaves>(v, waveSum, lane, wave, sum);
         if (g < groups)
             counts[g] = carry + excl;
         carry += sum;
@@ -208,14 +183,10 @@ __global__ __launch_bounds__(kSelBlock) void rtc_select_emit(const unsigned *__r
 /* Resolve.  Byte k of the Color buffer is component k % 3 of pixel k / 3, from accumulator float k: thread g takes the
  * aligned dword g of the buffer (four floats in, one dword out); the bytes before the first aligned dword and after the
  * last are stored singly by the first threads.  head: the bytes before the first aligned dword (0 .. 3, at most `bytes`). */
-__host__ __device__ inline float resolve_scale(float fspp, int s)
-{
-    return s > 0 ? fspp / (float)s : 0.f; /* the correctly rounded f32 division on both sides */
-}
 __device__ inline unsigned resolve_byte(const float *__restrict__ accum, const int *__restrict__ samples, float fspp,
                                         size_t k)
 {
-    return (unsigned)rtcdev::float_to_u8(accum[k] * resolve_scale(fspp, samples[k / 3]));
+    return (unsigned)rtcdev::float_to_u8(accum[k] * rtc_sample_scale(fspp, samples[k / 3]));
 }
 __global__ __launch_bounds__(kSelBlock) void rtc_resolve_colors(const float *__restrict__ accum,
                                                                  const int *__restrict__ samples, float fspp,
@@ -299,10 +270,8 @@ extern "C" int rtc_select_pixels_async(const float *dAccum, const float *dPrev, 
     if (const int rc = refuse_select(who, dAccum, dPrev, pixelCount, dIn, nIn, sel, dOut, capacity, dCount, dSamples))
         return rc;
     const size_t n = dIn ? nIn : pixelCount; /* the input sequence's length */
-    if (!dScratch)
-        return rtc_fail(RTC_EINVAL, "%s: null scratch", who);
-    if (((size_t)dScratch & 15) != 0)
-        return rtc_fail(RTC_EINVAL, "%s: the scratch must be 16-byte aligned", who);
+    if (const int rc = rtc_refuse_scratch(who, dScratch))
+        return rc;
     if (scratchBytes < rtc_select_scratch_bytes(n))
         return rtc_fail(RTC_EINVAL, "%s: %zu bytes of scratch, %zu entries need %zu (rtc_select_scratch_bytes)", who,
                         scratchBytes, n, rtc_select_scratch_bytes(n));
@@ -313,23 +282,16 @@ extern "C" int rtc_select_pixels_async(const float *dAccum, const float *dPrev, 
     const hipStream_t st = (hipStream_t)stream;
     const dim3 block(kSelBlock);
     const unsigned un = (unsigned)n, ug = (unsigned)L.groups, up = (unsigned)pixelCount, cap = (unsigned)capacity;
-    if (ug) {
-        if (dIn)
-            hipLaunchKernelGGL(rtc_select_judge<true>, dim3(ug), block, 0, st, dAccum, dPrev, up, dIn, un, *sel, mask, counts,
-                               dSamples);
-        else
-            hipLaunchKernelGGL(rtc_select_judge<false>, dim3(ug), block, 0, st, dAccum, dPrev, up, dIn, un, *sel, mask,
-                               counts, dSamples);
-    }
+    if (ug)
+        hipLaunchKernelGGL(dIn ? rtc_select_judge<true> : rtc_select_judge<false>, dim3(ug), block, 0, st, dAccum, dPrev, up,
+                           dIn, un, *sel, mask, counts, dSamples);
     if (dCount || cap)
         hipLaunchKernelGGL(rtc_select_scan, dim3(1), block, 0, st, counts, ug, total, dCount);
     if (cap) {
         const unsigned tailGroups = (cap + (unsigned)kSelTile - 1) / (unsigned)kSelTile;
         const dim3 grid(ug > tailGroups ? ug : tailGroups);
-        if (dIn)
-            hipLaunchKernelGGL(rtc_select_emit<true>, grid, block, 0, st, dIn, un, ug, mask, counts, total, dOut, cap);
-        else
-            hipLaunchKernelGGL(rtc_select_emit<false>, grid, block, 0, st, dIn, un, ug, mask, counts, total, dOut, cap);
+        hipLaunchKernelGGL(dIn ? rtc_select_emit<true> : rtc_select_emit<false>, grid, block, 0, st, dIn, un, ug, mask,
+                           counts, total, dOut, cap);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -401,7 +363,7 @@ extern "C" int rtc_resolve_host(const float *accum, const int *samples, size_t p
         return rc;
     const float fspp = (float)spp;
     for (size_t p = 0; p < pixelCount; ++p) {
-        const float scale = resolve_scale(fspp, samples[p]);
+        const float scale = rtc_sample_scale(fspp, samples[p]);
         const float v[3] = {accum[3 * p] * scale, accum[3 * p + 1] * scale, accum[3 * p + 2] * scale};
         if (const int rc = rtc_quantize(v, 1, (Color *)colors + p)) /* the host's floatToUint */
             return rc;
